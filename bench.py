@@ -3,12 +3,20 @@
 
 Contract (driver):  python bench.py --gpus N --steps K --warmup W   prints ONE JSON line.
 
+* plain run : sets up, warms up (W iterations, at least two hipGraph captures), times EXACTLY K iterations in one region
+              bracketed by barrier + synchronize, writes the outputs when --dump-outputs is given, prints the headline:
+              `value` = steps/s, `ms_per_step` = that region / K (max over ranks).  Nothing else runs.
+* --full    : everything below beside the headline (step()-only rate, repeated regions, ghia, roofline, farm, small_n,
+              cu_batch, CPU baseline); --headline-only, --no-cpu, --no-farm and --leg narrow a --full run.
+* --dump-outputs DIR : after the timed region, what its last step handed a caller (solver.arrays u, v on the full grid, p
+              on the inner grid, and that iteration's history record) as DIR/<name>.npy in float64, at most 64 MB in all
+              (a fixed, seeded sample of an array beyond its share).  The inputs depend on the arguments alone.
 * workload  : BASELINE.json configs[2] -- solver=spectral (SG), N=256, Re=1000, fp64,
               CFL=1.5, beta^2=5, cosine lid smoothing 0.15, fluid initially at rest.
 * a "step"  : one iteration of LidDrivenCavitySolver.solve (reference base.py:243-313):
               adaptive dt, 4 RK stages with BCs, change norms, residual norms and the
               E/Z/P diagnostics -- everything the reference does per iteration.  The
-              step()-only rate (no E/Z/P) is reported beside it as `step_only_value`.
+              step()-only rate (no E/Z/P) is reported beside it as `step_only_value` (--full).
 * N > 1     : one process per GPU, each rank advances its own independent trial (the
               sweep axis of the reference; no data-path collective), `value` is the sum
               over ranks of K / max-over-ranks(time): "weak" scaling.  The barrier and the
@@ -29,19 +37,19 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W   prints ONE J
               code -- AGPR round trips -- not the chip: DESIGN.md section 3).
 * cpu_baseline : the NumPy oracle (a port of the reference, pinned to its golden vectors)
               timed on this host's cores for a bounded sample of the same workload.
-* timed region: EXACTLY K iterations between barrier + synchronize on both sides, max over ranks -- repeated
-              until at least 0.25 s have been timed (K = 20 lasts one millisecond: a single such region measures
-              the host's launch latency, not the device); `ms_per_step` is the MEDIAN region / K, `reps` says how
-              many regions there were, `launch_path` what the K iterations were enqueued as ("graph": hipGraph
-              replays of captures of at most 64 iterations that divide K, "graph+eager" when K has a remainder,
-              "persistent": one launch of the persistent trial kernel).
+* timed region: EXACTLY K iterations between barrier + synchronize on both sides, max over ranks; `launch_path` says
+              what the K iterations were enqueued as ("graph": hipGraph replays of captures of at most 64 iterations
+              that divide K, "graph+eager" when K has a remainder, "persistent": one launch of the persistent trial
+              kernel).  --full adds `regions`: such regions repeated until at least 0.25 s have been timed (K = 20
+              lasts one millisecond: a single such region measures the host's launch latency, not the device), their
+              MEDIAN / K as `ms_per_step` there and `reps`, the number of regions.
 * small_n   : BASELINE.json configs[1] (N=64, Re=400) on the same GPU: full iterations per second through the small-N
               trial kernel (what the solver picks by default at N <= 79) and through the launch path (N = 1 only).
 * cu_batch   : 256 trials of N=32 in one batch (N = 1 only): trial-iterations per second through the trial-per-CU kernel.
 * --gpus N  : started plainly (no WORLD_SIZE in the environment) with N > 1, the process starts N ranks of itself through
               torch.distributed.run BEFORE it touches the GPU, relays rank 0's JSON line and exits with the ranks' code.
-* --headline-only : the headline, its roofline block and nothing else (no farm / small_n / cu_batch / cpu legs): what
-              tools/profile_round.py runs under rocprofv3 so that the kernel statistics carry the N=256 launches alone.
+* --headline-only : (with --full) the headline, its roofline block and nothing else (no farm / small_n / cu_batch / cpu
+              legs): what tools/profile_round.sh runs under rocprofv3 so that the kernel statistics carry the N=256 launches alone.
 * farm      : a second, sweep-shaped measurement for the multi-GPU runs -- every rank advances `trials_per_gpu`
               equal-N trials the way main.py advances the trials a rank owns in the Hydra multirun / Optuna search:
               two batches with shared launches, side by side on two HIP streams of different priority;
@@ -451,6 +459,37 @@ def cu_batch_block(device, N=32, B=256, K=2048):
             "workload": f"{B} SG trials of N={N} in one batch on one GPU (step()-only loop), one work-group per trial"}
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_sample(arrays: dict, limit=DUMP_LIMIT_BYTES, seed=0) -> dict:
+    """float64 copies of `arrays`, flat; an array beyond its equal share of `limit` becomes a fixed, seeded sample of its
+    entries (the same positions for the same size in every run), so that the dump as a whole stays within `limit`."""
+    import numpy as np
+    share = limit // (8 * max(1, len(arrays)))
+    out = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=share, replace=False))
+            a = a[idx]
+        out[name] = a
+    return out
+
+
+def dump_outputs(s, out_dir) -> None:
+    """What the timed path hands its caller after its last step: solver.arrays u and v (full (N+1)^2 grid), p (inner
+    (N-1)^2 grid) and that iteration's history record (relative change, ||R_u||, ||R_v||, ||R_p||, E, Z, P, dt)."""
+    import numpy as np
+    from solvers.spectral import ldc_lib as L
+    it = int(s.d["ctrl"][L.CTRL_ITER])
+    arrays = {"u": s.arrays.u, "v": s.arrays.v, "p": s.arrays.p,
+              "record": s.d["rec"][(it - 1) % s.rec_cap].cpu().numpy()}
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in dump_sample(arrays).items():
+        np.save(d / f"{name}.npy", a)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -459,17 +498,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=400)
     ap.add_argument("--N", type=int, default=WORKLOAD["N"])
     ap.add_argument("--Re", type=float, default=WORKLOAD["Re"])
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-farm", action="store_true", help="skip the batched-trials (sweep-shaped) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: step()-only rate, repeated regions, ghia, roofline, farm, small_n, cu_batch, "
+                         "CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, <= 64 MB)")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) skip the CPU baseline leg")
+    ap.add_argument("--no-farm", action="store_true", help="(--full) skip the batched-trials (sweep-shaped) measurement")
     ap.add_argument("--headline-only", action="store_true",
-                    help="the headline and its roofline block only (what tools/profile_round.py profiles)")
+                    help="(--full) the headline and its roofline block only (what tools/profile_round.sh profiles)")
     ap.add_argument("--leg", default="", choices=["", "farm", "small_n", "cu_batch"],
-                    help="ONE secondary leg only (no headline): what tools/profile_round.sh profiles leg by leg")
+                    help="(--full) ONE secondary leg only (no headline): what tools/profile_round.sh profiles leg by leg")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: the launcher, the rendezvous, the barrier, the max-over-ranks and the gather only (CPU test of --gpus N)")
     ap.add_argument("--persistent", type=int, default=-1,
                     help="-1 the library's choice (N=256: the chip-wide kernel), 0 launch per stage, 3 / 5 the persistent kernels")
     a = ap.parse_args()
+    if not a.full and (a.no_cpu or a.no_farm or a.headline_only or a.leg):
+        ap.error("--no-cpu, --no-farm, --headline-only and --leg narrow a --full run: add --full")
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.headline_only:
         a.no_cpu = a.no_farm = True
 
@@ -556,14 +604,46 @@ def main():
     timed_iterations(s, max(a.warmup, 2 * gi), True, barrier)
     timed_iterations(s, 2 * gi, False, barrier)
 
-    wall, ev, reps = timed_regions(s, a.steps, True, dist)
+    def check_state():
+        ctrl = s.d["ctrl"].cpu().numpy()
+        assert int(ctrl[0]) == 0, "latch fired during the bench (tolerance is 0: must not happen)"
+        rec = s.d["rec"].cpu().numpy()
+        assert bool((rec == rec).all()), "non-finite history record: the timed run diverged"
+        if mode != 0:     # a persistent launch that gave up a barrier wait leaves undefined state, not a rate
+            assert L.lib().ldc_solver_status(s._handle) == 0, "persistent kernel gave up a barrier wait (LDC_E_SYNC)"
+
+    # the headline: ONE region of exactly K iterations, max over ranks
+    wall, ev = timed_iterations(s, a.steps, True, barrier)
+    wall = dist.max_float(wall)
+    check_state()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(s, a.dump_outputs)
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "steady-state time-steps/sec at N=256 Re=1000",
+            "value": world * a.steps / wall, "unit": "steps/s", "n_gpus": world, "steps": a.steps,
+            "warmup": a.warmup, "ms_per_step": 1e3 * wall / a.steps, "launch_path": launch_path,
+            "solver_mode": mode, "graph_iters": gi, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"solver=spectral (SG) N={a.N} Re={a.Re:g} fp64, full solve() iteration "
+                                   "(dt, 4 RK stages + BCs, change/residual norms, E/Z/P), fluid from rest",
+                       "N": a.N, "Re": a.Re, "CFL": 1.5, "beta_squared": 5.0, "corner_smoothing": 0.15,
+                       "trials_per_gpu": 1, "parallelism": f"{world} independent trial(s), one per GPU"},
+            "event_ms_per_step": 1e3 * ev / a.steps,
+            "full": a.full,
+        }
+    if not a.full:
+        s.close()
+        barrier()
+        dist.close()
+        if rank == 0:
+            print(json.dumps(out))
+        return
+
+    wall_r, ev_r, reps = timed_regions(s, a.steps, True, dist)
     wall_so, _, _ = timed_regions(s, a.steps, False, dist)
-    ctrl = s.d["ctrl"].cpu().numpy()
-    assert int(ctrl[0]) == 0, "latch fired during the bench (tolerance is 0: must not happen)"
-    rec = s.d["rec"].cpu().numpy()
-    assert bool((rec == rec).all()), "non-finite history record: the timed run diverged"
-    if mode != 0:     # a persistent launch that gave up a barrier wait leaves undefined state, not a rate
-        assert L.lib().ldc_solver_status(s._handle) == 0, "persistent kernel gave up a barrier wait (LDC_E_SYNC)"
+    check_state()
 
     farm = None
     if not a.no_farm:
@@ -582,7 +662,6 @@ def main():
                            "rounds, at most 2.7x) and offers the reference's own ask-n_jobs / tell-n_jobs sequence as "
                            "search_mode=reference (no scaling beyond batching) -- DESIGN.md 3"}
 
-    out = None
     if rank == 0:
         M = a.N + 1
         peak_meas = mfma_peak_measured()
@@ -636,22 +715,15 @@ def main():
         # (76 M^3 + 2 M Mi (M + Mi)) over ms_per_step -- launch gaps and per-chunk costs included
         roof["iteration_frac"] = f_iter * a.steps / wall / 1e12 / PEAK_FP64_MFMA_TFLOPS
         roof["iteration_flops"] = f_iter
-        out = {
-            "metric": "steady-state time-steps/sec at N=256 Re=1000",
-            "value": world * a.steps / wall, "unit": "steps/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": 1e3 * wall / a.steps, "reps": reps, "launch_path": launch_path,
-            "solver_mode": mode, "graph_iters": gi, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"solver=spectral (SG) N={a.N} Re={a.Re:g} fp64, full solve() iteration "
-                                   "(dt, 4 RK stages + BCs, change/residual norms, E/Z/P), fluid from rest",
-                       "N": a.N, "Re": a.Re, "CFL": 1.5, "beta_squared": 5.0, "corner_smoothing": 0.15,
-                       "trials_per_gpu": 1, "parallelism": f"{world} independent trial(s), one per GPU"},
+        out.update({
+            "regions": {"value": world * a.steps / wall_r, "ms_per_step": 1e3 * wall_r / a.steps, "reps": reps,
+                        "event_ms_per_step": 1e3 * ev_r / a.steps,
+                        "statistic": "median of regions of K iterations repeated until 0.25 s were timed"},
             "step_only_value": world * a.steps / wall_so, "step_only_ms": 1e3 * wall_so / a.steps,
-            "event_ms_per_step": 1e3 * ev / a.steps,
             "iteration_tflops": f_iter * a.steps / wall / 1e12,
             "ghia": ghia_block(a.N, a.Re),
             "roofline": roof,
-        }
+        })
         out["farm"] = farm
         out["small_n"] = small_n_block(f"cuda:{local}") if (world == 1 and not a.headline_only) else None
         out["cu_batch"] = cu_batch_block(f"cuda:{local}") if (world == 1 and not a.headline_only) else None

@@ -99,3 +99,29 @@ def test_plain_gpus_2_starts_its_own_ranks(tmp_path):
     r2 = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "3", "--dry-run"], capture_output=True, text=True,
                         env=env2, timeout=120, cwd=tmp_path)
     assert r2.returncode != 0 and "WORLD_SIZE=2" in (r2.stderr + r2.stdout)
+
+
+def test_dump_sample_keeps_the_budget():
+    """--dump-outputs stays within its byte budget: small arrays pass whole as float64, a larger one becomes a fixed, seeded
+    sample of its entries (the same in every run)."""
+    import numpy as np
+    b = _bench()
+    small = {"u": np.arange(10, dtype=np.float32), "rec": np.ones(8)}
+    out = b.dump_sample(small, limit=1024)
+    assert all(a.dtype == np.float64 for a in out.values())
+    assert np.array_equal(out["u"], np.arange(10)) and np.array_equal(out["rec"], np.ones(8))
+    big = {"u": np.arange(1000.0).reshape(10, 100), "p": np.arange(50.0)}
+    one, two = b.dump_sample(big, limit=800), b.dump_sample(big, limit=800)
+    assert sum(a.nbytes for a in one.values()) <= 800 and one["u"].size == 50 and np.array_equal(one["p"], np.arange(50.0))
+    assert np.array_equal(one["u"], two["u"]) and len(np.unique(one["u"])) == 50
+    assert b.DUMP_LIMIT_BYTES == 64 * 2**20
+
+
+def test_secondary_measurements_need_full(tmp_path):
+    """A plain run measures the headline alone: the options that narrow the --full run are refused without it."""
+    import subprocess
+    import sys
+    for opt in (["--no-cpu"], ["--no-farm"], ["--headline-only"], ["--leg", "farm"]):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py")] + opt, capture_output=True, text=True, timeout=120,
+                           cwd=tmp_path)
+        assert r.returncode == 2 and "--full" in r.stderr, (opt, r.stderr)
