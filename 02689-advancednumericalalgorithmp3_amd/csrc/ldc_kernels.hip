@@ -1707,6 +1707,16 @@ struct ldc_solver {
 };
 
 
+// One captured chunk of the chip-wide kernel's batch form (every launch group, the transforms, the closing record) and the
+// event recorded behind its latest launch: a graph executable is destroyed only once that event has completed.
+struct WChunk {
+  int n_iters;               // 0: free slot
+  unsigned long long used;   // last launch, for the least-recently-used eviction
+  hipGraphExec_t exec;
+  hipEvent_t done;
+};
+constexpr int kWChunkCache = 3;
+
 // B independent trials of identical geometry advanced by every launch (blockIdx.y = trial).
 struct ldc_batch {
   int B;
@@ -1722,6 +1732,10 @@ struct ldc_batch {
   unsigned* d_xsync;         // XG_LEN launch words, then XS_LEN counter words per trial (zeroed before every launch)
   CArgs* d_cargs[2];         // [with_diagnostics] argument blocks of the trial-per-CU kernel
   WArgs* d_wargs[2];         // [with_diagnostics] argument blocks of the chip-wide kernel
+  int wT, wtail, wG;         // chip-wide kernel: tiles per axis, layout, trials per launch (wG = 0: it cannot run this batch)
+  int wide_knob;             // LDC_BATCH_WIDE=1 at creation: auto-mode trials take the chip-wide kernel too
+  WChunk wchunk[2][kWChunkCache];      // [with_diagnostics] chunk graphs by length
+  unsigned long long wclock;
   int post_grid[2], postT_grid, post_close_grid, postP_grid;
   int iters_per_graph;
   hipGraphExec_t graph[2];
@@ -2082,16 +2096,21 @@ int launch_xcd(ldc_solver* s, int n_iters, int with_diag, hipStream_t st) {
 // fit (N = 96 ... 240) index M-1 inside the tiles is the faster form with diagnostics (N=128 24.3 against 26.4 us per iteration,
 // N=240 32.5 against 35.1; step-only they are equal: profiles/r04_wide_ab_layouts.log) -- the boundary-line jobs cost more than
 // 2 T + 1 more work-groups.  LDC_WIDE_LAYOUT=tail | tiles picks one where both are possible (tests run both forms of one size).
-bool wide_tail(const ldc_solver* s) {
-  if ((s->p.M - 1) % 16 != 0 || s->p.stage_pressure != 0 || s->p.Mx != s->p.My) return false;
-  const int Tt = (s->p.M + 15) / 16;
-  const bool tiles_fit = Tt <= kWT && Tt * Tt <= s->n_cus;
+bool wide_tail_of(int M, int Mx, int My, int stage_pressure, int n_cus) {
+  if ((M - 1) % 16 != 0 || stage_pressure != 0 || Mx != My) return false;
+  const int Tt = (M + 15) / 16;
+  const bool tiles_fit = Tt <= kWT && Tt * Tt <= n_cus;
   const char* e = getenv("LDC_WIDE_LAYOUT");
   if (e != nullptr && strcmp(e, "tiles") == 0 && tiles_fit) return false;
   if (e != nullptr && strcmp(e, "tail") == 0) return true;
   return !tiles_fit;
 }
+bool wide_tail(const ldc_solver* s) { return wide_tail_of(s->p.M, s->p.Mx, s->p.My, s->p.stage_pressure, s->n_cus); }
 int wide_tiles(const ldc_solver* s) { return wide_tail(s) ? (s->p.M - 1) / 16 : (s->p.M + 15) / 16; }
+// Trials of a batch per launch of the chip-wide kernel: a co-resident launch gets its residency from its grid size alone, so a
+// launch carries as many trials as give every work-group a CU of its own -- floor(n_cus / T^2) (T = 6: 7, 7: 5, 8: 4, 9: 3,
+// 10-11: 2, 12-16: 1) -- and further launches cover the rest of the batch.  0: the kernel does not take T.
+int wide_group_of(int T, int n_cus) { return (T >= kWTmin && T <= kWT && T * T <= n_cus) ? n_cus / (T * T) : 0; }
 // one work-group per CU, all of them resident at once; the packed arrays hold T x T blocks; a partial-sum row per tile; the
 // flags and the ring scratch of the trial in its sync array
 bool wide_available(const ldc_solver* s) {
@@ -2167,6 +2186,12 @@ int launch_wide(ldc_solver* s, int n_iters, int with_diag, hipStream_t st) {
   wl.one = make_wargs(s, with_diag);
   HIP_TRY(hipMemsetAsync(s->p.sync + LDC_SYNC_WFLAGS, 0, sizeof(uint32_t) * 32 * T * T, st));
   return wide_launch_any(wl, T, s->p.stage_pressure != 0, with_diag != 0, wide_tail(s), st);
+}
+// The hand-over flags of a launch group's trials (blockIdx.y = trial of the group), each in its own sync array: one launch
+// instead of a memset per trial.
+__global__ void wide_flags_zero_kernel(const WArgs* trials, int words) {
+  unsigned* f = trials[blockIdx.y].flags;
+  for (int k = (int)(blockIdx.x * blockDim.x + threadIdx.x); k < words; k += (int)(gridDim.x * blockDim.x)) f[k] = 0u;
 }
 
 // ---- trial-per-CU kernel (mode 4) ------------------------------------------------------------------------------
@@ -2394,7 +2419,7 @@ size_t batch_bytes(int B) {
   auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
   return 4 * up(sizeof(StageArgs) * B) + 6 * up(sizeof(PostArgs) * B) + up(sizeof(PalinArgs) * B) +
          up(sizeof(FinalArgs) * B) + 2 * up(sizeof(XArgs) * B) + up(sizeof(uint32_t) * (XG_LEN + (size_t)XS_LEN * B)) +
-         2 * up(sizeof(CArgs) * B);
+         2 * up(sizeof(CArgs) * B) + 2 * up(sizeof(WArgs) * B);
 }
 
 int batch_launch_stage(ldc_batch* b, int k, int diag, hipStream_t st) {
@@ -2435,6 +2460,63 @@ int batch_closing_diagnostics(ldc_batch* b, hipStream_t st) {
   if ((e = (int)hipGetLastError()) != 0) return e;
   hipLaunchKernelGGL(finalize_kernel<true>, dim3(1, b->B), dim3(kThreads), 0, st, fdummy, (const FinalArgs*)b->d_flush);
   return (int)hipGetLastError();
+}
+
+// Batch form of the chip-wide kernel (mode 5): launch groups of wG trials, each launch wG x T^2 work-groups (one per CU), the
+// group's flags zeroed in front of it; then the transforms of the final pressures and the closing record of every trial, as
+// behind the small-N kernel's batch launches.  The groups run one after another on the stream: the next group's work-groups
+// find the CUs the previous one has left.
+int enqueue_wide_batch_chunk(ldc_batch* b, int n_iters, int with_diag, hipStream_t st) {
+  const ldc_solver* s0 = b->s[0];
+  const int T = b->wT, words = 32 * T * T;
+  for (int lo = 0; lo < b->B; lo += b->wG) {
+    const int g = (b->B - lo < b->wG) ? (b->B - lo) : b->wG;
+    hipLaunchKernelGGL(wide_flags_zero_kernel, dim3((words + kThreads - 1) / kThreads, g), dim3(kThreads), 0, st,
+                       (const WArgs*)(b->d_wargs[with_diag] + lo), words);
+    HIP_TRY(hipGetLastError());
+    WLaunch wl;
+    memset(&wl, 0, sizeof(wl));
+    wl.B = g; wl.n_iters = n_iters; wl.trials = b->d_wargs[with_diag] + lo;
+    const int e = wide_launch_any(wl, T, s0->p.stage_pressure != 0, with_diag != 0, b->wtail != 0, st);
+    if (e) return e;
+  }
+  const PostArgs pdummy = {};
+  hipLaunchKernelGGL(post_kernel<true>, dim3(b->postP_grid, b->B), dim3(kThreads), 0, st, pdummy, (const PostArgs*)b->d_postP);
+  HIP_TRY(hipGetLastError());
+  return with_diag ? batch_closing_diagnostics(b, st) : 0;
+}
+// The chunk of n_iters iterations as ONE graph, kept in a cache of kWChunkCache lengths per diagnostics form (a solve's
+// chunks are check_every long and its last one shorter).  A slot is reused least-recently-used first, and only after the
+// event behind its graph's latest launch has completed: a launch still queued on the caller's stream never loses its graph.
+int batch_wide_chunk(ldc_batch* b, int n_iters, int with_diag, WChunk** out) {
+  WChunk* slots = b->wchunk[with_diag];
+  for (int k = 0; k < kWChunkCache; ++k)
+    if (slots[k].n_iters == n_iters && slots[k].exec) { *out = &slots[k]; return 0; }
+  std::lock_guard<std::mutex> lock(g_setup_mutex);
+  WChunk* c = &slots[0];
+  for (int k = 0; k < kWChunkCache; ++k) {
+    if (slots[k].exec == nullptr) { c = &slots[k]; break; }
+    if (slots[k].used < c->used) c = &slots[k];
+  }
+  if (c->exec) {
+    HIP_TRY(hipEventSynchronize(c->done));
+    (void)hipGraphExecDestroy(c->exec);
+    c->exec = nullptr; c->n_iters = 0;
+  }
+  if (c->done == nullptr) HIP_TRY(hipEventCreateWithFlags(&c->done, hipEventDisableTiming));
+  HIP_TRY(setup_stream(&b->capture_stream));
+  hipGraph_t g = nullptr;
+  HIP_TRY(hipStreamBeginCapture(b->capture_stream, kCaptureMode));
+  const int e = enqueue_wide_batch_chunk(b, n_iters, with_diag, b->capture_stream);
+  const hipError_t ce = hipStreamEndCapture(b->capture_stream, &g);
+  if (e != 0) { if (g) (void)hipGraphDestroy(g); return e; }
+  if (ce != hipSuccess) return (int)ce;
+  const hipError_t ie = hipGraphInstantiate(&c->exec, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  if (ie != hipSuccess) { c->exec = nullptr; return (int)ie; }
+  c->n_iters = n_iters;
+  *out = c;
+  return 0;
 }
 
 int batch_build_graph(ldc_batch* b, int with_diag) {
@@ -2783,6 +2865,12 @@ int ldc_batch_create(ldc_solver* const* solvers, int n_trials, void* workspace, 
   b->iters_per_graph = s0->iters_per_graph;
   b->graph[0] = b->graph[1] = nullptr;
   b->capture_stream = nullptr;
+  memset(b->wchunk, 0, sizeof(b->wchunk));
+  b->wclock = 0;
+  {
+    const char* kn = getenv("LDC_BATCH_WIDE");
+    b->wide_knob = (kn != nullptr && strcmp(kn, "1") == 0) ? 1 : 0;
+  }
   auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
   char* w = static_cast<char*>(workspace);
   auto carve = [&](size_t bytes) { char* r = w; w += up(bytes); return r; };
@@ -2855,6 +2943,22 @@ int ldc_batch_create(ldc_solver* const* solvers, int n_trials, void* workspace, 
       b->d_cargs[wd] = reinterpret_cast<CArgs*>(carve(sizeof(CArgs) * n_trials));
       put(b->d_cargs[wd], hc.data(), sizeof(CArgs) * n_trials);
     }
+    // the chip-wide kernel's blocks; every trial of a launch group must share the tiling and the layout (the kernel takes
+    // T from the group's first block), and the layout is the one of this moment (LDC_WIDE_LAYOUT) for the batch's life.
+    // Batches run the layout with index M-1 inside the tiles only: a batch in the tail layout (N=128, four trials per launch)
+    // once ended one trial's 300 iterations off the lone run's bits ("Batch form"); until that is explained a
+    // batch whose trials take the tail layout keeps today's rule.
+    b->wT = wide_tiles(s0); b->wtail = wide_tail(s0) ? 1 : 0;
+    bool wide_ok = b->wtail == 0;
+    for (int q = 0; q < n_trials; ++q)
+      wide_ok = wide_ok && wide_available(solvers[q]) && wide_tiles(solvers[q]) == b->wT && (wide_tail(solvers[q]) ? 1 : 0) == b->wtail;
+    b->wG = wide_ok ? wide_group_of(b->wT, s0->n_cus) : 0;
+    for (int wd = 0; wd < 2; ++wd) {
+      std::vector<WArgs> hw(n_trials);
+      for (int q = 0; q < n_trials; ++q) hw[q] = make_wargs(solvers[q], wd);
+      b->d_wargs[wd] = reinterpret_cast<WArgs*>(carve(sizeof(WArgs) * n_trials));
+      put(b->d_wargs[wd], hw.data(), sizeof(WArgs) * n_trials);
+    }
   }
   if (he != hipSuccess) { delete b; return (int)he; }
   *out = b;
@@ -2866,6 +2970,11 @@ int ldc_batch_destroy(ldc_batch* b) {
   {
     std::lock_guard<std::mutex> lock(g_setup_mutex);
     for (int q = 0; q < 2; ++q) if (b->graph[q]) (void)hipGraphExecDestroy(b->graph[q]);
+    for (int q = 0; q < 2; ++q)
+      for (WChunk& c : b->wchunk[q]) {
+        if (c.exec) { (void)hipEventSynchronize(c.done); (void)hipGraphExecDestroy(c.exec); }
+        if (c.done) (void)hipEventDestroy(c.done);
+      }
   }
   delete b;
   return 0;
@@ -2889,9 +2998,22 @@ bool batch_uses_cu(const ldc_batch* b) {
   return all_auto && b->B >= need;
 }
 
+// The chip-wide kernel for a batch of N = 81 ... 256 trials: taken when every trial asked for mode 5, or when every trial is in
+// auto mode and LDC_BATCH_WIDE=1 was set when the batch was made (off by default: auto-mode batches stay on the launch path).
+bool batch_uses_wide(const ldc_batch* b) {
+  if (b->wG < 1) return false;        // a trial the kernel cannot run, or trials of different tiling / layout
+  bool all_asked = true, all_auto = true;
+  for (const ldc_solver* t : b->s) {
+    all_asked = all_asked && t->persist_mode == 5;
+    all_auto = all_auto && t->persist_mode == -1;
+  }
+  return all_asked || (all_auto && b->wide_knob != 0);
+}
+
 int ldc_batch_mode(ldc_batch* b) {
   if (!b) return LDC_E_STATE;
   if (batch_uses_cu(b)) return 4;
+  if (batch_uses_wide(b)) return 5;
   bool all_xcd = true;
   for (const ldc_solver* t : b->s) all_xcd = all_xcd && use_xcd(t);
   return all_xcd ? 3 : 0;
@@ -2916,6 +3038,15 @@ int ldc_batch_enqueue(ldc_batch* b, int n_iters, int with_diag, void* stream) {
                        (const PostArgs*)b->d_postP);
     { const int e = (int)hipGetLastError(); if (e) return e; }
     return with_diag ? batch_closing_diagnostics(b, st) : 0;
+  }
+  if (n_iters > 1 && batch_uses_wide(b)) {
+    // chip-wide kernel, launch group after launch group, and the closing launches: one graph per chunk length
+    WChunk* c = nullptr;
+    { const int e = batch_wide_chunk(b, n_iters, with_diag, &c); if (e) return e; }
+    HIP_TRY(hipGraphLaunch(c->exec, st));
+    HIP_TRY(hipEventRecord(c->done, st));
+    c->used = ++b->wclock;
+    return 0;
   }
   {
     // small-N trial kernel: every trial of the batch on an XCD of its own (as many trials per launch as the XCDs hold,
@@ -2957,6 +3088,22 @@ int ldc_batch_enqueue(ldc_batch* b, int n_iters, int with_diag, void* stream) {
   }
   for (; left > 0; --left) { int e = batch_launch_iteration(b, with_diag, st); if (e) return e; }
   return (with_diag && n_iters > 0) ? batch_closing_diagnostics(b, st) : 0;
+}
+
+int ldc_wide_trials_per_launch(int nx, int ny, int stage_pressure, int n_cus) {
+  if (nx < 1 || ny < 1 || n_cus < 1) return 0;
+  // the geometry the Python solver builds (solvers/spectral/sg.py): M = max(nx, ny) + 1, LD = 16 T' + 16 with T' the
+  // launch path's tiles per axis, the partial-sum rows of T'^2 tiles plus the tail layout's edge blocks
+  const int Mx = nx + 1, My = ny + 1, M = Mx > My ? Mx : My;
+  int Tp = (M - 1 + 15) / 16;
+  const int ptail = (16 * Tp == M - 1 && Tp <= 16 && Mx == My) ? 1 : 0;
+  if (16 * Tp == M - 1 && !ptail) ++Tp;
+  const int LD = 16 * Tp + 16;
+  const int64_t stride = (int64_t)(Tp * Tp + (ptail ? (2 * M - 1 + 3) / 4 : 0)) * LDC_NPART;
+  if (wide_tail_of(M, Mx, My, stage_pressure, n_cus)) return 0;      // (batches run the tiles layout only: ldc_batch_create)
+  const int T = (M + 15) / 16;
+  if (LD / 16 < T || stride < (int64_t)PS_N * ((T * T + 3) & ~3) || wlds_bytes(T) + 256 > kLdsLimit) return 0;
+  return wide_group_of(T, n_cus);
 }
 
 int ldc_pack(const double* src, double* dst, int LD, void* stream) {

@@ -1215,6 +1215,11 @@ __global__ __launch_bounds__(kStageThreads, 2) void wide_kernel(const WLaunch L)
   const WLds Ld = wlds_of(T);
   const int NB = a.NB, M = a.M, LD = a.LD;
   const int I = bx / T, J = bx % T;
+  // Everything past the geometry (T, and NB / M / LD, equal in a launch group) comes from the trial's own block `a`: its state,
+  // ctrl / scal words, flags, give-up word, ring / rvec / wedge / jobs, partials.  A trial latched before the launch (converged,
+  // capped by the host, NaN) leaves at once -- every work-group of the trial reads the same word, nobody writes it before the
+  // exit -- and touches nothing, its own words or another trial's of the group.
+  if (a.fin.ctrl[LDC_CTRL_DONE] != 0) return;
   if (tid == 0) {
     S.done = a.fin.ctrl[LDC_CTRL_DONE]; S.iter = a.fin.ctrl[LDC_CTRL_ITER]; S.step = a.fin.ctrl[LDC_CTRL_STEP];
     S.flushed = a.fin.ctrl[LDC_CTRL_FLUSHED]; S.pdone = a.fin.ctrl[LDC_CTRL_PDONE]; S.drows = a.fin.ctrl[LDC_CTRL_DROWS];

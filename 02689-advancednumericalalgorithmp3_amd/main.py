@@ -119,6 +119,23 @@ def _device_cus(device: str = None) -> int:
     return int(cus.value)
 
 
+def one_wide_batch(cfgs: list, n_cus: int, knob: str = None) -> bool:
+    """Whether an equal-N group stays ONE batch because the library advances it on the chip-wide kernel's batch form
+    (ldc_batch_mode 5: every trial asked for ``persistent=5``, or every trial is in auto mode and ``LDC_BATCH_WIDE=1``)
+    with at least two trials per launch.  Halves on two streams would only take turns at the chip: co-resident launches
+    run one at a time per device (ldc_lib.resident_lock).  ``knob``: the value of LDC_BATCH_WIDE (default: the
+    environment's)."""
+    if knob is None:
+        knob = os.environ.get("LDC_BATCH_WIDE", "")
+    modes = {int(c["solver"].get("persistent", -1)) for c in cfgs}
+    if not (modes == {5} or (modes == {-1} and knob == "1")):
+        return False
+    from solvers.spectral import ldc_lib as L
+    n = int(cfgs[0]["N"])
+    fsg = cfgs[0]["solver"]["_target_"].endswith("FSGSolver")      # (its fine level runs the smoother: stage pressures)
+    return L.lib().ldc_wide_trials_per_launch(n, n, 1 if fsg else 0, int(n_cus)) >= 2
+
+
 def run_batches(groups: list, device: str = None) -> list:
     """groups: [(cfgs, out_dirs)], each a set of SG (or FSG) trials of equal N that can share their launches.
     Returns the record lists in the same order.
@@ -142,6 +159,9 @@ def run_batches(groups: list, device: str = None) -> list:
         n = int(cfgs[0]["N"])
         if n_workers > 1 and ((n + 15) // 16) ** 2 >= n_cus:
             parts = len(cfgs)
+        # a group the chip-wide kernel advances several trials per launch of (batch mode 5) stays one batch
+        if parts > 1 and one_wide_batch(cfgs, n_cus):
+            parts = 1
         # sizes the small-N trial kernel advances (SG: N <= 79; FSG: the coarse levels, where the time goes) run every
         # trial on an XCD of its own inside ONE launch: halves on two streams would only take turns at the chip
         sv = cfgs[0]["solver"]

@@ -6,9 +6,11 @@ occupies 64 of the 256 CUs of an MI355X (one 16x16 tile per work-group), an N=64
 batching B trials into every launch (``blockIdx.y`` = trial) fills the chip and amortises the per-launch
 fixed cost.  Each trial keeps its own state, Re / lid profile / tolerance, dt, latch and history, so results
 are bit-identical to running the trials one after another WITH THE SAME KERNEL (tests/test_gpu_batched.py).
-Which kernel that is -- ``kernel_mode``: 0 the launch path, 3 one XCD per trial, 4 one CU per trial -- depends in
-auto mode (``persistent=-1``) on the size and on how many trials share the batch (mode 4 from 80 trials, 32 at
-N=32; a lone N>=80 trial takes mode 5, a batch of them the launch path).  The kernels agree to rounding
+Which kernel that is -- ``kernel_mode``: 0 the launch path, 3 one XCD per trial, 4 one CU per trial, 5 the chip-wide
+kernel (N = 81 ... 256: T x T work-groups per trial, one per CU, ``ldc_wide_trials_per_launch`` trials per launch) --
+depends in auto mode (``persistent=-1``) on the size and on how many trials share the batch (mode 4 from 80 trials, 32
+at N=32; a lone N>=80 trial takes mode 5, a batch of them the launch path unless ``LDC_BATCH_WIDE=1``).  A batch whose
+trials all ask for ``persistent=5`` takes mode 5 wherever it applies.  The kernels agree to rounding
 (<= 1e-12 over a fixture trajectory), not bit for bit, so an iteration count at the stopping threshold can move
 by one with the batch size.  Every trial's ``results.json`` carries ``kernel_mode``; a study that must not depend
 on batch size, world size or search-round size pins one (``LDC_PIN_MODE=0|3``, or ``search_mode=reference``
@@ -81,7 +83,7 @@ class BatchedSGSolver:
             L.check(lib.ldc_batch_create(arr, B, base, nbytes, L.stream_ptr(dev), C.byref(h)), "ldc_batch_create")
         self._batch = h
         self._batch_keys = [s._handle_key for s in self.solvers]
-        # which kernel advances these trials (0 launch path, 3 one XCD per trial, 4 one CU per trial): in auto mode that
+        # which kernel advances these trials (0 launch path, 3 one XCD per trial, 4 one CU per trial, 5 chip-wide): in auto mode that
         # depends on the size AND on how many trials share the batch -- every trial's record says which it was
         self.kernel_mode = int(lib.ldc_batch_mode(h))
         for s in self.solvers:
@@ -159,7 +161,7 @@ class BatchedSGSolver:
         def words(key):
             return torch.stack([s.d[key] for s in self.solvers]).cpu().numpy()
         starts = [int(x) for x in words("ctrl")[:, L.CTRL_ITER]]
-        resident = int(n_iters) > 1 and self.kernel_mode in (3, 4)
+        resident = int(n_iters) > 1 and self.kernel_mode in (3, 4, 5)
         lock = L.resident_lock(dev.index or 0) if resident else contextlib.nullcontext()
         with lock, torch.cuda.device(dev):        # (see ldc_lib.resident_lock: co-resident launches one at a time per device)
             L.check(L.lib().ldc_batch_enqueue(self._batch, int(n_iters), int(bool(diagnostics)), L.stream_ptr(dev)),

@@ -101,6 +101,7 @@ def lib() -> C.CDLL:
     L.ldc_batch_create.argtypes = [C.POINTER(_dp), C.c_int, _dp, C.c_size_t, _dp, C.POINTER(_dp)]
     L.ldc_batch_destroy.argtypes = [_dp]
     L.ldc_batch_enqueue.argtypes = [_dp, C.c_int, C.c_int, _dp]
+    L.ldc_wide_trials_per_launch.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     L.ldc_residual_debug.argtypes = [_dp, C.c_int, C.POINTER(_dp), _dp]
     L.ldc_gemm_nt.argtypes = [_dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
     L.ldc_poisson_fastdiag.argtypes = [_dp] * 10 + [C.c_int, C.c_int, _dp]
@@ -127,7 +128,7 @@ EXPORTS = (
     "ldc_stage", "ldc_pressure_transform", "ldc_diagnostics", "ldc_finalize", "ldc_prime", "ldc_global_quantities",
     "ldc_solver_enqueue", "ldc_solver_set_graph_iters", "ldc_solver_set_persistent", "ldc_solver_status", "ldc_solver_mode", "ldc_batch_mode", "ldc_device_info", "ldc_attribute_rounds",
     "ldc_residual_debug", "ldc_gemm_nt",
-    "ldc_batch_workspace_bytes", "ldc_batch_create", "ldc_batch_destroy", "ldc_batch_enqueue",
+    "ldc_batch_workspace_bytes", "ldc_batch_create", "ldc_batch_destroy", "ldc_batch_enqueue", "ldc_wide_trials_per_launch",
     "ldc_poisson_fastdiag", "ldc_vortex_extrema", "ldc_vortex_extrema_xy", "ldc_mfma_selftest", "ldc_mfma_peak", "ldc_debug_ablate", "ldc_debug_stamps",
     "ldc_pack", "ldc_stream_priority_range", "ldc_stream_create", "ldc_stream_destroy", "ldc_timing_build",
 )

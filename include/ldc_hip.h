@@ -228,7 +228,8 @@ int ldc_solver_set_graph_iters(ldc_solver *s, int iters_per_graph);
 /* contractions of stage 1.  Needs desc->sync and T*T <= CUs, all of them free (one work-group per CU must be resident at once:   */
 /* LDC_E_SYNC after a bounded wait otherwise); the smoother at M = 16 T + 1 = 257 has no such form (LDC_E_ARG).  Entry and exit    */
 /* state as mode 3; trajectories agree with the other paths to rounding.  Chosen in mode -1 wherever it applies and mode 3 does   */
-/* not (N = 81 ... 256).                                                                                                          */
+/* not (N = 81 ... 256).  A batch whose trials all asked for mode 5 -- or are all in mode -1 while LDC_BATCH_WIDE=1 is set at    */
+/* ldc_batch_create -- runs on it too (ldc_batch_mode 5), in the tiles layout: launch groups of ldc_wide_trials_per_launch trials. */
 /* (measured, profiles/r03_cu_ab.log: the trial-per-CU kernel scales with the number of trials up to 256, the small-N kernel    */
 /*  saturates where its XCDs are full -- 64 trials at ceil(M/16) <= 2 (5.7 M trial-iterations/s), 8 ... 24 above (1.9 M); the    */
 /*  thresholds are where the two lines cross: profiles/r03_cu_ab_thresholds.log)                                                                                     */
@@ -236,7 +237,7 @@ int ldc_solver_set_graph_iters(ldc_solver *s, int iters_per_graph);
 #define LDC_CU_AUTO_TRIALS_T3 80     /* ceil(M/16) == 3                                                  */
 #define LDC_CU_AUTO_TRIALS_M33 32    /* M == 33 (N = 32): four tile waves + two edge + two helper waves, not nine tile waves */
 int ldc_solver_set_persistent(ldc_solver *s, int mode);
-/* the mode ldc_solver_enqueue will really use for more than one iteration (0, 1, 2, 3 or 4): what set_persistent asked   */
+/* the mode ldc_solver_enqueue will really use for more than one iteration (0, 3, 4 or 5): what set_persistent asked     */
 /* for, resolved against what the handle's size and device allow.  A host that drives several streams uses it to keep  */
 /* launches that need co-resident work-groups (modes 3, 5) from overlapping each other.                                */
 int ldc_solver_mode(ldc_solver *s);
@@ -267,8 +268,19 @@ int ldc_batch_destroy(ldc_batch *b);
 /* n_iters iterations of base.py:243-313 for every trial that is not latched yet                 */
 int ldc_batch_enqueue(ldc_batch *b, int n_iters, int with_diagnostics, void *stream);
 /* how ldc_batch_enqueue will advance more than one iteration: 0 shared launches per stage (blockIdx.y = trial), 3 the        */
-/* small-N kernel (every trial on an XCD of its own), 4 the trial-per-CU kernel (one work-group per trial)                    */
+/* small-N kernel (every trial on an XCD of its own), 4 the trial-per-CU kernel (one work-group per trial), 5 the chip-wide   */
+/* kernel (a launch carries ldc_wide_trials_per_launch trials, T x T work-groups each, one per CU; further launches cover the  */
+/* rest of the batch).  Mode 5 captures each chunk length as a graph and keeps up to three lengths per diagnostics form; a    */
+/* graph is destroyed (evicted, or at ldc_batch_destroy) only after the event recorded behind its latest launch on the       */
+/* caller's stream has completed, so the caller need not wait between enqueues.  A mode-5 chunk needs its work-groups        */
+/* co-resident: a host that drives several streams keeps it from overlapping other launches of modes 3, 4 and 5.            */
 int ldc_batch_mode(ldc_batch *b);
+/* trials per launch of the chip-wide kernel's batch form for an nx x ny grid built as the Python solver builds it      */
+/* (M = max(nx, ny) + 1) with or without stage pressures (the FSG smoother), on a device of n_cus CUs: floor(n_cus / T^2) */
+/* (T = 6: 7, 7: 5, 8: 4, 9: 3, 10-11: 2, 12-16: 1); 0 where the batch form does not apply: sizes the kernel does not   */
+/* take, and the tail layout (batches run index M-1 inside the tiles only; where LDC_WIDE_LAYOUT or the lone rule gives  */
+/* the tail layout -- N = 256 -- a batch keeps today's rule).  Pure host function: no device is touched.               */
+int ldc_wide_trials_per_launch(int nx, int ny, int stage_pressure, int n_cus);
 
 /* packed twin of a row-major LD x LD array (both device pointers, src != dst); used by the host   */
 /* after it uploads or edits operators / state                                                     */
