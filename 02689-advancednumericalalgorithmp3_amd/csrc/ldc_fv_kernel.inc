@@ -1,0 +1,628 @@
+// ldc_fv_kernel.inc -- the finite-volume SIMPLE solver (include/ldc_fv.h), included at the end of ldc_kernels.hip.
+//
+// Reference: src/solvers/fv/solver.py:170-257 (one SIMPLE iteration), its assembly / discretisation helpers and
+// base.py:202-330 (the loop), 359-450 (E, Z, P by ghost cells).  Quirks: DESIGN.md FV-Q1 ... FV-Q4.
+//
+// Mapping: ONE work-group of 512 threads (8 waves, two per SIMD) advances ONE trial for a whole chunk of iterations.
+// A SIMPLE iteration is a sequence of cell sweeps (each thread takes cells tid, tid + 512, ...) separated by
+// __syncthreads(); every scalar the iteration needs (BiCGSTAB dots, norms, the latch, E / Z / P) is a work-group
+// reduction through LDS.  No work-group ever waits for another, so a batch launch is B independent work-groups:
+// no flags, no spin limits, no co-residency.  512 threads rather than 1024: the iteration's live state takes ~175
+// VGPRs, which two waves per SIMD allow; with four (1024 threads, 128 VGPRs) the kernel spilled ~400 registers to
+// scratch.  The state of an N = 128 trial (32 vectors of 128 KB) stays L2-resident.
+//
+// Momentum: u and v share one matrix (the assembly depends on mdot and mu only), kept as five diagonals with aP
+// unrelaxed; the relaxed diagonal is aP / alpha_uv.  Both systems run through ONE BiCGSTAB loop (Jacobi
+// preconditioner, SciPy's iteration and stopping rule per component), so each iteration's reductions serve both.
+// Pressure correction: the pinned Neumann Laplacian is solved exactly by fast diagonalisation, four GEMMs on fp64 MFMA
+// (v_mfma_f64_16x16x4_f64) with the eigenvectors the host computed once.
+
+#include "ldc_fv.h"
+
+namespace {
+
+constexpr int kFvThreads = 512;
+constexpr int kFvWaves = kFvThreads / 64;
+constexpr int kFvRed = 10;                  // most values one reduction carries
+
+// work vectors (n doubles each), in the order of LDC_FV_NWORK
+enum FvVec {
+  FV_GPX, FV_GPY, FV_AP, FV_AW, FV_AE, FV_AS, FV_AN,
+  FV_XU, FV_XV, FV_RU, FV_RV, FV_RTU, FV_RTV, FV_PU, FV_PV, FV_VU, FV_VV,
+  FV_PHU, FV_PHV, FV_SHU, FV_SHV, FV_TU, FV_TV,
+  FV_C, FV_W1, FV_W2, FV_Y, FV_UP, FV_VP, FV_OMEGA, FV_BU, FV_BV,
+  FV_NVEC
+};
+static_assert(FV_NVEC == LDC_FV_NWORK, "work vectors");
+
+struct FvDesc {
+  int nx, ny, scheme, rec_cap, warmup, maxit;
+  double dx, dy, rho, mu, alpha_uv, alpha_p, lin_tol, tol, lid;
+  const double *ulid, *Qx, *lamx, *Qy, *lamy;
+  double *u, *v, *p, *mdot, *work, *rec;
+  long long *ctrl;
+};
+static_assert(sizeof(FvDesc) <= LDC_FV_DESC_DOUBLES * sizeof(double), "descriptor slot");
+
+struct FvLaunch {
+  const FvDesc* d[LDC_FV_LAUNCH_MAX];
+  int n_iters;
+};
+
+struct FvDebug {
+  double* out[LDC_FV_DBG_COUNT];
+};
+
+// sums of K values over the work-group; every thread gets the same totals (fixed order: bit-reproducible)
+template <int K>
+__device__ inline void fv_reduce(double (&a)[K], double* lds) {
+  static_assert(K <= kFvRed, "reduction slot");
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a[k] += __shfl_xor(a[k], off);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) lds[w * kFvRed + k] = a[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    double s = 0.0;
+#pragma unroll 1
+    for (int q = 0; q < kFvWaves; ++q) s += lds[q * kFvRed + k];
+    a[k] = s;
+  }
+}
+
+__device__ inline double fv_muscl(double r) {
+  return r > 0 ? fmax(0.0, fmin(fmin(2.0, 2.0 * r), 0.5 * (1 + r))) : 0.0;
+}
+
+// TVD deferred correction of a face with owner value fP (west / south cell), neighbour value fN and flux m (P -> N).
+// FV-Q1: for m >= 0 the reference's compiled code leaves psi unassigned; the stored converged fields select
+// psi = MUSCL(r) by the same formula as the m < 0 branch (profiles/fv_q1_table.md).
+__device__ inline double fv_dc(double m, double fP, double fN) {
+  double up, down, r;
+  const double F_low = m * (m >= 0 ? fP : fN);
+  if (m >= 0) {
+    up = fP; down = fN;
+    const double fW = 2 * fP - fN;
+    r = (fN - fP) / (fP - fW + 1e-12);
+  } else {
+    up = fN; down = fP;
+    const double fW = 2 * fN - fP;
+    r = (fP - fN) / (fN - fW + 1e-12);
+  }
+  const double psi = fv_muscl(r);
+  return m * (up + 0.5 * psi * (down - up)) - F_low;
+}
+
+// central-difference gradient with the reference's rules (structured_gradient.py): the pinned cell 0 has a zero
+// gradient, its neighbours skip it, a wall cell averages the one-sided differences it has
+__device__ inline void fv_grad(const double* f, int c, int i, int j, int nx, int ny, double dx, double dy,
+                               double& gx, double& gy) {
+  gx = 0.0; gy = 0.0;
+  if (c == 0) return;
+  const double fc = f[c];
+  double sx = 0.0, sy = 0.0;
+  int nxc = 0, nyc = 0;
+  if (i > 0 && c - 1 != 0) { sx += (f[c - 1] - fc) / (-dx); ++nxc; }
+  if (i < nx - 1) { sx += (f[c + 1] - fc) / dx; ++nxc; }
+  if (j > 0 && c - nx != 0) { sy += (f[c - nx] - fc) / (-dy); ++nyc; }
+  if (j < ny - 1) { sy += (f[c + nx] - fc) / dy; ++nyc; }
+  gx = nxc > 0 ? sx / nxc : 0.0;
+  gy = nyc > 0 ? sy / nyc : 0.0;
+}
+
+// y = (relaxed A) x at cell c: diag = aP / alpha_uv
+__device__ inline double fv_matvec(const double* w, int n, const double* x, int c, int i, int j, int nx, int ny,
+                                   double inv_a) {
+  double y = (w[FV_AP * n + c] * inv_a) * x[c];
+  if (i > 0) y += w[FV_AW * n + c] * x[c - 1];
+  if (i < nx - 1) y += w[FV_AE * n + c] * x[c + 1];
+  if (j > 0) y += w[FV_AS * n + c] * x[c - nx];
+  if (j < ny - 1) y += w[FV_AN * n + c] * x[c + nx];
+  return y;
+}
+
+// C[r][c] = sum_k A(r, k) B(k, c) (M x N, row-major), A(r, k) = A[r*sar + k*sak], B(k, c) = B[k*sbk + c*sbc].
+// One wave per 16 x 16 output tile (waves take tiles round-robin), operands read from L2 with zero fill at the edges;
+// SCALE: the fast-diagonalisation epilogue, C[a][b] /= ax*lamx[b] + ay*lamy[a], the (0, 0) zero mode dropped.
+template <bool SCALE>
+__device__ void fv_gemm(const double* A, int sar, int sak, const double* B, int sbk, int sbc, double* Cm, int M,
+                        int N, int K, const double* lamx, const double* lamy, double ax, double ay) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int tn = (N + 15) >> 4, tiles = ((M + 15) >> 4) * tn;
+  for (int t = w; t < tiles; t += kFvWaves) {
+    const int r0 = (t / tn) * 16, c0 = (t % tn) * 16;
+    const int ar = r0 + (lane & 15), bc = c0 + (lane & 15), kq = lane >> 4;
+    v4d acc = {0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < K; k0 += 4) {
+      const int k = k0 + kq;
+      const double a = (ar < M && k < K) ? A[ar * sar + k * sak] : 0.0;
+      const double b = (bc < N && k < K) ? B[k * sbk + bc * sbc] : 0.0;
+      acc = MFMA_F64(a, b, acc);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int row = r0 + (lane >> 4) + 4 * q, col = c0 + (lane & 15);
+      if (row < M && col < N) {
+        double val = acc[q];
+        if (SCALE) val = (row == 0 && col == 0) ? 0.0 : val * (1.0 / (ax * lamx[col] + ay * lamy[row]));
+        Cm[row * N + col] = val;
+      }
+    }
+  }
+}
+
+// the trial's work vectors, recomputed at each use (held as pointers they spill the register file)
+#define gpx (w + FV_GPX * n)
+#define gpy (w + FV_GPY * n)
+#define xu (w + FV_XU * n)
+#define xv (w + FV_XV * n)
+#define ru (w + FV_RU * n)
+#define rv (w + FV_RV * n)
+#define rtu (w + FV_RTU * n)
+#define rtv (w + FV_RTV * n)
+#define pu (w + FV_PU * n)
+#define pv (w + FV_PV * n)
+#define vu (w + FV_VU * n)
+#define vv (w + FV_VV * n)
+#define phu (w + FV_PHU * n)
+#define phv (w + FV_PHV * n)
+#define shu (w + FV_SHU * n)
+#define shv (w + FV_SHV * n)
+#define tu (w + FV_TU * n)
+#define tv (w + FV_TV * n)
+#define Cp (w + FV_C * n)
+#define W1 (w + FV_W1 * n)
+#define W2 (w + FV_W2 * n)
+#define Y (w + FV_Y * n)
+#define up (w + FV_UP * n)
+#define vp (w + FV_VP * n)
+#define om (w + FV_OMEGA * n)
+
+__global__ __launch_bounds__(kFvThreads) void fv_kernel(FvLaunch L, FvDebug dbg) {
+  __shared__ double red[2][kFvWaves * kFvRed];
+  // the descriptor pointer is read straight from the kernarg segment: indexing the by-value array with blockIdx.x
+  // would make the compiler materialise all LDC_FV_LAUNCH_MAX pointers in registers
+  typedef const FvDesc* FvDescPtr;
+  const FvDesc& d = **(const __attribute__((address_space(4))) FvDescPtr*)((kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                                           __builtin_offsetof(FvLaunch, d) + blockIdx.x * sizeof(FvDescPtr));
+  const int nx = d.nx, ny = d.ny, n = nx * ny, tid = threadIdx.x;
+  const int ldx = nx + 1;
+  double* const w = d.work;
+  double* const fx = d.mdot;
+  double* const fy = d.mdot + ny * ldx;
+  const double dx = d.dx, dy = d.dy, V = dx * dy, rho = d.rho;
+  const double Dx = d.mu * dy / dx, Dy = d.mu * dx / dy;
+  const double Dbx = d.mu * dy / (0.5 * dx), Dby = d.mu * dx / (0.5 * dy);
+  const double inv_a = 1.0 / d.alpha_uv, scale = (1.0 - d.alpha_uv) / d.alpha_uv;
+  const double rhotol = 2.220446049250313e-16 * 2.220446049250313e-16;
+  const bool tvd = d.scheme == 1;
+  int rb = 0;
+  long long done = d.ctrl[0], iter = d.ctrl[1], giveups = 0, lin_iters = 0, solves = 0;
+  bool nan_seen = d.ctrl[2] != 0;
+
+  for (int k = 0; k < L.n_iters && !done && !nan_seen; ++k) {
+    // ---- 1. grad p, both momentum matrices (five diagonals), relaxed right-hand sides, BiCGSTAB start -----------
+    double acc[kFvRed] = {0.0};
+    for (int c = tid; c < n; c += kFvThreads) {
+      const int i = c % nx, j = c / nx;
+      double gx, gy;
+      fv_grad(d.p, c, i, j, nx, ny, dx, dy, gx, gy);
+      gpx[c] = gx; gpy[c] = gy;
+      double aP = 0.0, aW = 0.0, aE = 0.0, aS = 0.0, aN = 0.0, bu = 0.0, bv = 0.0;
+      const double uc = d.u[c], vc = d.v[c];
+      if (i > 0) {                 // west face: owner c-1, neighbour c
+        const double m = fx[j * ldx + i];
+        aP += Dx - fmin(m, 0.0); aW = -(fmax(m, 0.0) + Dx);
+        if (tvd) { bu += fv_dc(m, d.u[c - 1], uc); bv += fv_dc(m, d.v[c - 1], vc); }
+      } else {
+        aP += Dbx + (-fx[j * ldx]);
+      }
+      if (i < nx - 1) {            // east face: owner c
+        const double m = fx[j * ldx + i + 1];
+        aP += fmax(m, 0.0) + Dx; aE = fmin(m, 0.0) - Dx;
+        if (tvd) { bu -= fv_dc(m, uc, d.u[c + 1]); bv -= fv_dc(m, vc, d.v[c + 1]); }
+      } else {
+        aP += Dbx + fx[j * ldx + nx];
+      }
+      if (j > 0) {
+        const double m = fy[j * nx + i];
+        aP += Dy - fmin(m, 0.0); aS = -(fmax(m, 0.0) + Dy);
+        if (tvd) { bu += fv_dc(m, d.u[c - nx], uc); bv += fv_dc(m, d.v[c - nx], vc); }
+      } else {
+        aP += Dby + (-fy[i]);
+      }
+      if (j < ny - 1) {
+        const double m = fy[(j + 1) * nx + i];
+        aP += fmax(m, 0.0) + Dy; aN = fmin(m, 0.0) - Dy;
+        if (tvd) { bu -= fv_dc(m, uc, d.u[c + nx]); bv -= fv_dc(m, vc, d.v[c + nx]); }
+      } else {
+        const double mo = fy[ny * nx + i];
+        aP += Dby + mo;
+        bu += (Dby + mo) * d.ulid[i];
+      }
+      w[FV_AP * n + c] = aP; w[FV_AW * n + c] = aW; w[FV_AE * n + c] = aE;
+      w[FV_AS * n + c] = aS; w[FV_AN * n + c] = aN;
+      w[FV_BU * n + c] = bu; w[FV_BV * n + c] = bv;
+      const double hu = (bu - gx * V) + scale * aP * uc;      // Patankar relaxation (helpers.py:6-25)
+      const double hv = (bv - gy * V) + scale * aP * vc;
+      xu[c] = 0.0; xv[c] = 0.0;
+      ru[c] = hu; rtu[c] = hu; rv[c] = hv; rtv[c] = hv;
+      acc[0] += hu * hu; acc[1] += hv * hv;
+    }
+    {
+      double s[2] = {acc[0], acc[1]};
+      fv_reduce(s, red[rb]); rb ^= 1;
+      acc[0] = s[0]; acc[1] = s[1];
+    }
+    // ---- 2. BiCGSTAB for u and v together (SciPy's loop: rtol * |b|, x0 = 0, non-convergence accepted) ---------
+    double atol[2], nr2[2] = {acc[0], acc[1]}, rh[2] = {acc[0], acc[1]}, rh_prev[2] = {0, 0};
+    double alpha[2] = {0, 0}, omega[2] = {0, 0};
+    bool act[2];
+    int its[2] = {0, 0};
+    for (int q = 0; q < 2; ++q) {
+      const double bn = sqrt(nr2[q]);
+      atol[q] = d.lin_tol * bn;
+      act[q] = bn != 0.0;
+    }
+    for (int it = 0; it < d.maxit; ++it) {
+      double beta[2] = {0, 0};
+      for (int q = 0; q < 2; ++q) {
+        if (!act[q]) continue;
+        if (sqrt(nr2[q]) < atol[q] || fabs(rh[q]) < rhotol || (it > 0 && fabs(omega[q]) < rhotol)) {
+          act[q] = false; its[q] = it; continue;
+        }
+        if (it > 0) beta[q] = (rh[q] / rh_prev[q]) * (alpha[q] / omega[q]);
+      }
+      if (!act[0] && !act[1]) break;
+      for (int c = tid; c < n; c += kFvThreads) {
+        const double dg = w[FV_AP * n + c] * inv_a;
+        if (act[0]) { const double pp = it > 0 ? (pu[c] - omega[0] * vu[c]) * beta[0] + ru[c] : ru[c]; pu[c] = pp; phu[c] = pp / dg; }
+        if (act[1]) { const double pp = it > 0 ? (pv[c] - omega[1] * vv[c]) * beta[1] + rv[c] : rv[c]; pv[c] = pp; phv[c] = pp / dg; }
+      }
+      __syncthreads();
+      double s2[2] = {0, 0};
+      for (int c = tid; c < n; c += kFvThreads) {
+        const int i = c % nx, j = c / nx;
+        if (act[0]) { const double y = fv_matvec(w, n, phu, c, i, j, nx, ny, inv_a); vu[c] = y; s2[0] += rtu[c] * y; }
+        if (act[1]) { const double y = fv_matvec(w, n, phv, c, i, j, nx, ny, inv_a); vv[c] = y; s2[1] += rtv[c] * y; }
+      }
+      fv_reduce(s2, red[rb]); rb ^= 1;
+      bool brk[2] = {false, false};
+      for (int q = 0; q < 2; ++q) {
+        if (!act[q]) continue;
+        if (s2[q] == 0.0) { brk[q] = true; continue; }
+        alpha[q] = rh[q] / s2[q];
+      }
+      for (int c = tid; c < n; c += kFvThreads) {
+        const double dg = w[FV_AP * n + c] * inv_a;
+        if (act[0] && !brk[0]) { const double s = ru[c] - alpha[0] * vu[c]; ru[c] = s; shu[c] = s / dg; }
+        if (act[1] && !brk[1]) { const double s = rv[c] - alpha[1] * vv[c]; rv[c] = s; shv[c] = s / dg; }
+      }
+      __syncthreads();
+      double s3[6] = {0, 0, 0, 0, 0, 0};
+      for (int c = tid; c < n; c += kFvThreads) {
+        const int i = c % nx, j = c / nx;
+        if (act[0] && !brk[0]) {
+          const double t = fv_matvec(w, n, shu, c, i, j, nx, ny, inv_a), s = ru[c];
+          tu[c] = t; s3[0] += s * s; s3[1] += t * s; s3[2] += t * t;
+        }
+        if (act[1] && !brk[1]) {
+          const double t = fv_matvec(w, n, shv, c, i, j, nx, ny, inv_a), s = rv[c];
+          tv[c] = t; s3[3] += s * s; s3[4] += t * s; s3[5] += t * t;
+        }
+      }
+      fv_reduce(s3, red[rb]); rb ^= 1;
+      bool fin[2] = {false, false};          // converged on |s|: x += alpha phat and stop
+      for (int q = 0; q < 2; ++q) {
+        if (!act[q]) continue;
+        if (brk[q]) { act[q] = false; its[q] = it + 1; continue; }
+        if (sqrt(s3[3 * q]) < atol[q]) { fin[q] = true; continue; }
+        omega[q] = s3[3 * q + 1] / s3[3 * q + 2];
+      }
+      double s4[4] = {0, 0, 0, 0};
+      for (int c = tid; c < n; c += kFvThreads) {
+        if (act[0]) {
+          if (fin[0]) xu[c] += alpha[0] * phu[c];
+          else {
+            double x = xu[c]; x += alpha[0] * phu[c]; x += omega[0] * shu[c]; xu[c] = x;
+            const double r = ru[c] - omega[0] * tu[c]; ru[c] = r; s4[0] += r * r; s4[1] += rtu[c] * r;
+          }
+        }
+        if (act[1]) {
+          if (fin[1]) xv[c] += alpha[1] * phv[c];
+          else {
+            double x = xv[c]; x += alpha[1] * phv[c]; x += omega[1] * shv[c]; xv[c] = x;
+            const double r = rv[c] - omega[1] * tv[c]; rv[c] = r; s4[2] += r * r; s4[3] += rtv[c] * r;
+          }
+        }
+      }
+      fv_reduce(s4, red[rb]); rb ^= 1;
+      for (int q = 0; q < 2; ++q) {
+        if (!act[q]) continue;
+        if (fin[q]) { act[q] = false; its[q] = it + 1; continue; }
+        nr2[q] = s4[2 * q]; rh_prev[q] = rh[q]; rh[q] = s4[2 * q + 1];
+        its[q] = it + 1;
+      }
+    }
+    for (int q = 0; q < 2; ++q) {
+      if (act[q]) ++giveups;               // still active after max_lin_iters: accepted (scipy_solver.py:45-49)
+      lin_iters += its[q];
+    }
+    solves += 2;
+    __syncthreads();
+    // ---- 3. Rhie-Chow face velocities, mdot*, rhs_p = -div mdot* (rhs_p[0] = 0) -------------------------------
+    double csum[1] = {0.0};
+    for (int c = tid; c < n; c += kFvThreads) {
+      const int i = c % nx, j = c / nx;
+      const double DP = V / (w[FV_AP * n + c] + 1e-14);
+      double flux[4];                      // W, E, S, N in +x / +y
+      for (int f = 0; f < 4; ++f) {
+        const bool xdir = f < 2;
+        const int o = f == 0 ? c - 1 : f == 1 ? c + 1 : f == 2 ? c - nx : c + nx;
+        const bool wall = f == 0 ? i == 0 : f == 1 ? i == nx - 1 : f == 2 ? j == 0 : j == ny - 1;
+        if (wall) { flux[f] = 0.0; continue; }     // boundary velocity has no normal component
+        const int P = (f == 0 || f == 2) ? o : c, N = (f == 0 || f == 2) ? c : o;
+        const double g = 0.5;
+        const double* st = xdir ? xu : xv;
+        const double* gp = xdir ? gpx : gpy;
+        const double DPc = P == c ? DP : V / (w[FV_AP * n + P] + 1e-14);
+        const double DNc = N == c ? DP : V / (w[FV_AP * n + N] + 1e-14);
+        const double Uf = (1.0 - g) * st[P] + g * st[N];
+        const double gbar = g * gp[N] + (1.0 - g) * gp[P];          // interpolate_to_face(grad_p)
+        const double gin = (1.0 - g) * gp[P] + g * gp[N];           // rhie_chow.py's inline interpolation (FV-Q2)
+        const double Df = g * DNc + (1.0 - g) * DPc;
+        flux[f] = rho * ((Uf - Df * (gbar - gin)) * (xdir ? dy : dx));
+      }
+      if (i == 0) fx[j * ldx] = flux[0];
+      fx[j * ldx + i + 1] = flux[1];
+      if (j == 0) fy[i] = flux[2];
+      fy[(j + 1) * nx + i] = flux[3];
+      const double rhs = c == 0 ? 0.0 : -((flux[1] - flux[0]) + (flux[3] - flux[2]));
+      Cp[c] = rhs;
+      csum[0] += rhs;
+      if (dbg.out[LDC_FV_DBG_RHS_P]) dbg.out[LDC_FV_DBG_RHS_P][c] = rhs;
+    }
+    fv_reduce(csum, red[rb]); rb ^= 1;
+    if (tid == 0) Cp[0] = -csum[0];
+    if (dbg.out[LDC_FV_DBG_MDOT_STAR] || dbg.out[LDC_FV_DBG_GRAD_P] || dbg.out[LDC_FV_DBG_DIAG] ||
+        dbg.out[LDC_FV_DBG_B] || dbg.out[LDC_FV_DBG_USTAR] || dbg.out[LDC_FV_DBG_VSTAR]) {
+      for (int c = tid; c < n; c += kFvThreads) {
+        if (dbg.out[LDC_FV_DBG_GRAD_P]) { dbg.out[LDC_FV_DBG_GRAD_P][c] = gpx[c]; dbg.out[LDC_FV_DBG_GRAD_P][n + c] = gpy[c]; }
+        if (dbg.out[LDC_FV_DBG_DIAG]) for (int q = 0; q < 5; ++q) dbg.out[LDC_FV_DBG_DIAG][q * n + c] = w[(FV_AP + q) * n + c];
+        if (dbg.out[LDC_FV_DBG_B]) { dbg.out[LDC_FV_DBG_B][c] = w[FV_BU * n + c]; dbg.out[LDC_FV_DBG_B][n + c] = w[FV_BV * n + c]; }
+        if (dbg.out[LDC_FV_DBG_USTAR]) dbg.out[LDC_FV_DBG_USTAR][c] = xu[c];
+        if (dbg.out[LDC_FV_DBG_VSTAR]) dbg.out[LDC_FV_DBG_VSTAR][c] = xv[c];
+      }
+      __syncthreads();                      // (the face writes above are visible to the copy)
+      if (dbg.out[LDC_FV_DBG_MDOT_STAR]) {
+        const int nf = ny * ldx + (ny + 1) * nx;
+        for (int f = tid; f < nf; f += kFvThreads) dbg.out[LDC_FV_DBG_MDOT_STAR][f] = d.mdot[f];
+      }
+    }
+    __syncthreads();
+    // ---- 4. pressure correction by fast diagonalisation: p' = Qy (Qy^T C Qx / Lambda) Qx^T, minus its cell-0 value
+    const double ax = dy / dx, ay = dx / dy;
+    fv_gemm<false>(d.Qy, 1, ny, Cp, nx, 1, W1, ny, nx, ny, nullptr, nullptr, 0, 0);       // W1 = Qy^T C
+    __syncthreads();
+    fv_gemm<true>(W1, nx, 1, d.Qx, nx, 1, W2, ny, nx, nx, d.lamx, d.lamy, ax, ay);       // W2 = W1 Qx / Lambda
+    __syncthreads();
+    fv_gemm<false>(d.Qy, ny, 1, W2, nx, 1, W1, ny, nx, ny, nullptr, nullptr, 0, 0);      // W1 = Qy W2
+    __syncthreads();
+    fv_gemm<false>(W1, nx, 1, d.Qx, 1, nx, Y, ny, nx, nx, nullptr, nullptr, 0, 0);       // Y = W1 Qx^T
+    __syncthreads();
+    // ---- 5. u' = -D grad p', u = u* + u', p += alpha_p p' (grad of y - y_0 is grad y) -------------------------
+    const double y0 = Y[0];
+    double part[kFvRed] = {0.0};           // du^2, u_old^2, dv^2, v_old^2, u'^2, v'^2, u^2+v^2, div^2, w^2, |grad w|^2
+    for (int c = tid; c < n; c += kFvThreads) {
+      const int i = c % nx, j = c / nx;
+      double gx, gy;
+      fv_grad(Y, c, i, j, nx, ny, dx, dy, gx, gy);
+      const double D = V / (w[FV_AP * n + c] + 1e-14);
+      const double upc = -D * gx, vpc = -D * gy;
+      const double un = xu[c] + upc, vn = xv[c] + vpc, uo = d.u[c], vo = d.v[c];
+      const double pp = Y[c] - y0;
+      d.p[c] += d.alpha_p * pp;
+      d.u[c] = un; d.v[c] = vn; up[c] = upc; vp[c] = vpc;
+      part[0] += (un - uo) * (un - uo); part[1] += uo * uo;
+      part[2] += (vn - vo) * (vn - vo); part[3] += vo * vo;
+      part[4] += upc * upc; part[5] += vpc * vpc; part[6] += un * un + vn * vn;
+      if (dbg.out[LDC_FV_DBG_P_PRIME]) dbg.out[LDC_FV_DBG_P_PRIME][c] = pp;
+      if (dbg.out[LDC_FV_DBG_U_PRIME]) dbg.out[LDC_FV_DBG_U_PRIME][c] = upc;
+      if (dbg.out[LDC_FV_DBG_V_PRIME]) dbg.out[LDC_FV_DBG_V_PRIME][c] = vpc;
+    }
+    __syncthreads();
+    // ---- 6. mdot += rho interp(u', v') . S (walls: rho u'_P |S|, FV-Q4); vorticity with ghost cells -------------
+    for (int c = tid; c < n; c += kFvThreads) {
+      const int i = c % nx, j = c / nx;
+      const double ue = i < nx - 1 ? 0.5 * up[c + 1] + (1.0 - 0.5) * up[c] : up[c];
+      const double vn = j < ny - 1 ? 0.5 * vp[c + nx] + (1.0 - 0.5) * vp[c] : vp[c];
+      if (i == 0) fx[j * ldx] += rho * (up[c] * dy);
+      fx[j * ldx + i + 1] += rho * (ue * dy);
+      if (j == 0) fy[i] += rho * (vp[c] * dx);
+      fy[(j + 1) * nx + i] += rho * (vn * dx);
+      const double vE = i < nx - 1 ? d.v[c + 1] : -d.v[c], vW = i > 0 ? d.v[c - 1] : -d.v[c];
+      const double uN = j < ny - 1 ? d.u[c + nx] : 2 * d.lid - d.u[c], uS = j > 0 ? d.u[c - nx] : -d.u[c];
+      const double wc = (vE - vW) / (2 * dx) - (uN - uS) / (2 * dy);
+      om[c] = wc;
+      part[8] += wc * wc;
+    }
+    __syncthreads();
+    // ---- 7. |div mdot|, palinstrophy, the record row and the latch ---------------------------------------------
+    for (int c = tid; c < n; c += kFvThreads) {
+      const int i = c % nx, j = c / nx;
+      const double dv = (fx[j * ldx + i + 1] - fx[j * ldx + i]) + (fy[(j + 1) * nx + i] - fy[j * nx + i]);
+      part[7] += dv * dv;
+      const double wc = om[c];
+      const double wE = i < nx - 1 ? om[c + 1] : -wc, wW = i > 0 ? om[c - 1] : -wc;
+      const double wN = j < ny - 1 ? om[c + nx] : -wc, wS = j > 0 ? om[c - nx] : -wc;
+      const double gx = (wE - wW) / (2 * dx), gy = (wN - wS) / (2 * dy);
+      part[9] += gx * gx + gy * gy;
+    }
+    fv_reduce(part, red[rb]); rb ^= 1;
+    if (dbg.out[LDC_FV_DBG_MDOT]) {
+      const int nf = ny * ldx + (ny + 1) * nx;
+      for (int f = tid; f < nf; f += kFvThreads) dbg.out[LDC_FV_DBG_MDOT][f] = d.mdot[f];
+    }
+    const double chu = sqrt(part[0]) / (sqrt(part[1]) + 1e-12), chv = sqrt(part[2]) / (sqrt(part[3]) + 1e-12);
+    const double rel = chu > chv ? chu : chv;
+    if (tid == 0) {
+      double* row = d.rec + (long long)k * LDC_FV_REC_LEN;
+      row[0] = rel; row[1] = sqrt(part[4]); row[2] = sqrt(part[5]); row[3] = sqrt(part[7]);
+      row[4] = 0.5 * (part[6] * V); row[5] = 0.5 * (part[8] * V); row[6] = 0.5 * (part[9] * V); row[7] = 0.0;
+    }
+    if (rel != rel) nan_seen = true;
+    else if (iter >= d.warmup && rel < d.tol) done = 1;
+    ++iter;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    d.ctrl[0] = done; d.ctrl[1] = iter; d.ctrl[2] = nan_seen ? 1 : 0;
+    d.ctrl[3] += giveups; d.ctrl[4] += lin_iters; d.ctrl[5] += solves;
+  }
+}
+
+#undef gpx
+#undef gpy
+#undef xu
+#undef xv
+#undef ru
+#undef rv
+#undef rtu
+#undef rtv
+#undef pu
+#undef pv
+#undef vu
+#undef vv
+#undef phu
+#undef phv
+#undef shu
+#undef shv
+#undef tu
+#undef tv
+#undef Cp
+#undef W1
+#undef W2
+#undef Y
+#undef up
+#undef vp
+#undef om
+
+}  // namespace
+
+struct ldc_fv {
+  FvDesc* dev;              // the descriptor in the tail of the trial's work buffer
+  long long* ctrl;
+  int rec_cap;
+  int device;
+};
+
+namespace {
+
+int fv_launch(ldc_fv* const* hs, int n, int n_iters, const FvDebug& dbg, void* stream) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
+  for (int lo = 0; lo < n; lo += LDC_FV_LAUNCH_MAX) {
+    FvLaunch L;
+    const int b = n - lo < LDC_FV_LAUNCH_MAX ? n - lo : LDC_FV_LAUNCH_MAX;
+    for (int q = 0; q < b; ++q) {
+      if (hs[lo + q]->device != dev) return LDC_E_STATE;
+      L.d[q] = hs[lo + q]->dev;
+    }
+    for (int q = b; q < LDC_FV_LAUNCH_MAX; ++q) L.d[q] = nullptr;
+    L.n_iters = n_iters;
+    hipLaunchKernelGGL(fv_kernel, dim3(b), dim3(kFvThreads), 0, as_stream(stream), L, dbg);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldc_fv_version(void) { return LDC_FV_VERSION; }
+
+int ldc_fv_create(const struct ldc_fv_problem* pr, ldc_fv** out) {
+  if (!pr || !out) return LDC_E_ARG;
+  *out = nullptr;
+  if (pr->nx < LDC_FV_MIN_N || pr->nx > LDC_FV_MAX_N || pr->ny < LDC_FV_MIN_N || pr->ny > LDC_FV_MAX_N) return LDC_E_ARG;
+  if (pr->scheme != 0 && pr->scheme != 1) return LDC_E_ARG;
+  if (pr->rec_cap < 1 || pr->warmup < 0 || pr->max_lin_iters < 1) return LDC_E_ARG;
+  if (!(pr->dx > 0) || !(pr->dy > 0) || !(pr->rho > 0) || !(pr->mu > 0)) return LDC_E_ARG;
+  if (!(pr->alpha_uv > 0 && pr->alpha_uv <= 1) || !(pr->alpha_p > 0 && pr->alpha_p <= 1)) return LDC_E_ARG;
+  if (!(pr->lin_tol > 0) || !(pr->tol >= 0)) return LDC_E_ARG;
+  const void* req[] = {pr->ulid, pr->Qx, pr->lamx, pr->Qy, pr->lamy, pr->u, pr->v, pr->p, pr->mdot, pr->work,
+                       pr->rec, pr->ctrl};
+  for (const void* q : req) if (!q) return LDC_E_ARG;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
+  FvDesc h;
+  h.nx = pr->nx; h.ny = pr->ny; h.scheme = pr->scheme; h.rec_cap = pr->rec_cap; h.warmup = pr->warmup;
+  h.maxit = pr->max_lin_iters;
+  h.dx = pr->dx; h.dy = pr->dy; h.rho = pr->rho; h.mu = pr->mu; h.alpha_uv = pr->alpha_uv; h.alpha_p = pr->alpha_p;
+  h.lin_tol = pr->lin_tol; h.tol = pr->tol; h.lid = pr->lid_velocity;
+  h.ulid = pr->ulid; h.Qx = pr->Qx; h.lamx = pr->lamx; h.Qy = pr->Qy; h.lamy = pr->lamy;
+  h.u = pr->u; h.v = pr->v; h.p = pr->p; h.mdot = pr->mdot; h.work = pr->work; h.rec = pr->rec;
+  h.ctrl = reinterpret_cast<long long*>(pr->ctrl);
+  FvDesc* slot = reinterpret_cast<FvDesc*>(pr->work + (int64_t)LDC_FV_NWORK * pr->nx * pr->ny);
+  const hipError_t e = hipMemcpy(slot, &h, sizeof(h), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return (int)e;
+  ldc_fv* s = new (std::nothrow) ldc_fv;
+  if (!s) return LDC_E_STATE;
+  s->dev = slot; s->ctrl = h.ctrl; s->rec_cap = pr->rec_cap; s->device = dev;
+  *out = s;
+  return 0;
+}
+
+int ldc_fv_destroy(ldc_fv* h) {
+  if (!h) return LDC_E_STATE;
+  delete h;
+  return 0;
+}
+
+int ldc_fv_enqueue(ldc_fv* h, int n_iters, void* stream) {
+  if (!h) return LDC_E_STATE;
+  if (n_iters < 1 || n_iters > h->rec_cap) return LDC_E_ARG;
+  FvDebug dbg = {};
+  return fv_launch(&h, 1, n_iters, dbg, stream);
+}
+
+int ldc_fv_batch_enqueue(ldc_fv* const* hs, int n, int n_iters, void* stream) {
+  if (!hs || n < 1 || n_iters < 1) return LDC_E_ARG;
+  for (int q = 0; q < n; ++q) {
+    if (!hs[q]) return LDC_E_STATE;
+    if (n_iters > hs[q]->rec_cap) return LDC_E_ARG;
+  }
+  FvDebug dbg = {};
+  return fv_launch(hs, n, n_iters, dbg, stream);
+}
+
+int ldc_fv_status(ldc_fv* h) {
+  if (!h) return LDC_E_STATE;
+  long long flag = 0;
+  const hipError_t e = hipMemcpy(&flag, h->ctrl + 2, sizeof(flag), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return (int)e;
+  return flag ? LDC_FV_E_NAN : 0;
+}
+
+int ldc_fv_step_debug(ldc_fv* h, int which, double* const* out, void* stream) {
+  if (!h) return LDC_E_STATE;
+  if (which < 0 || which >= (1 << LDC_FV_DBG_COUNT) || (which && !out)) return LDC_E_ARG;
+  FvDebug dbg = {};
+  for (int k = 0; k < LDC_FV_DBG_COUNT; ++k) {
+    if (!(which & (1 << k))) continue;
+    if (!out[k]) return LDC_E_ARG;
+    dbg.out[k] = out[k];
+  }
+  return fv_launch(&h, 1, 1, dbg, stream);
+}
+
+}  // extern "C"

@@ -3198,3 +3198,5 @@ int ldc_stream_destroy(void* stream) {
 }
 
 }  // extern "C"
+
+#include "ldc_fv_kernel.inc"      // the finite-volume SIMPLE solver (include/ldc_fv.h)

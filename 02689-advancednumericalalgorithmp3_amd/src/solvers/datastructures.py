@@ -77,6 +77,27 @@ class SpectralParameters(Parameters):
         return {k: _mlflow_scalar(v) for k, v in self.as_dict().items() if k not in skip}
 
 
+@dataclass
+class FVParameters(Parameters):
+    """Finite-volume SIMPLE solver (solvers.fv.solver.FVSolver); nx/ny are cell counts.  Defaults as the reference's
+    (src/solvers/datastructures.py:174-186); conf/solver/fv.yaml overrides several (TVD, 0.4 / 0.2, 1e-9)."""
+    convection_scheme: str = "Upwind"
+    limiter: str = "MUSCL"
+    alpha_uv: float = 0.6
+    alpha_p: float = 0.4
+    linear_solver_tol: float = 1e-6
+    method: str = "FV-SIMPLE"
+    corner_treatment: str = "none"
+    corner_smoothing: float = 0.15
+    # --- additions of the MI355X build (optional, defaults keep reference behaviour) ---
+    device: str = "cuda:0"
+    check_every: int = 2048        # iterations enqueued between host polls of the latch
+
+    def to_mlflow(self) -> dict:
+        skip = {"device", "check_every"}
+        return {k: _mlflow_scalar(v) for k, v in self.as_dict().items() if k not in skip}
+
+
 _VORTEX_KEYS = (
     "psi_min", "psi_min_x", "psi_min_y", "omega_center",
     "omega_max", "omega_max_x", "omega_max_y",

@@ -1,0 +1,75 @@
+"""ctypes binding of the finite-volume entry points of ``libldc_hip.so`` (C ABI: ``include/ldc_fv.h``).
+
+The same library and loader as the spectral solver (solvers.spectral.ldc_lib): Python owns the device memory as torch
+tensors and hands raw pointers to the HIP kernel.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from solvers.spectral import ldc_lib as _L
+
+VERSION = 1
+MIN_N, MAX_N = 8, 256
+REC_LEN, CTRL_LEN = 8, 8
+NWORK, DESC_DOUBLES = 32, 64
+LAUNCH_MAX = 256
+E_NAN = -5
+CTRL_DONE, CTRL_ITER, CTRL_NAN, CTRL_GIVEUP, CTRL_LIN_ITERS, CTRL_SOLVES = range(6)
+DBG = ("grad_p", "diag", "b", "u_star", "v_star", "mdot_star", "rhs_p", "p_prime", "u_prime", "v_prime", "mdot")
+
+_dp = C.c_void_p
+
+
+class Problem(C.Structure):
+    """Mirror of ``struct ldc_fv_problem`` -- keep field order in sync with the header."""
+    _fields_ = (
+        [(n, C.c_int32) for n in ("nx", "ny", "scheme", "rec_cap", "warmup", "max_lin_iters")]
+        + [(n, C.c_double) for n in ("dx", "dy", "rho", "mu", "alpha_uv", "alpha_p", "lin_tol", "tol", "lid_velocity")]
+        + [(n, _dp) for n in ("ulid", "Qx", "lamx", "Qy", "lamy", "u", "v", "p", "mdot", "work", "rec", "ctrl")]
+    )
+
+
+# every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
+EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
+           "ldc_fv_status", "ldc_fv_step_debug")
+
+_bound = None
+
+
+def work_len(nx: int, ny: int) -> int:
+    return NWORK * nx * ny + DESC_DOUBLES
+
+
+def faces(nx: int, ny: int) -> int:
+    return ny * (nx + 1) + (ny + 1) * nx
+
+
+def lib() -> C.CDLL:
+    """The shared library with the FV entry points' signatures set (raises if it has not been built)."""
+    global _bound
+    L = _L.lib()
+    if _bound is None:
+        L.ldc_fv_version.restype = C.c_int
+        L.ldc_fv_create.argtypes = [C.POINTER(Problem), C.POINTER(_dp)]
+        L.ldc_fv_destroy.argtypes = [_dp]
+        L.ldc_fv_enqueue.argtypes = [_dp, C.c_int, _dp]
+        L.ldc_fv_batch_enqueue.argtypes = [C.POINTER(_dp), C.c_int, C.c_int, _dp]
+        L.ldc_fv_status.argtypes = [_dp]
+        L.ldc_fv_step_debug.argtypes = [_dp, C.c_int, C.POINTER(_dp), _dp]
+        for name in EXPORTS:
+            getattr(L, name).restype = C.c_int
+        _bound = L
+    return L
+
+
+def check(code: int, what: str = "ldc_fv call"):
+    if code == E_NAN:
+        raise _L.LdcError(f"{what}: the finite-volume trial produced a NaN and stopped (code {code})")
+    _L.check(code, what)
+
+
+def batch_enqueue(handles, n_iters: int, stream) -> None:
+    """One launch (per LAUNCH_MAX trials) advancing every handle by up to n_iters iterations."""
+    arr = (_dp * len(handles))(*[h.value if isinstance(h, _dp) else h for h in handles])
+    check(lib().ldc_fv_batch_enqueue(arr, len(handles), int(n_iters), _dp(stream)), "ldc_fv_batch_enqueue")

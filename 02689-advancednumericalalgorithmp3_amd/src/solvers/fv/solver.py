@@ -1,0 +1,260 @@
+"""Finite-volume SIMPLE solver of the lid-driven cavity on MI355X (the reference's ``solvers.fv.solver.FVSolver``).
+
+Contract: reference src/solvers/fv/solver.py (the iteration, :170-257), base.py:202-330 (the loop and its record),
+:359-450 (E, Z, P), :569-760 (streamfunction and vortex extrema).  Every SIMPLE iteration runs in the HIP kernel of
+include/ldc_fv.h -- one work-group per trial, ``check_every`` iterations per launch -- and the host only reads the
+record rows and the latch.  The host computes, once per trial, the eigenvectors of the 1-D Neumann Laplacians that the
+kernel's exact pressure-correction solve uses, and, once per solve, the vortex metrics.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import logging
+
+import numpy as np
+
+from .. import validation as _val
+from ..base import LidDrivenCavitySolver
+from ..datastructures import FVParameters
+from . import ldc_fv_lib as F
+
+log = logging.getLogger(__name__)
+
+SCHEMES = {"Upwind": 0, "TVD": 1}
+LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
+
+
+def lid_profile(nx, Lx=1.0, lid_velocity=1.0, corner_treatment="none", corner_smoothing=0.15) -> np.ndarray:
+    """u on the lid faces, evaluated as the reference's mesh builder does (simple_structured.py:244-262)."""
+    x = np.linspace(0, Lx, nx + 1)
+    xf = 0.5 * (x[:-1] + x[1:])
+    xi = xf / Lx
+    if corner_treatment in ("polynomial", "saad"):
+        return 16.0 * xi**2 * (1.0 - xi) ** 2 * lid_velocity
+    u = np.full(nx, float(lid_velocity))
+    if corner_treatment == "smoothing":
+        d = corner_smoothing * Lx
+        for i, x_face in enumerate(xf):
+            if x_face < d:
+                u[i] = 0.5 * (1 - np.cos(np.pi * x_face / d)) * lid_velocity
+            elif x_face > (Lx - d):
+                u[i] = 0.5 * (1 - np.cos(np.pi * (Lx - x_face) / d)) * lid_velocity
+    return u
+
+
+def neumann_eig(n: int):
+    """(eigenvalues ascending, eigenvectors as columns) of the 1-D Neumann second difference; index 0 = zero mode."""
+    T = 2 * np.eye(n) - np.eye(n, k=1) - np.eye(n, k=-1)
+    T[0, 0] = T[-1, -1] = 1.0
+    lam, Q = np.linalg.eigh(T)
+    assert abs(lam[0]) < 1e-10 and lam[1] > 1e-6, "Neumann Laplacian: one zero mode, first"
+    return lam, Q
+
+
+class FVSolver(LidDrivenCavitySolver):
+    """Collocated finite-volume SIMPLE solver; ``nx`` x ``ny`` cells (8 ... 256 each)."""
+
+    Parameters = FVParameters
+    rho = 1.0
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        p = self.params
+        if p.convection_scheme not in SCHEMES:
+            raise ValueError(f"convection_scheme={p.convection_scheme!r}: 'Upwind' or 'TVD'")
+        if p.convection_scheme == "TVD" and p.limiter != "MUSCL":
+            raise ValueError(f"limiter={p.limiter!r}: the TVD scheme of the reference is MUSCL")
+        nx, ny = int(p.nx), int(p.ny)
+        if not (F.MIN_N <= nx <= F.MAX_N and F.MIN_N <= ny <= F.MAX_N):
+            raise ValueError(f"nx, ny = {nx}, {ny}: the FV kernel takes {F.MIN_N} ... {F.MAX_N} cells per axis")
+        self.nx, self.ny, self.n_cells = nx, ny, nx * ny
+        self.dx_min, self.dy_min = p.Lx / nx, p.Ly / ny
+        self.shape_full = (ny, nx)               # as the reference's FV solver: cells c = j*nx + i
+        self.mu = self.rho * p.lid_velocity * p.Lx / p.Re
+        xc, yc = (np.arange(nx) + 0.5) * self.dx_min, (np.arange(ny) + 0.5) * self.dy_min
+        X, Y = np.meshgrid(xc, yc)
+        self._init_fields(x=X.ravel(), y=Y.ravel())
+
+        import torch
+        from solvers.spectral import ldc_lib
+        self.device = torch.device(p.device)
+        ldc_lib.require_device(self.device)      # no GPU / not gfx950 -> LdcError: there is no CPU fallback
+        L = F.lib()
+        if L.ldc_fv_version() != F.VERSION:
+            raise ldc_lib.LdcError(f"ldc_fv ABI {L.ldc_fv_version()} != {F.VERSION}: rebuild the library")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        lamx, Qx = neumann_eig(nx)
+        lamy, Qy = neumann_eig(ny)
+        self.rec_cap = max(1, int(p.check_every))
+        self.t = dict(
+            ulid=torch.tensor(lid_profile(nx, p.Lx, p.lid_velocity, p.corner_treatment, p.corner_smoothing), **f64),
+            Qx=torch.tensor(Qx, **f64).contiguous(), lamx=torch.tensor(lamx, **f64),
+            Qy=torch.tensor(Qy, **f64).contiguous(), lamy=torch.tensor(lamy, **f64),
+            u=torch.zeros(nx * ny, **f64), v=torch.zeros(nx * ny, **f64), p=torch.zeros(nx * ny, **f64),
+            mdot=torch.zeros(F.faces(nx, ny), **f64), work=torch.zeros(F.work_len(nx, ny), **f64),
+            rec=torch.zeros((self.rec_cap, F.REC_LEN), **f64),
+            ctrl=torch.zeros(F.CTRL_LEN, dtype=torch.int64, device=self.device))
+        self._handle = None
+        self._handle_tol = None
+        self._make_handle(p.tolerance)
+
+    # ---- device handle ----------------------------------------------------------------------------
+    def _problem(self, tolerance: float) -> F.Problem:
+        p, t = self.params, self.t
+        pr = F.Problem(nx=self.nx, ny=self.ny, scheme=SCHEMES[p.convection_scheme], rec_cap=self.rec_cap, warmup=10,
+                       max_lin_iters=LINEAR_MAX_ITERATIONS, dx=self.dx_min, dy=self.dy_min, rho=self.rho, mu=self.mu,
+                       alpha_uv=float(p.alpha_uv), alpha_p=float(p.alpha_p), lin_tol=float(p.linear_solver_tol),
+                       tol=float(tolerance), lid_velocity=float(p.lid_velocity))
+        for name in ("ulid", "Qx", "lamx", "Qy", "lamy", "u", "v", "p", "mdot", "work", "rec", "ctrl"):
+            setattr(pr, name, t[name].data_ptr())
+        return pr
+
+    def _make_handle(self, tolerance: float):
+        import torch
+        if self._handle is not None and self._handle_tol == tolerance:
+            return
+        self._destroy_handle()
+        h = C.c_void_p()
+        pr = self._problem(tolerance)
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream(self.device).synchronize()
+            F.check(F.lib().ldc_fv_create(C.byref(pr), C.byref(h)), "ldc_fv_create")
+        self._handle, self._handle_tol = h, tolerance
+
+    def _destroy_handle(self):
+        if self._handle is not None:
+            F.lib().ldc_fv_destroy(self._handle)
+            self._handle = None
+
+    def close(self):
+        """Release the device handle (the torch tensors go with the object)."""
+        self._destroy_handle()
+
+    def __del__(self):
+        try:
+            self._destroy_handle()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._handle
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    # ---- state access (tests, tools) -------------------------------------------------------------------
+    def set_state(self, u, v, p, mdot):
+        """Overwrite the device state: u, v, p per cell (c = j*nx + i), mdot in the [fx | fy] face layout."""
+        import torch
+        for name, val in (("u", u), ("v", v), ("p", p), ("mdot", mdot)):
+            self.t[name].copy_(torch.as_tensor(np.asarray(val, dtype=np.float64).ravel()))
+        self.t["ctrl"].zero_()
+
+    def state(self) -> dict:
+        return {k: self.t[k].cpu().numpy().copy() for k in ("u", "v", "p", "mdot")}
+
+    def counters(self) -> dict:
+        c = self.t["ctrl"].cpu().numpy()
+        return dict(done=int(c[F.CTRL_DONE]), iterations=int(c[F.CTRL_ITER]), nan=int(c[F.CTRL_NAN]),
+                    linear_giveups=int(c[F.CTRL_GIVEUP]), linear_iterations=int(c[F.CTRL_LIN_ITERS]),
+                    momentum_solves=int(c[F.CTRL_SOLVES]))
+
+    def step_debug(self, which=F.DBG) -> dict:
+        """One iteration through ldc_fv_step_debug; returns the named intermediates (include/ldc_fv.h)."""
+        import torch
+        n, nf = self.n_cells, F.faces(self.nx, self.ny)
+        size = dict(grad_p=2 * n, diag=5 * n, b=2 * n, mdot_star=nf, mdot=nf)
+        bufs = {k: torch.full((size.get(k, n),), float("nan"), dtype=torch.float64, device=self.device) for k in which}
+        ptrs = (C.c_void_p * len(F.DBG))(*[bufs[k].data_ptr() if k in bufs else None for k in F.DBG])
+        mask = sum(1 << F.DBG.index(k) for k in which)
+        with torch.cuda.device(self.device):
+            F.check(F.lib().ldc_fv_step_debug(self._handle, mask, ptrs, C.c_void_p(self._stream())), "ldc_fv_step_debug")
+            torch.cuda.current_stream(self.device).synchronize()
+        return {k: b.cpu().numpy() for k, b in bufs.items()}
+
+    # ---- LidDrivenCavitySolver hooks --------------------------------------------------------------------
+    def _begin(self, tolerance: float):
+        self._make_handle(tolerance)
+        self.t["ctrl"][F.CTRL_DONE] = 0
+
+    def _advance(self, n_iters: int):
+        import torch
+        n_iters = max(1, min(int(n_iters), self.rec_cap))
+        before = int(self.t["ctrl"][F.CTRL_ITER].item())
+        with torch.cuda.device(self.device):
+            F.check(F.lib().ldc_fv_enqueue(self._handle, n_iters, C.c_void_p(self._stream())), "ldc_fv_enqueue")
+            ctrl = self.t["ctrl"].cpu().numpy()            # (synchronises the stream)
+        total = int(ctrl[F.CTRL_ITER])
+        rows = self.t["rec"][: total - before].cpu().numpy().copy()
+        if ctrl[F.CTRL_NAN]:
+            F.check(F.lib().ldc_fv_status(self._handle), f"FV trial at iteration {total}")
+        return rows, int(ctrl[F.CTRL_DONE]), total
+
+    def _finalize_fields(self):
+        st = self.state()
+        self.fields.u, self.fields.v, self.fields.p = st["u"], st["v"], st["p"]
+
+    # ---- vortex metrics (reference base.py:569-760), on the host once per solve ----------------------------
+    def _ghost_gradient(self, f2, bc_lid):
+        g = np.zeros((self.ny + 2, self.nx + 2))
+        g[1:-1, 1:-1] = f2
+        g[0, 1:-1] = -f2[0, :]
+        g[-1, 1:-1] = 2 * bc_lid - f2[-1, :]
+        g[1:-1, 0] = -f2[:, 0]
+        g[1:-1, -1] = -f2[:, -1]
+        return ((g[1:-1, 2:] - g[1:-1, :-2]) / (2 * self.dx_min), (g[2:, 1:-1] - g[:-2, 1:-1]) / (2 * self.dy_min))
+
+    def _vorticity(self) -> np.ndarray:
+        U, V = self.fields.u.reshape(self.shape_full), self.fields.v.reshape(self.shape_full)
+        dvdx, _ = self._ghost_gradient(V, 0.0)
+        _, dudy = self._ghost_gradient(U, float(getattr(self.params, "lid_velocity", 1.0)))
+        return dvdx - dudy
+
+    def _streamfunction(self, omega):
+        """psi from the 5-point Dirichlet Poisson problem on the interior cells (base.py:569-630)."""
+        from scipy.sparse import diags
+        from scipy.sparse.linalg import spsolve
+        ny, nx = self.shape_full
+        dx, dy = self.dx_min, self.dy_min
+        ni = (ny - 2) * (nx - 2)
+        cx, cy = 1.0 / (dx * dx), 1.0 / (dy * dy)
+        dmain = np.full(ni, -2.0 * (cx + cy))
+        dxo = np.full(ni - 1, cx)
+        dyo = np.full(ni - (nx - 2), cy)
+        for i in range(1, ny - 2):
+            idx = i * (nx - 2) - 1
+            if idx < len(dxo):
+                dxo[idx] = 0.0
+        A = diags([dyo, dxo, dmain, dxo, dyo], [-(nx - 2), -1, 0, 1, (nx - 2)], format="csr")
+        psi = np.zeros((ny, nx))
+        psi[1:-1, 1:-1] = spsolve(A, -omega[1:-1, 1:-1].ravel()).reshape(ny - 2, nx - 2)
+        return psi
+
+    def compute_vortex_metrics(self) -> dict:
+        omega = self._vorticity()
+        psi = self._streamfunction(omega)
+        xs, ys = np.sort(np.unique(self.fields.x)), np.sort(np.unique(self.fields.y))
+        imin = np.unravel_index(np.argmin(psi), psi.shape)
+        imax = np.unravel_index(np.argmax(np.abs(omega)), omega.shape)
+        out = dict(psi_min=float(psi[imin]), psi_min_x=float(xs[imin[1]]), psi_min_y=float(ys[imin[0]]),
+                   omega_center=float(omega[imin]), omega_max=float(omega[imax]),
+                   omega_max_x=float(xs[imax[1]]), omega_max_y=float(ys[imax[0]]))
+        X, Y = np.meshgrid(xs, ys)
+        regions = {"BR": (X > 0.5) & (Y < 0.5), "BL": (X < 0.5) & (Y < 0.5), "TL": (X < 0.5) & (Y > 0.5)}
+        for name, mask in regions.items():
+            k = np.unravel_index(np.argmax(np.where(mask, psi, -np.inf)), psi.shape)
+            if psi[k] > 0:
+                out.update({f"psi_{name}": float(psi[k]), f"psi_{name}_x": float(xs[k[1]]),
+                            f"psi_{name}_y": float(ys[k[0]])})
+            else:
+                out.update({f"psi_{name}": 0.0, f"psi_{name}_x": 0.0, f"psi_{name}_y": 0.0})
+        return out
+
+    # ---- Ghia centrelines: linear interpolation, as the reference plots FV fields ----------------------------
+    def ghia_error(self) -> dict:
+        ny, nx = self.shape_full
+        x, y = self.fields.x.reshape(ny, nx)[0, :], self.fields.y.reshape(ny, nx)[:, 0]
+        U, V = self.fields.u.reshape(ny, nx).T, self.fields.v.reshape(ny, nx).T        # -> [ix, iy]
+        return _val.ghia_centerline_error(x, y, U, V, int(self.params.Re), interpolation="linear")

@@ -49,17 +49,25 @@ def load_ghia(Re: int, data_dir=None):
     return (u["y"], u["u"]), (v["x"], v["v"])
 
 
-def ghia_centerline_error(x_nodes, y_nodes, U, V, Re, data_dir=None) -> dict:
+def ghia_centerline_error(x_nodes, y_nodes, U, V, Re, data_dir=None, interpolation: str = "legendre") -> dict:
     """RMS and relative-L2 error of the centreline profiles at the tabulated Ghia points.
 
     U, V are [ix, iy].  u is taken on the grid line nearest x = centre (exact for even N),
     v on the line nearest y = centre, both interpolated with the Legendre-modal interpolant
-    the reference uses for its Ghia plots."""
+    the reference uses for its Ghia plots of spectral fields; ``interpolation="linear"`` is its
+    choice for FV fields (np.interp, constant beyond the outermost nodes;
+    src/shared/plotting/ldc/validation.py:308-312)."""
+    if interpolation not in ("legendre", "linear"):
+        raise ValueError(f"interpolation={interpolation!r}: 'legendre' or 'linear'")
     (yu, ug), (xv, vg) = load_ghia(Re, data_dir)
     ic = int(np.argmin(np.abs(x_nodes - 0.5 * (x_nodes.min() + x_nodes.max()))))
     jc = int(np.argmin(np.abs(y_nodes - 0.5 * (y_nodes.min() + y_nodes.max()))))
-    eu = spectral_interpolate(y_nodes, U[ic, :], yu, basis="legendre") - ug
-    ev = spectral_interpolate(x_nodes, V[:, jc], xv, basis="legendre") - vg
+    if interpolation == "linear":
+        eu = np.interp(yu, y_nodes, U[ic, :]) - ug
+        ev = np.interp(xv, x_nodes, V[:, jc]) - vg
+    else:
+        eu = spectral_interpolate(y_nodes, U[ic, :], yu, basis="legendre") - ug
+        ev = spectral_interpolate(x_nodes, V[:, jc], xv, basis="legendre") - vg
     return dict(u_rms=float(np.sqrt(np.mean(eu**2))), v_rms=float(np.sqrt(np.mean(ev**2))),
                 u_rel=float(np.linalg.norm(eu) / np.linalg.norm(ug)),
                 v_rel=float(np.linalg.norm(ev) / np.linalg.norm(vg)),

@@ -75,6 +75,12 @@ def us_per_iteration(n: float, batch: int = 1, smoother: bool = False) -> float:
     return (1.0 - w) * at(lone) + w * at(full)
 
 
+# Finite-volume SIMPLE trials (solvers.fv, one work-group per trial): iterations to tolerance 1e-6 with the YAML's TVD
+# settings (profiles/fv_q1_table.md, N = 128) and microseconds per iteration of a lone trial (profiles/fv_perf.md).
+_FV_ITERATIONS = {(128, 100): 11545, (128, 1000): 11570}
+_FV_US_PER_ITERATION = {64: 654.9, 128: 2498.1, 256: 15169.7}
+
+
 def expected_iterations(n: float, re: float) -> float:
     """Iterations to the reference's stopping rule: the measured table at the nearest Re, log-log in N."""
     res = sorted({r for _, r in _SG_ITERATIONS})
@@ -91,6 +97,11 @@ def trial_cost(trial: dict, solver: str = None, batch: int = 1) -> float:
     t = dict(trial)
     n, re = float(t.get("N", 32)), float(t.get("Re", 100))
     kind = str(t.get("solver", solver or "")).lower()
+    if "solvers.fv" in kind or kind == "fv":
+        res = sorted({r for _, r in _FV_ITERATIONS})
+        r = min(res, key=lambda q: abs(math.log(q / max(re, 1e-9))))
+        its = _FV_ITERATIONS[(128, r)] * (n / 128.0)           # SIMPLE iterations grow about linearly in N
+        return its * _interp_log(_FV_US_PER_ITERATION, max(n, 8.0)) * 1e-6
     if "fsg" in kind:
         levels = int(t.get("n_levels", t.get("solver.n_levels", 2)))
         cost, m = 0.0, n

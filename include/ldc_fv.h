@@ -1,0 +1,95 @@
+/* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc).
+ *
+ * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
+ * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
+ * whole chunk of iterations; a launch of B trials is B independent work-groups (no inter-group waits).
+ *
+ * Conventions (all arrays are device memory owned by the caller, doubles unless stated):
+ *  - cells  c = j*nx + i  (y outer, x inner; simple_structured.py:197-200), n = nx*ny;
+ *  - face fluxes  mdot = [ fx | fy ]:  fx[j*(nx+1) + i], i = 0..nx, the flux in +x through the face at x = i*dx;
+ *    fy[j*nx + i], j = 0..ny, the flux in +y through the face at y = j*dy  (length LDC_FV_FACES(nx, ny));
+ *  - Qx (nx x nx, row-major, column k = k-th eigenvector) and lamx (nx): numpy.linalg.eigh of the 1-D Neumann
+ *    second difference (diagonal 1, 2, ..., 2, 1; off-diagonals -1), eigenvalues ascending, so the zero mode is
+ *    index 0; Qy, lamy likewise for ny.  The pressure correction is solved with them exactly (fast diagonalisation).
+ *  - rec: rec_cap rows of LDC_FV_REC_LEN doubles, row k = iteration k of the last enqueue:
+ *    rel_change, |u'|, |v'|, |div mdot|, E, Z, P, 0   (the record of include/ldc_hip.h with DT = 0);
+ *  - ctrl: LDC_FV_CTRL_LEN int64: [0] converged latch, [1] iterations done, [2] NaN seen (the trial stopped),
+ *    [3] momentum solves that hit max_lin_iters (accepted, as the reference does), [4] BiCGSTAB iterations of all
+ *    momentum solves, [5] momentum solves.  Zero it before the first enqueue.
+ *  - functions return 0, a negative LDC_E_* code of ldc_hip.h, LDC_FV_E_NAN, or a positive hipError_t.
+ */
+#ifndef LDC_FV_H
+#define LDC_FV_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define LDC_FV_VERSION 1
+#define LDC_FV_MIN_N 8
+#define LDC_FV_MAX_N 256
+#define LDC_FV_REC_LEN 8
+#define LDC_FV_CTRL_LEN 8
+#define LDC_FV_NWORK 32            /* work vectors of n doubles */
+#define LDC_FV_DESC_DOUBLES 64     /* + the trial's device-side descriptor */
+#define LDC_FV_WORK_LEN(nx, ny) (LDC_FV_NWORK * (int64_t)(nx) * (ny) + LDC_FV_DESC_DOUBLES)
+#define LDC_FV_FACES(nx, ny) ((int64_t)(ny) * ((nx) + 1) + (int64_t)((ny) + 1) * (nx))
+#define LDC_FV_LAUNCH_MAX 256      /* trials per launch of ldc_fv_batch_enqueue (more: several launches) */
+#define LDC_FV_E_NAN (-5)          /* ldc_fv_status: the trial produced a NaN and stopped */
+
+/* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
+#define LDC_FV_DBG_GRAD_P 0        /* 2n: d/dx p, then d/dy p                                    */
+#define LDC_FV_DBG_DIAG 1          /* 5n: aP (unrelaxed), aW, aE, aS, aN                          */
+#define LDC_FV_DBG_B 2             /* 2n: b_u, b_v of the assembly (boundary + deferred correction) */
+#define LDC_FV_DBG_USTAR 3         /* n */
+#define LDC_FV_DBG_VSTAR 4         /* n */
+#define LDC_FV_DBG_MDOT_STAR 5     /* faces */
+#define LDC_FV_DBG_RHS_P 6         /* n: -div mdot*, entry 0 = 0 */
+#define LDC_FV_DBG_P_PRIME 7       /* n */
+#define LDC_FV_DBG_U_PRIME 8       /* n */
+#define LDC_FV_DBG_V_PRIME 9       /* n */
+#define LDC_FV_DBG_MDOT 10         /* faces */
+#define LDC_FV_DBG_COUNT 11
+
+struct ldc_fv_problem {
+  int32_t nx, ny;                 /* LDC_FV_MIN_N .. LDC_FV_MAX_N each */
+  int32_t scheme;                 /* 0 = Upwind, 1 = TVD (MUSCL; DESIGN.md FV-Q1) */
+  int32_t rec_cap;                /* rows of rec: the most iterations one enqueue may run */
+  int32_t warmup;                 /* no convergence test before this many iterations (10) */
+  int32_t max_lin_iters;          /* BiCGSTAB iterations per momentum solve (1000) */
+  double dx, dy;                  /* Lx / nx, Ly / ny */
+  double rho, mu;                 /* density, viscosity rho * U * Lx / Re */
+  double alpha_uv, alpha_p;       /* under-relaxation, each in (0, 1] */
+  double lin_tol;                 /* BiCGSTAB rtol relative to |b| (atol = 0) */
+  double tol;                     /* outer latch on the relative change of u, v */
+  double lid_velocity;            /* u on the lid in E/Z/P's ghost cells (base.py:424-425) */
+  const double *ulid;             /* nx: u on the lid faces (the lid profile of the mesh) */
+  const double *Qx, *lamx, *Qy, *lamy;
+  double *u, *v, *p, *mdot;       /* state: n, n, n, faces */
+  double *work;                   /* LDC_FV_WORK_LEN(nx, ny) */
+  double *rec;                    /* rec_cap * LDC_FV_REC_LEN */
+  int64_t *ctrl;                  /* LDC_FV_CTRL_LEN */
+};
+
+typedef struct ldc_fv ldc_fv;
+
+int ldc_fv_version(void);
+/* Validate (no device needed), then write the trial's descriptor into the tail of `work` (synchronous copy). */
+int ldc_fv_create(const struct ldc_fv_problem *prob, ldc_fv **out);
+int ldc_fv_destroy(ldc_fv *h);
+/* Up to n_iters SIMPLE iterations (<= rec_cap) in one launch; stops early at the latch or a NaN. */
+int ldc_fv_enqueue(ldc_fv *h, int n_iters, void *stream);
+/* The same for n trials (any sizes and parameters, one device): one work-group each. */
+int ldc_fv_batch_enqueue(ldc_fv *const *hs, int n, int n_iters, void *stream);
+/* 0, or LDC_FV_E_NAN when the trial stopped on a NaN (reads ctrl; synchronises the device). */
+int ldc_fv_status(ldc_fv *h);
+/* One iteration, copying the intermediates selected by `which` into out[k] (device pointers). */
+int ldc_fv_step_debug(ldc_fv *h, int which, double *const *out, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* LDC_FV_H */
