@@ -573,7 +573,7 @@ int ldc_fv_create(const struct ldc_fv_problem* pr, ldc_fv** out) {
   h.u = pr->u; h.v = pr->v; h.p = pr->p; h.mdot = pr->mdot; h.work = pr->work; h.rec = pr->rec;
   h.ctrl = reinterpret_cast<long long*>(pr->ctrl);
   FvDesc* slot = reinterpret_cast<FvDesc*>(pr->work + (int64_t)LDC_FV_NWORK * pr->nx * pr->ny);
-  const hipError_t e = hipMemcpy(slot, &h, sizeof(h), hipMemcpyHostToDevice);
+  const hipError_t e = copy_now(slot, &h, sizeof(h), hipMemcpyHostToDevice);
   if (e != hipSuccess) return (int)e;
   ldc_fv* s = new (std::nothrow) ldc_fv;
   if (!s) return LDC_E_STATE;
@@ -608,7 +608,7 @@ int ldc_fv_batch_enqueue(ldc_fv* const* hs, int n, int n_iters, void* stream) {
 int ldc_fv_status(ldc_fv* h) {
   if (!h) return LDC_E_STATE;
   long long flag = 0;
-  const hipError_t e = hipMemcpy(&flag, h->ctrl + 2, sizeof(flag), hipMemcpyDeviceToHost);
+  const hipError_t e = copy_now(&flag, h->ctrl + 2, sizeof(flag), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return (int)e;
   return flag ? LDC_FV_E_NAN : 0;
 }

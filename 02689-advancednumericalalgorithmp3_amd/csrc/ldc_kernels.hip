@@ -1688,6 +1688,27 @@ __global__ __launch_bounds__(512) void mfma_peak_kernel(double* sink, int iters)
 // =======================================================================================
 // host side
 // =======================================================================================
+// Chunk graphs of the chip-wide kernel (mode 5): a whole enqueue of n_iters iterations -- the flags' reset, the kernel, the
+// closing launches -- captured as ONE graph, kept for up to kLengths lengths per diagnostics form (a solve's chunks are
+// check_every long and its last one shorter) with the event recorded behind each graph's latest launch.  A slot is reused
+// least-recently-used first, and a graph is destroyed (evicted, or by clear()) only once that event has completed: a launch
+// still queued on the caller's stream never loses its graph.
+struct ChunkCache {
+  static constexpr int kLengths = 3;
+  struct Slot {
+    int n_iters = 0;               // 0: free slot
+    unsigned long long used = 0;   // last launch, for the least-recently-used eviction
+    hipGraphExec_t exec = nullptr;
+    hipEvent_t done = nullptr;
+  };
+  Slot slot[2][kLengths];          // [with_diagnostics]
+  unsigned long long clock = 0;
+  // the graph of this length (captured by enqueue(capture stream) if it is not kept), launched on st
+  template <typename F>
+  int launch(int n_iters, int with_diag, hipStream_t st, F&& enqueue);
+  void clear();
+};
+
 struct ldc_solver {
   ldc_problem p;
   int device;        // HIP device that was current at ldc_solver_create: every launch of this handle belongs there
@@ -1698,24 +1719,11 @@ struct ldc_solver {
   int ablate;
   double* stamps;            // ldc_debug_stamps
   hipGraphExec_t graph[2];   // [with_diagnostics]
-  hipGraphExec_t chunk_graph[2];   // a whole enqueue of chunk_iters[] iterations on one of the trial kernels (modes 3, 5) with its closing launches
-  int chunk_iters[2];
-  hipStream_t capture_stream;
+  ChunkCache chunks;         // mode 5
   int persist_mode;          // -1 auto, 0 launch per stage, 3 small-N kernel, 4 trial-per-CU kernel, 5 chip-wide kernel
   int n_cus;                 // compute units of the handle's device
   int n_xcds;                // its XCDs (gfx950: 32 active CUs each; a CPX partition is one)
 };
-
-
-// One captured chunk of the chip-wide kernel's batch form (every launch group, the transforms, the closing record) and the
-// event recorded behind its latest launch: a graph executable is destroyed only once that event has completed.
-struct WChunk {
-  int n_iters;               // 0: free slot
-  unsigned long long used;   // last launch, for the least-recently-used eviction
-  hipGraphExec_t exec;
-  hipEvent_t done;
-};
-constexpr int kWChunkCache = 3;
 
 // B independent trials of identical geometry advanced by every launch (blockIdx.y = trial).
 struct ldc_batch {
@@ -1734,12 +1742,10 @@ struct ldc_batch {
   WArgs* d_wargs[2];         // [with_diagnostics] argument blocks of the chip-wide kernel
   int wT, wtail, wG;         // chip-wide kernel: tiles per axis, layout, trials per launch (wG = 0: it cannot run this batch)
   int wide_knob;             // LDC_BATCH_WIDE=1 at creation: auto-mode trials take the chip-wide kernel too
-  WChunk wchunk[2][kWChunkCache];      // [with_diagnostics] chunk graphs by length
-  unsigned long long wclock;
+  ChunkCache chunks;         // mode 5
   int post_grid[2], postT_grid, post_close_grid, postP_grid;
   int iters_per_graph;
   hipGraphExec_t graph[2];
-  hipStream_t capture_stream;
 };
 
 namespace {
@@ -1753,7 +1759,8 @@ namespace {
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // write-through stores (st_out); ldc_debug_ablate bits 128 / 256 force plain / write-through for A/B timing
-// (tiles = work-groups of 16 x 16 nodes in the launch, all trials of a batch together)
+// (tiles = work-groups of 16 x 16 nodes in the launch, all trials of a batch together: the `tiles` of make_stage_args and
+//  make_post_args)
 int write_through_policy(const ldc_solver* s, int tiles) {
 #ifdef LDC_TIMING
   if (s->ablate & 128) return 0;
@@ -1764,7 +1771,7 @@ int write_through_policy(const ldc_solver* s, int tiles) {
   return tiles >= LDC_WT_MIN_TILES ? 1 : 0;
 }
 
-StageArgs make_stage_args(const ldc_solver* s, int k) {
+StageArgs make_stage_args(const ldc_solver* s, int k, int tiles) {
   const ldc_problem& p = s->p;
   StageArgs a;
   memset(&a, 0, sizeof(a));
@@ -1783,7 +1790,7 @@ StageArgs make_stage_args(const ldc_solver* s, int k) {
   a.W = p.W; a.WT = p.WT;
   a.partZ0 = p.partials + p.partials_stride; a.partP0 = p.partials + 3 * p.partials_stride;
   a.stride = p.partials_stride;
-  a.wt = write_through_policy(s, s->nt);
+  a.wt = write_through_policy(s, tiles);
   a.rm_out = (k == 3) ? 1 : 0;
 #ifdef LDC_TIMING
   a.ablate = s->stamps ? s->ablate : (s->ablate & ~64);
@@ -1818,59 +1825,49 @@ StageArgs make_stage_args(const ldc_solver* s, int k) {
   return a;
 }
 
-// dynamic LDS above 64 KiB has to be enabled per kernel and device (hipFuncSetAttribute): done once per device by the
-// first ldc_solver_create / ldc_batch_create there (ensure_kernel_attributes), so a launch itself touches nothing but its arguments.
+// Each kernel family has ONE variant function: it maps the run-time choice to the instantiation and to what its launch needs.
+// The launchers call it, and so does ensure_kernel_attributes, over the function's whole domain: dynamic LDS above 64 KiB has
+// to be enabled per kernel and device (hipFuncSetAttribute), and a variant the pass did not see would fail only at launch.
+using StageKernel = void (*)(const StageArgs, const StageArgs*);
+struct StageVariant {
+  StageKernel fn;     // nullptr: no such variant
+  size_t lds;         // dynamic LDS of its launch
+};
 template <bool GP, bool LAST, bool DUMP, bool BATCH, int DIAG>
-int enable_stage_lds() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stage_kernel<GP, LAST, DUMP, BATCH, DIAG, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
-  if (e != hipSuccess) return (int)e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(stage_kernel<GP, LAST, DUMP, BATCH, DIAG, true>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit);
-  return (int)e;
-}
-template <bool BATCH>
-int enable_stage_lds_all() {
-  int e;
-  if ((e = enable_stage_lds<true, false, false, BATCH, 0>()) != 0) return e;
-  if ((e = enable_stage_lds<true, true, false, BATCH, 0>()) != 0) return e;
-  if ((e = enable_stage_lds<true, false, false, BATCH, 1>()) != 0) return e;
-  if ((e = enable_stage_lds<false, false, false, BATCH, 2>()) != 0) return e;
-  if ((e = enable_stage_lds<false, false, false, BATCH, 0>()) != 0) return e;
-  if ((e = enable_stage_lds<false, true, false, BATCH, 0>()) != 0) return e;
-  if (!BATCH && (e = enable_stage_lds<true, false, true, false, 0>()) != 0) return e;
-  return 0;
-}
-
-template <bool GP, bool LAST, bool DUMP, bool BATCH, int DIAG>
-int launch_stage_kernel(const StageArgs& a, const StageArgs* arr, int nt, int nbatch, hipStream_t st, bool rect) {
+StageVariant stage_variant_of(bool rect) {
   constexpr size_t lds_bytes = StageLds<GP || DIAG == 2, GP || DIAG != 0 || LAST || DUMP>::BYTES;
   static_assert(lds_bytes <= kLdsLimit, "stage kernel LDS");
   // (rect: nx != ny; a batch has one geometry, so the caller's flag holds for every trial of it)
-  if (rect) hipLaunchKernelGGL((stage_kernel<GP, LAST, DUMP, BATCH, DIAG, true>), dim3(nt, nbatch), dim3(kStageThreads), lds_bytes, st, a, arr);
-  else hipLaunchKernelGGL((stage_kernel<GP, LAST, DUMP, BATCH, DIAG, false>), dim3(nt, nbatch), dim3(kStageThreads), lds_bytes, st, a, arr);
+  return {rect ? stage_kernel<GP, LAST, DUMP, BATCH, DIAG, true> : stage_kernel<GP, LAST, DUMP, BATCH, DIAG, false>, lds_bytes};
+}
+// which instantiation runs RK stage k (diag: fuse the omega / palinstrophy work into stages 1 and 2; dump: the form of
+// ldc_residual_debug, lone trials only)
+template <bool BATCH>
+StageVariant stage_variant_b(int k, bool stage_pressure, bool diag, bool dump, bool rect) {
+  if (dump) {
+    if constexpr (BATCH) return {nullptr, 0};
+    else return stage_variant_of<true, false, true, false, 0>(rect);
+  }
+  if (stage_pressure)   // FSG smoother: every stage differentiates its own input pressure; no diagnostics
+    return k < 3 ? stage_variant_of<true, false, false, BATCH, 0>(rect) : stage_variant_of<true, true, false, BATCH, 0>(rect);
+  if (k == 0) return diag ? stage_variant_of<true, false, false, BATCH, 1>(rect) : stage_variant_of<true, false, false, BATCH, 0>(rect);
+  if (k == 1) return diag ? stage_variant_of<false, false, false, BATCH, 2>(rect) : stage_variant_of<false, false, false, BATCH, 0>(rect);
+  if (k == 2) return stage_variant_of<false, false, false, BATCH, 0>(rect);
+  return stage_variant_of<false, true, false, BATCH, 0>(rect);
+}
+StageVariant stage_variant(int k, bool stage_pressure, bool diag, bool dump, bool rect, bool batch) {
+  return batch ? stage_variant_b<true>(k, stage_pressure, diag, dump, rect) : stage_variant_b<false>(k, stage_pressure, diag, dump, rect);
+}
+
+int launch_stage_kernel(const StageVariant& v, const StageArgs& a, const StageArgs* arr, int nt, int nbatch, hipStream_t st) {
+  hipLaunchKernelGGL(v.fn, dim3(nt, nbatch), dim3(kStageThreads), v.lds, st, a, arr);
   return (int)hipGetLastError();
 }
 
-// which instantiation runs RK stage k (diag: fuse the omega / palinstrophy work into stages 1 and 2)
-template <bool BATCH>
-int launch_stage_any(const StageArgs& a, const StageArgs* arr, int k, bool stage_pressure, bool diag, int nt,
-                     int nbatch, hipStream_t st, bool rect) {
-  if (stage_pressure) {   // FSG smoother: every stage differentiates its own input pressure; no diagnostics
-    if (k < 3) return launch_stage_kernel<true, false, false, BATCH, 0>(a, arr, nt, nbatch, st, rect);
-    return launch_stage_kernel<true, true, false, BATCH, 0>(a, arr, nt, nbatch, st, rect);
-  }
-  if (k == 0) return diag ? launch_stage_kernel<true, false, false, BATCH, 1>(a, arr, nt, nbatch, st, rect)
-                          : launch_stage_kernel<true, false, false, BATCH, 0>(a, arr, nt, nbatch, st, rect);
-  if (k == 1) return diag ? launch_stage_kernel<false, false, false, BATCH, 2>(a, arr, nt, nbatch, st, rect)
-                          : launch_stage_kernel<false, false, false, BATCH, 0>(a, arr, nt, nbatch, st, rect);
-  if (k == 2) return launch_stage_kernel<false, false, false, BATCH, 0>(a, arr, nt, nbatch, st, rect);
-  return launch_stage_kernel<false, true, false, BATCH, 0>(a, arr, nt, nbatch, st, rect);
-}
-
 int launch_stage(ldc_solver* s, int k, int diag, hipStream_t st) {
-  const StageArgs a = make_stage_args(s, k);
-  return launch_stage_any<false>(a, nullptr, k, s->p.stage_pressure != 0, diag != 0, s->nt, 1, st, s->p.Mx != s->p.My);
+  const StageArgs a = make_stage_args(s, k, s->nt);
+  const StageVariant v = stage_variant(k, s->p.stage_pressure != 0, diag != 0, false, s->p.Mx != s->p.My, false);
+  return launch_stage_kernel(v, a, nullptr, s->nt, 1, st);
 }
 
 FinalArgs make_final_args(const ldc_solver* s, int with_diag, int do_critical) {
@@ -1889,7 +1886,7 @@ FinalArgs make_final_args(const ldc_solver* s, int with_diag, int do_critical) {
 }
 
 // T1T/T2T (+ omega tiles) (+ the finalize block); `loop` = inside the iteration loop
-PostArgs make_post_args(const ldc_solver* s, const double* P, int do_omega, int loop, int with_diag, int* grid_out) {
+PostArgs make_post_args(const ldc_solver* s, const double* P, int do_omega, int loop, int with_diag, int tiles, int* grid_out) {
   const ldc_problem& p = s->p;
   PostArgs a;
   memset(&a, 0, sizeof(a));
@@ -1897,7 +1894,7 @@ PostArgs make_post_args(const ldc_solver* s, const double* P, int do_omega, int 
   a.Dx = p.Dx; a.Dy = p.Dy; a.IyF = p.IyF; a.GyF = p.GyF;
   a.U = p.U; a.V = p.V; a.VT = p.VT; a.P = P;
   a.NB = p.LD / 16;
-  a.wt = write_through_policy(s, s->nt);
+  a.wt = write_through_policy(s, tiles);
   a.PK = (P == p.PA) ? p.PAK : (P == p.PB) ? p.PBK : p.PK;
   a.IyFK = p.IyFK; a.GyFK = p.GyFK; a.T1TK = p.T1TK; a.T2TK = p.T2TK;
   a.DxK = p.DxK; a.DyK = p.DyK; a.UK = p.UK; a.VTK = p.VTK; a.WK = p.WK; a.WTK = p.WTK;
@@ -1918,7 +1915,7 @@ PostArgs make_post_args(const ldc_solver* s, const double* P, int do_omega, int 
 
 int launch_post(const ldc_solver* s, const double* P, int do_omega, int loop, int with_diag, hipStream_t st) {
   int grid = 0;
-  const PostArgs a = make_post_args(s, P, do_omega, loop, with_diag, &grid);
+  const PostArgs a = make_post_args(s, P, do_omega, loop, with_diag, s->nt, &grid);
   hipLaunchKernelGGL(post_kernel<false>, dim3(grid), dim3(kThreads), 0, st, a, (const PostArgs*)nullptr);
   return (int)hipGetLastError();
 }
@@ -1993,22 +1990,27 @@ int persistent_mode(const ldc_solver* s) {
 
 // ---- small-N trial kernel (mode 3) -----------------------------------------------------------------------------
 static_assert(XLds::BYTES_NST <= kLdsLimit - 1024, "small-N trial kernel LDS (plus its static words)");
+using XcdKernel = void (*)(const XLaunch);
+struct XcdVariant {
+  XcdKernel fn;       // nullptr: no such variant
+  size_t lds;
+};
 template <int T>
-int enable_xcd_lds_t() {
-  const void* k[3] = {reinterpret_cast<const void*>(xcd_kernel<T, false, false>), reinterpret_cast<const void*>(xcd_kernel<T, false, true>),
-                      reinterpret_cast<const void*>(xcd_kernel<T, true, false>)};
-  for (const void* f : k) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kXLdsBytes<T>);
-    if (e != hipSuccess) return (int)e;
+XcdVariant xcd_variant_of(bool sp, bool diag) {
+  return {sp ? xcd_kernel<T, true, false> : diag ? xcd_kernel<T, false, true> : xcd_kernel<T, false, false>, kXLdsBytes<T>};
+}
+// T tiles per axis (1 ... kXT), stage pressures (the smoother), diagnostics
+XcdVariant xcd_variant(int T, bool sp, bool diag) {
+  switch (T) {
+    case 1: return xcd_variant_of<1>(sp, diag);
+    case 2: return xcd_variant_of<2>(sp, diag);
+    case 3: return xcd_variant_of<3>(sp, diag);
+    case 4: return xcd_variant_of<4>(sp, diag);
+    case 5: return xcd_variant_of<5>(sp, diag);
+    default: return {nullptr, 0};
   }
-  return 0;
 }
-int enable_xcd_lds() {
-  int e;
-  if ((e = enable_xcd_lds_t<1>()) != 0 || (e = enable_xcd_lds_t<2>()) != 0 || (e = enable_xcd_lds_t<3>()) != 0 ||
-      (e = enable_xcd_lds_t<4>()) != 0 || (e = enable_xcd_lds_t<5>()) != 0) return e;
-  return 0;
-}
+static_assert(kXT == 5, "xcd_variant covers T = 1 ... kXT");
 int xcd_tiles(const ldc_solver* s) { return (s->p.M + 15) / 16; }
 // every tile's work-group on one XCD, one per CU; the packed arrays hold T x T blocks; a partial-sum row per tile
 bool xcd_available(const ldc_solver* s) {
@@ -2050,29 +2052,14 @@ XArgs make_xargs(const ldc_solver* s, int with_diag, unsigned* sync) {
   return a;
 }
 
-template <typename K>
-int xcd_launch_kernel(K kern, const XLaunch& xl, int nwg, int n_xcds, hipStream_t st, size_t lds_bytes) {
+int xcd_launch(const XLaunch& xl, bool sp, bool diag, int T, int n_xcds, hipStream_t st) {
+  const XcdVariant v = xcd_variant(T, sp, diag);
+  if (v.fn == nullptr) return LDC_E_ARG;
   // work-groups are dealt round-robin over the XCDs: (slots x tiles + 8) per XCD put at least slots x tiles of them on
   // every XCD; the surplus leaves at once
-  const int per_xcd = ((xl.B + n_xcds - 1) / n_xcds) * nwg + 8;
-  hipLaunchKernelGGL(kern, dim3(n_xcds * per_xcd), dim3(kStageThreads), lds_bytes, st, xl);
+  const int per_xcd = ((xl.B + n_xcds - 1) / n_xcds) * (T * T) + 8;
+  hipLaunchKernelGGL(v.fn, dim3(n_xcds * per_xcd), dim3(kStageThreads), v.lds, st, xl);
   return (int)hipGetLastError();
-}
-template <int T>
-int xcd_launch_t(const XLaunch& xl, bool sp, bool diag, int n_xcds, hipStream_t st) {
-  if (sp) return xcd_launch_kernel(xcd_kernel<T, true, false>, xl, T * T, n_xcds, st, kXLdsBytes<T>);
-  if (diag) return xcd_launch_kernel(xcd_kernel<T, false, true>, xl, T * T, n_xcds, st, kXLdsBytes<T>);
-  return xcd_launch_kernel(xcd_kernel<T, false, false>, xl, T * T, n_xcds, st, kXLdsBytes<T>);
-}
-int xcd_launch_any(const XLaunch& xl, bool sp, bool diag, int T, int n_xcds, hipStream_t st) {
-  switch (T) {
-    case 1: return xcd_launch_t<1>(xl, sp, diag, n_xcds, st);
-    case 2: return xcd_launch_t<2>(xl, sp, diag, n_xcds, st);
-    case 3: return xcd_launch_t<3>(xl, sp, diag, n_xcds, st);
-    case 4: return xcd_launch_t<4>(xl, sp, diag, n_xcds, st);
-    case 5: return xcd_launch_t<5>(xl, sp, diag, n_xcds, st);
-    default: return LDC_E_ARG;
-  }
 }
 
 // one trial: the launch words in [LDC_SYNC_XLAUNCH, +XG_LEN) and the flags in [LDC_SYNC_XFLAGS, +XS_LEN) of its own sync array
@@ -2087,7 +2074,7 @@ int launch_xcd(ldc_solver* s, int n_iters, int with_diag, hipStream_t st) {
   static_assert(LDC_SYNC_XLAUNCH + XG_LEN <= LDC_SYNC_XFLAGS && LDC_SYNC_XFLAGS + XS_LEN <= LDC_SYNC_XRING &&
                 LDC_SYNC_XRING + 2 * kXT * kXT * 64 <= LDC_SYNC_LEN, "sync array layout");
   HIP_TRY(hipMemsetAsync(s->p.sync + LDC_SYNC_XLAUNCH, 0, sizeof(uint32_t) * (LDC_SYNC_XFLAGS + XS_LEN - LDC_SYNC_XLAUNCH), st));
-  return xcd_launch_any(xl, s->p.stage_pressure != 0, with_diag != 0, T, s->n_xcds, st);
+  return xcd_launch(xl, s->p.stage_pressure != 0, with_diag != 0, T, s->n_xcds, st);
 }
 
 // ---- chip-wide trial kernel (mode 5) ---------------------------------------------------------------------------
@@ -2119,16 +2106,12 @@ bool wide_available(const ldc_solver* s) {
   return s->p.sync != nullptr && T >= kWTmin && T <= kWT && T * T <= s->n_cus && s->p.LD / 16 >= T &&
          s->p.partials_stride >= (int64_t)PS_N * ((T * T + 3) & ~3) && s->p.partials_stride % 4 == 0 && wlds_bytes(T) + 256 <= kLdsLimit;
 }
-bool use_wide(const ldc_solver* s) { return persistent_mode(s) == 5; }
-int enable_wide_lds() {
-  const void* k[5] = {reinterpret_cast<const void*>(wide_kernel<false, false, false>), reinterpret_cast<const void*>(wide_kernel<false, true, false>),
-                      reinterpret_cast<const void*>(wide_kernel<true, false, false>),
-                      reinterpret_cast<const void*>(wide_kernel<false, false, true>), reinterpret_cast<const void*>(wide_kernel<false, true, true>)};
-  for (const void* f : k) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds_bytes(kWT));
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
+using WideKernel = void (*)(const WLaunch);
+// stage pressures (the smoother: the tiles layout only), diagnostics, layout; the dynamic LDS follows T (wlds_bytes)
+WideKernel wide_variant(bool sp, bool diag, bool tail) {
+  if (sp) return tail ? nullptr : wide_kernel<true, false, false>;
+  if (tail) return diag ? wide_kernel<false, true, true> : wide_kernel<false, false, true>;
+  return diag ? wide_kernel<false, true, false> : wide_kernel<false, false, false>;
 }
 
 WArgs make_wargs(const ldc_solver* s, int with_diag) {
@@ -2168,14 +2151,10 @@ WArgs make_wargs(const ldc_solver* s, int with_diag) {
 static_assert(LDC_SYNC_WFLAGS + 32 * kWT * kWT <= LDC_SYNC_WRING && LDC_SYNC_WRING + 2 * (64 * kWT * kWT + 6 * 16 * kWT + (2 * kWT + 1) * kWJobDoubles) <= LDC_SYNC_LEN,
               "sync array layout (chip-wide kernel)");
 
-int wide_launch_any(const WLaunch& wl, int T, bool sp, bool diag, bool tail, hipStream_t st) {
-  const dim3 grid(wl.B * T * T), block(kStageThreads);
-  const size_t bytes = wlds_bytes(T);
-  if (sp) hipLaunchKernelGGL((wide_kernel<true, false, false>), grid, block, bytes, st, wl);
-  else if (tail && diag) hipLaunchKernelGGL((wide_kernel<false, true, true>), grid, block, bytes, st, wl);
-  else if (tail) hipLaunchKernelGGL((wide_kernel<false, false, true>), grid, block, bytes, st, wl);
-  else if (diag) hipLaunchKernelGGL((wide_kernel<false, true, false>), grid, block, bytes, st, wl);
-  else hipLaunchKernelGGL((wide_kernel<false, false, false>), grid, block, bytes, st, wl);
+int wide_launch(const WLaunch& wl, int T, bool sp, bool diag, bool tail, hipStream_t st) {
+  const WideKernel fn = wide_variant(sp, diag, tail);
+  if (fn == nullptr) return LDC_E_ARG;
+  hipLaunchKernelGGL(fn, dim3(wl.B * T * T), dim3(kStageThreads), wlds_bytes(T), st, wl);
   return (int)hipGetLastError();
 }
 int launch_wide(ldc_solver* s, int n_iters, int with_diag, hipStream_t st) {
@@ -2185,7 +2164,7 @@ int launch_wide(ldc_solver* s, int n_iters, int with_diag, hipStream_t st) {
   wl.B = 1; wl.n_iters = n_iters; wl.trials = nullptr;
   wl.one = make_wargs(s, with_diag);
   HIP_TRY(hipMemsetAsync(s->p.sync + LDC_SYNC_WFLAGS, 0, sizeof(uint32_t) * 32 * T * T, st));
-  return wide_launch_any(wl, T, s->p.stage_pressure != 0, with_diag != 0, wide_tail(s), st);
+  return wide_launch(wl, T, s->p.stage_pressure != 0, with_diag != 0, wide_tail(s), st);
 }
 // The hand-over flags of a launch group's trials (blockIdx.y = trial of the group), each in its own sync array: one launch
 // instead of a memset per trial.
@@ -2196,30 +2175,39 @@ __global__ void wide_flags_zero_kernel(const WArgs* trials, int words) {
 
 // ---- trial-per-CU kernel (mode 4) ------------------------------------------------------------------------------
 constexpr size_t kCuLdsMax = kLdsLimit - 128;        // (the kernel also has 48 bytes of static LDS: its control block)
+using CuKernel = void (*)(const CLaunch);
+struct CuVariant {
+  CuKernel fn;        // nullptr: no such variant
+  int block;          // threads per work-group
+};
 template <int T, bool EDGE>
-int enable_cu_lds_t() {
-  const void* k[3] = {reinterpret_cast<const void*>(cu_kernel<T, EDGE, false, false>),
-                      reinterpret_cast<const void*>(cu_kernel<T, EDGE, false, true>),
-                      reinterpret_cast<const void*>(cu_kernel<T, EDGE, true, false>)};
-  for (const void* f : k) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCuLdsMax);
-    if (e != hipSuccess) return (int)e;
+CuVariant cu_variant_of(bool sp, bool diag) {
+  return {sp ? cu_kernel<T, EDGE, true, false> : diag ? cu_kernel<T, EDGE, false, true> : cu_kernel<T, EDGE, false, false>,
+          64 * (T * T + ((EDGE || T < 3) ? kCHelp : 0))};
+}
+// T tiles per axis, EDGE (index M-1 outside the tiles: T = 1, 2), stage pressures (the smoother), diagnostics
+CuVariant cu_variant(int T, bool edge, bool sp, bool diag) {
+  if (edge) {
+    switch (T) {
+      case 1: return cu_variant_of<1, true>(sp, diag);
+      case 2: return cu_variant_of<2, true>(sp, diag);
+      default: return {nullptr, 0};
+    }
   }
-  return 0;
+  switch (T) {
+    case 1: return cu_variant_of<1, false>(sp, diag);
+    case 2: return cu_variant_of<2, false>(sp, diag);
+    case 3: return cu_variant_of<3, false>(sp, diag);
+    default: return {nullptr, 0};
+  }
 }
-int enable_cu_lds() {
-  int e;
-  if ((e = enable_cu_lds_t<1, false>()) != 0 || (e = enable_cu_lds_t<2, false>()) != 0 || (e = enable_cu_lds_t<3, false>()) != 0 ||
-      (e = enable_cu_lds_t<1, true>()) != 0 || (e = enable_cu_lds_t<2, true>()) != 0) return e;
-  return 0;
-}
+static_assert(kCT == 3, "cu_variant covers T = 1 ... kCT");
 // the stage state of the trial, in both orientations, and the operators fit one CU's LDS
 bool cu_available(const ldc_solver* s) {
   const int M = s->p.M;
   return s->p.Mx == s->p.My && M >= 3 && M <= kCMaxM && cu_tiles(M) <= kCT && s->p.LD / 16 >= (M + 15) / 16 && cu_lds_bytes(M) <= kCuLdsMax &&
          s->p.partials_stride >= (int64_t)LDC_NPART;
 }
-bool use_cu(const ldc_solver* s) { return persistent_mode(s) == 4; }
 
 CArgs make_cargs(const ldc_solver* s, int with_diag) {
   const ldc_problem& p = s->p;
@@ -2240,38 +2228,19 @@ CArgs make_cargs(const ldc_solver* s, int with_diag) {
   return a;
 }
 
-template <int T, bool EDGE>
-int cu_launch_t(const CLaunch& cl, bool sp, bool diag, size_t lds_bytes, hipStream_t st) {
-  const dim3 grid(cl.B), block(64 * (T * T + ((EDGE || T < 3) ? kCHelp : 0)));
-  if (sp) hipLaunchKernelGGL((cu_kernel<T, EDGE, true, false>), grid, block, lds_bytes, st, cl);
-  else if (diag) hipLaunchKernelGGL((cu_kernel<T, EDGE, false, true>), grid, block, lds_bytes, st, cl);
-  else hipLaunchKernelGGL((cu_kernel<T, EDGE, false, false>), grid, block, lds_bytes, st, cl);
+int cu_launch(const CLaunch& cl, const ldc_solver* s0, int with_diag, hipStream_t st) {
+  const int M = s0->p.M;
+  const CuVariant v = cu_variant(cu_tiles(M), cu_edge(M), s0->p.stage_pressure != 0, with_diag != 0);
+  if (v.fn == nullptr) return LDC_E_ARG;
+  hipLaunchKernelGGL(v.fn, dim3(cl.B), dim3(v.block), cu_lds_bytes(M), st, cl);
   return (int)hipGetLastError();
-}
-int cu_launch_any(const CLaunch& cl, const ldc_solver* s0, int with_diag, hipStream_t st) {
-  const int M = s0->p.M, T = cu_tiles(M);
-  const bool sp = s0->p.stage_pressure != 0, diag = with_diag != 0;
-  const size_t bytes = cu_lds_bytes(M);
-  if (cu_edge(M)) {
-    switch (T) {
-      case 1: return cu_launch_t<1, true>(cl, sp, diag, bytes, st);
-      case 2: return cu_launch_t<2, true>(cl, sp, diag, bytes, st);
-      default: return LDC_E_ARG;
-    }
-  }
-  switch (T) {
-    case 1: return cu_launch_t<1, false>(cl, sp, diag, bytes, st);
-    case 2: return cu_launch_t<2, false>(cl, sp, diag, bytes, st);
-    case 3: return cu_launch_t<3, false>(cl, sp, diag, bytes, st);
-    default: return LDC_E_ARG;
-  }
 }
 int launch_cu(ldc_solver* s, int n_iters, int with_diag, hipStream_t st) {
   CLaunch cl;
   memset(&cl, 0, sizeof(cl));
   cl.B = 1; cl.n_iters = n_iters; cl.trials = nullptr;
   cl.one = make_cargs(s, with_diag);
-  return cu_launch_any(cl, s, with_diag, st);
+  return cu_launch(cl, s, with_diag, st);
 }
 
 // Captures record kernel launches on a private non-blocking stream and nothing else, so no call anywhere needs to be
@@ -2334,86 +2303,94 @@ int ensure_kernel_attributes() {
   HIP_TRY(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
   if (g_attrs_done[dev]) return 0;
-  int e;
-  if ((e = enable_stage_lds_all<false>()) != 0 || (e = enable_stage_lds_all<true>()) != 0 || (e = enable_xcd_lds()) != 0 ||
-      (e = enable_cu_lds()) != 0 || (e = enable_wide_lds()) != 0)
-    return e;
+  // every variant of every family, with the most dynamic LDS any launch of it asks for
+  auto allow = [](auto fn, size_t bytes) {
+    return fn ? hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)
+              : hipSuccess;
+  };
+  for (int f = 0; f < 128; ++f)         // bits: stage k (2), stage pressures, diagnostics, dump, rect, batch
+    HIP_TRY(allow(stage_variant(f & 3, f & 4, f & 8, f & 16, f & 32, f & 64).fn, kLdsLimit));
+  for (int f = 0; f < 4; ++f) {         // bits: stage pressures, diagnostics
+    for (int T = 1; T <= kXT; ++T) {
+      const XcdVariant v = xcd_variant(T, f & 1, f & 2);
+      HIP_TRY(allow(v.fn, v.lds));
+    }
+    for (int T = 1; T <= kCT; ++T)
+      for (int edge = 0; edge < 2; ++edge) HIP_TRY(allow(cu_variant(T, edge, f & 1, f & 2).fn, kCuLdsMax));
+    for (int tail = 0; tail < 2; ++tail) HIP_TRY(allow(wide_variant(f & 1, f & 2, tail), wlds_bytes(kWT)));
+  }
   g_attrs_done[dev] = true;
   ++g_attr_rounds;
   return 0;
 }
 
-#ifdef LDC_TIMING
-// Timing probe (instrumented build, LDC_FORK_PROBE=1; RESULTS ARE WRONG): the iteration captured as a FORKED graph -- after
-// stage 3 the post launch goes to a side branch beside stage 4 instead of behind it.  The branch reads what stage 4 is
-// still writing (the real thing would need a div(u3) -> p kernel in front of the transforms), so only the TIMING means
-// anything: it answers whether a second launch finds room beside the 256 x 512-thread work-groups of stage 4 at all.
-int launch_iteration_forked(ldc_solver* s, int with_diag, hipStream_t st, hipStream_t side, hipEvent_t fork, hipEvent_t join) {
-  int e;
-  for (int k = 0; k < 3; ++k) if ((e = launch_stage(s, k, with_diag, st)) != 0) return e;
-  HIP_TRY(hipEventRecord(fork, st));
-  HIP_TRY(hipStreamWaitEvent(side, fork, 0));
-  if ((e = launch_stage(s, 3, with_diag, st)) != 0) return e;
-  if ((e = launch_post(s, s->p.P, 0, 1, with_diag, side)) != 0) return e;
-  HIP_TRY(hipEventRecord(join, side));
-  HIP_TRY(hipStreamWaitEvent(st, join, 0));
+// Every graph of the library is captured here: enqueue(capture stream) on the device's setup stream, under the setup mutex,
+// then instantiated into *out; the template graph is destroyed on every path.
+template <typename F>
+int capture(F&& enqueue, hipGraphExec_t* out) {
+  std::lock_guard<std::mutex> lock(g_setup_mutex);
+  hipStream_t cs = nullptr;
+  HIP_TRY(setup_stream(&cs));
+  HIP_TRY(hipStreamBeginCapture(cs, kCaptureMode));
+  const int e = enqueue(cs);
+  hipGraph_t g = nullptr;
+  const hipError_t ce = hipStreamEndCapture(cs, &g);
+  if (e != 0 || ce != hipSuccess) {
+    if (g) (void)hipGraphDestroy(g);
+    return e != 0 ? e : (int)ce;
+  }
+  const hipError_t ie = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  if (ie != hipSuccess) *out = nullptr;
+  return (int)ie;
+}
+
+}  // namespace
+
+template <typename F>
+int ChunkCache::launch(int n_iters, int with_diag, hipStream_t st, F&& enqueue) {
+  Slot* slots = slot[with_diag];
+  Slot* c = nullptr;
+  for (int k = 0; k < kLengths && c == nullptr; ++k)
+    if (slots[k].exec && slots[k].n_iters == n_iters) c = &slots[k];
+  if (c == nullptr) {
+    c = &slots[0];
+    for (int k = 0; k < kLengths; ++k) {
+      if (slots[k].exec == nullptr) { c = &slots[k]; break; }
+      if (slots[k].used < c->used) c = &slots[k];
+    }
+    {
+      std::lock_guard<std::mutex> lock(g_setup_mutex);
+      if (c->exec) {
+        HIP_TRY(hipEventSynchronize(c->done));
+        (void)hipGraphExecDestroy(c->exec);
+        c->exec = nullptr; c->n_iters = 0;
+      }
+      // (no system-scope fence: the event only says that a launch has completed, nothing reads memory through it; the fence
+      //  cost a 20-iteration enqueue about 3 us)
+      if (c->done == nullptr) HIP_TRY(hipEventCreateWithFlags(&c->done, hipEventDisableTiming | hipEventDisableSystemFence));
+    }
+    const int e = capture(enqueue, &c->exec);
+    if (e) return e;
+    c->n_iters = n_iters;
+  }
+  HIP_TRY(hipGraphLaunch(c->exec, st));
+  HIP_TRY(hipEventRecord(c->done, st));
+  c->used = ++clock;
   return 0;
 }
-#endif
 
-int build_graph(ldc_solver* s, int with_diag) {
+void ChunkCache::clear() {
   std::lock_guard<std::mutex> lock(g_setup_mutex);
-  HIP_TRY(setup_stream(&s->capture_stream));
-  hipGraph_t g = nullptr;
-#ifdef LDC_TIMING
-  static hipStream_t side = nullptr;
-  static hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  const char* fp = getenv("LDC_FORK_PROBE");
-  const bool forked = fp != nullptr && fp[0] == '1' && s->p.stage_pressure == 0;
-  if (forked && side == nullptr) {
-    HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-  }
-#endif
-  HIP_TRY(hipStreamBeginCapture(s->capture_stream, kCaptureMode));
-  int e = 0;
-#ifdef LDC_TIMING
-  if (forked) {
-    for (int it = 0; it < s->iters_per_graph && e == 0; ++it)
-      e = launch_iteration_forked(s, with_diag, s->capture_stream, side, ev_fork, ev_join);
-  } else
-#endif
-  for (int it = 0; it < s->iters_per_graph && e == 0; ++it) e = launch_iteration(s, with_diag, s->capture_stream);
-  hipError_t ce = hipStreamEndCapture(s->capture_stream, &g);
-  if (e != 0) { if (g) (void)hipGraphDestroy(g); return e; }
-  if (ce != hipSuccess) return (int)ce;
-  hipError_t ie = hipGraphInstantiate(&s->graph[with_diag], g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  return (int)ie;
+  for (auto& form : slot)
+    for (Slot& c : form) {
+      if (c.exec) { (void)hipEventSynchronize(c.done); (void)hipGraphExecDestroy(c.exec); }
+      if (c.done) (void)hipEventDestroy(c.done);
+      c = Slot();
+    }
 }
 
-int enqueue_wide_chunk(ldc_solver* s, int n_iters, int with_diag, hipStream_t st) {
-  int e = launch_wide(s, n_iters, with_diag, st);
-  if (e) return e;
-  // (the closing diagnostics' own post launch forms the transforms too: no second one in front of it)
-  return with_diag ? launch_closing_diagnostics(s, st) : launch_post(s, s->p.P, 0, 0, 0, st);
-}
-int build_chunk_graph(ldc_solver* s, int n_iters, int with_diag) {
-  std::lock_guard<std::mutex> lock(g_setup_mutex);
-  if (s->chunk_graph[with_diag]) { (void)hipGraphExecDestroy(s->chunk_graph[with_diag]); s->chunk_graph[with_diag] = nullptr; s->chunk_iters[with_diag] = 0; }
-  HIP_TRY(setup_stream(&s->capture_stream));
-  hipGraph_t g = nullptr;
-  HIP_TRY(hipStreamBeginCapture(s->capture_stream, kCaptureMode));
-  const int e = enqueue_wide_chunk(s, n_iters, with_diag, s->capture_stream);
-  const hipError_t ce = hipStreamEndCapture(s->capture_stream, &g);
-  if (e != 0) { if (g) (void)hipGraphDestroy(g); return e; }
-  if (ce != hipSuccess) return (int)ce;
-  const hipError_t ie = hipGraphInstantiate(&s->chunk_graph[with_diag], g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (ie == hipSuccess) s->chunk_iters[with_diag] = n_iters;
-  return (int)ie;
-}
+namespace {
 
 size_t batch_bytes(int B) {
   auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
@@ -2425,11 +2402,11 @@ size_t batch_bytes(int B) {
 int batch_launch_stage(ldc_batch* b, int k, int diag, hipStream_t st) {
   const ldc_solver* s0 = b->s[0];
   const StageArgs dummy = {};
-  return launch_stage_any<true>(dummy, b->d_stage[k], k, s0->p.stage_pressure != 0, diag != 0, s0->nt, b->B, st,
-                                s0->p.Mx != s0->p.My);
+  const StageVariant v = stage_variant(k, s0->p.stage_pressure != 0, diag != 0, false, s0->p.Mx != s0->p.My, true);
+  return launch_stage_kernel(v, dummy, b->d_stage[k], s0->nt, b->B, st);
 }
 
-int batch_launch_iteration(ldc_batch* b, int with_diag, hipStream_t st) {
+int launch_iteration(ldc_batch* b, int with_diag, hipStream_t st) {
   const ldc_solver* s0 = b->s[0];
   const PostArgs pdummy = {};
   int e;
@@ -2446,7 +2423,7 @@ int batch_launch_iteration(ldc_batch* b, int with_diag, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-int batch_closing_diagnostics(ldc_batch* b, hipStream_t st) {
+int launch_closing_diagnostics(ldc_batch* b, hipStream_t st) {
   const ldc_solver* s0 = b->s[0];
   const PostArgs pdummy = {};
   const PalinArgs qdummy = {};
@@ -2462,10 +2439,43 @@ int batch_closing_diagnostics(ldc_batch* b, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+// What closes an enqueue on one of the trial kernels (modes 3, 4, 5): the transforms of the final pressure in the launch
+// path's form (row M-1 of the row-major T1T / T2T in the tail layout), so that whatever runs next finds the state it expects,
+// and with diagnostics the closing record.  A lone trial's closing record forms the transforms by its own post launch: no
+// second one in front of it.
+int finish_chunk(ldc_solver* s, int with_diag, hipStream_t st) {
+  return with_diag ? launch_closing_diagnostics(s, st) : launch_post(s, s->p.P, 0, 0, 0, st);
+}
+int finish_chunk(ldc_batch* b, int with_diag, hipStream_t st) {
+  const PostArgs pdummy = {};
+  hipLaunchKernelGGL(post_kernel<true>, dim3(b->postP_grid, b->B), dim3(kThreads), 0, st, pdummy, (const PostArgs*)b->d_postP);
+  HIP_TRY(hipGetLastError());
+  return with_diag ? launch_closing_diagnostics(b, st) : 0;
+}
+
+// The launch path (mode 0) of either handle kind: graphs of iters_per_graph iterations (captured by the first enqueue that
+// needs one, kept for the handle's life), the rest iteration by iteration, then the closing record.
+template <typename H>
+int enqueue_launch_path(H* h, int n_iters, int with_diag, hipStream_t st) {
+  int left = n_iters;
+  if (left >= h->iters_per_graph) {
+    if (!h->graph[with_diag]) {
+      const int e = capture([&](hipStream_t cs) {
+        int r = 0;
+        for (int it = 0; it < h->iters_per_graph && r == 0; ++it) r = launch_iteration(h, with_diag, cs);
+        return r;
+      }, &h->graph[with_diag]);
+      if (e) return e;
+    }
+    for (; left >= h->iters_per_graph; left -= h->iters_per_graph) HIP_TRY(hipGraphLaunch(h->graph[with_diag], st));
+  }
+  for (; left > 0; --left) { const int e = launch_iteration(h, with_diag, st); if (e) return e; }
+  return (with_diag && n_iters > 0) ? launch_closing_diagnostics(h, st) : 0;
+}
+
 // Batch form of the chip-wide kernel (mode 5): launch groups of wG trials, each launch wG x T^2 work-groups (one per CU), the
-// group's flags zeroed in front of it; then the transforms of the final pressures and the closing record of every trial, as
-// behind the small-N kernel's batch launches.  The groups run one after another on the stream: the next group's work-groups
-// find the CUs the previous one has left.
+// group's flags zeroed in front of it; then the closing launches.  The groups run one after another on the stream: the next
+// group's work-groups find the CUs the previous one has left.
 int enqueue_wide_batch_chunk(ldc_batch* b, int n_iters, int with_diag, hipStream_t st) {
   const ldc_solver* s0 = b->s[0];
   const int T = b->wT, words = 32 * T * T;
@@ -2477,61 +2487,10 @@ int enqueue_wide_batch_chunk(ldc_batch* b, int n_iters, int with_diag, hipStream
     WLaunch wl;
     memset(&wl, 0, sizeof(wl));
     wl.B = g; wl.n_iters = n_iters; wl.trials = b->d_wargs[with_diag] + lo;
-    const int e = wide_launch_any(wl, T, s0->p.stage_pressure != 0, with_diag != 0, b->wtail != 0, st);
+    const int e = wide_launch(wl, T, s0->p.stage_pressure != 0, with_diag != 0, b->wtail != 0, st);
     if (e) return e;
   }
-  const PostArgs pdummy = {};
-  hipLaunchKernelGGL(post_kernel<true>, dim3(b->postP_grid, b->B), dim3(kThreads), 0, st, pdummy, (const PostArgs*)b->d_postP);
-  HIP_TRY(hipGetLastError());
-  return with_diag ? batch_closing_diagnostics(b, st) : 0;
-}
-// The chunk of n_iters iterations as ONE graph, kept in a cache of kWChunkCache lengths per diagnostics form (a solve's
-// chunks are check_every long and its last one shorter).  A slot is reused least-recently-used first, and only after the
-// event behind its graph's latest launch has completed: a launch still queued on the caller's stream never loses its graph.
-int batch_wide_chunk(ldc_batch* b, int n_iters, int with_diag, WChunk** out) {
-  WChunk* slots = b->wchunk[with_diag];
-  for (int k = 0; k < kWChunkCache; ++k)
-    if (slots[k].n_iters == n_iters && slots[k].exec) { *out = &slots[k]; return 0; }
-  std::lock_guard<std::mutex> lock(g_setup_mutex);
-  WChunk* c = &slots[0];
-  for (int k = 0; k < kWChunkCache; ++k) {
-    if (slots[k].exec == nullptr) { c = &slots[k]; break; }
-    if (slots[k].used < c->used) c = &slots[k];
-  }
-  if (c->exec) {
-    HIP_TRY(hipEventSynchronize(c->done));
-    (void)hipGraphExecDestroy(c->exec);
-    c->exec = nullptr; c->n_iters = 0;
-  }
-  if (c->done == nullptr) HIP_TRY(hipEventCreateWithFlags(&c->done, hipEventDisableTiming));
-  HIP_TRY(setup_stream(&b->capture_stream));
-  hipGraph_t g = nullptr;
-  HIP_TRY(hipStreamBeginCapture(b->capture_stream, kCaptureMode));
-  const int e = enqueue_wide_batch_chunk(b, n_iters, with_diag, b->capture_stream);
-  const hipError_t ce = hipStreamEndCapture(b->capture_stream, &g);
-  if (e != 0) { if (g) (void)hipGraphDestroy(g); return e; }
-  if (ce != hipSuccess) return (int)ce;
-  const hipError_t ie = hipGraphInstantiate(&c->exec, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (ie != hipSuccess) { c->exec = nullptr; return (int)ie; }
-  c->n_iters = n_iters;
-  *out = c;
-  return 0;
-}
-
-int batch_build_graph(ldc_batch* b, int with_diag) {
-  std::lock_guard<std::mutex> lock(g_setup_mutex);
-  HIP_TRY(setup_stream(&b->capture_stream));
-  hipGraph_t g = nullptr;
-  HIP_TRY(hipStreamBeginCapture(b->capture_stream, kCaptureMode));
-  int e = 0;
-  for (int it = 0; it < b->iters_per_graph && e == 0; ++it) e = batch_launch_iteration(b, with_diag, b->capture_stream);
-  hipError_t ce = hipStreamEndCapture(b->capture_stream, &g);
-  if (e != 0) { if (g) (void)hipGraphDestroy(g); return e; }
-  if (ce != hipSuccess) return (int)ce;
-  hipError_t ie = hipGraphInstantiate(&b->graph[with_diag], g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  return (int)ie;
+  return finish_chunk(b, with_diag, st);
 }
 
 bool bad_ptr(const void* p) { return p == nullptr; }
@@ -2622,19 +2581,16 @@ int ldc_solver_create(const ldc_problem* d, ldc_solver** out) {
   s->ablate = 0;
   s->stamps = nullptr;
   s->graph[0] = s->graph[1] = nullptr;
-  s->chunk_graph[0] = s->chunk_graph[1] = nullptr;
-  s->chunk_iters[0] = s->chunk_iters[1] = 0;
-  s->capture_stream = nullptr;
   *out = s;
   return 0;
 }
 
 int ldc_solver_destroy(ldc_solver* s) {
   if (!s) return LDC_E_STATE;
+  s->chunks.clear();
   {
     std::lock_guard<std::mutex> lock(g_setup_mutex);
     for (int q = 0; q < 2; ++q) if (s->graph[q]) (void)hipGraphExecDestroy(s->graph[q]);
-    for (int q = 0; q < 2; ++q) if (s->chunk_graph[q]) (void)hipGraphExecDestroy(s->chunk_graph[q]);
   }
   delete s;
   return 0;
@@ -2650,10 +2606,7 @@ int ldc_solver_set_graph_iters(ldc_solver* s, int n) {
 int ldc_solver_set_persistent(ldc_solver* s, int mode) {
   if (!s) return LDC_E_STATE;
   if (mode < -1 || mode > 5 || mode == 1 || mode == 2) return LDC_E_ARG;          // (1, 2: the round-2 persistent kernel, removed)
-  {
-    std::lock_guard<std::mutex> lock(g_setup_mutex);          // (a chunk graph holds the kernel of the mode it was captured under)
-    for (int q = 0; q < 2; ++q) if (s->chunk_graph[q]) { (void)hipGraphExecDestroy(s->chunk_graph[q]); s->chunk_graph[q] = nullptr; s->chunk_iters[q] = 0; }
-  }
+  s->chunks.clear();          // (a chunk graph holds the kernel of the mode it was captured under)
   s->persist_mode = mode;
   if (mode == 3 && !xcd_available(s)) { s->persist_mode = -1; return LDC_E_ARG; }
   if (mode == 4 && !cu_available(s)) { s->persist_mode = -1; return LDC_E_ARG; }
@@ -2786,39 +2739,20 @@ int ldc_solver_enqueue(ldc_solver* s, int n_iters, int with_diag, void* stream) 
   // (a single iteration always goes launch by launch: nothing to gain, and it is the form the host uses for the first
   //  iteration after an upload, when phi^n may still carry other values on the row / column of index M-1 than the
   //  stage buffers do -- the tile-resident kernel stages those boundary values ONCE, from phi^n)
-  if (n_iters > 1 && use_xcd(s)) {
-    // the small-N trial kernel, then the transforms of the final pressure in the launch path's form (row M-1 of the
-    // row-major T1T / T2T in the tail layout): whatever runs next finds the state it expects
-    int e = launch_xcd(s, n_iters, with_diag, st);
-    if (e) return e;
-    return with_diag ? launch_closing_diagnostics(s, st) : launch_post(s, s->p.P, 0, 0, 0, st);      // (either forms the transforms)
+  const int mode = n_iters > 1 ? persistent_mode(s) : 0;
+  if (mode == 3 || mode == 4) {
+    const int e = mode == 3 ? launch_xcd(s, n_iters, with_diag, st) : launch_cu(s, n_iters, with_diag, st);
+    return e ? e : finish_chunk(s, with_diag, st);
   }
-  if (n_iters > 1 && use_wide(s)) {
-    // the chip-wide trial kernel, then the transforms of the final pressure in the launch path's form and the closing record: five
-    // nodes (the flags' memset, the kernel, up to four closing launches) as ONE graph per chunk length -- launched one by one
+  if (mode == 5) {
+    // the flags' memset, the kernel and up to four closing launches as ONE graph per chunk length -- launched one by one
     // they cost 76 us of gaps per enqueue, as much as two iterations (the driver's bench line times chunks of 20)
-    if (s->chunk_graph[with_diag] == nullptr || s->chunk_iters[with_diag] != n_iters) {
-      const int e = build_chunk_graph(s, n_iters, with_diag);
-      if (e) return e;
-    }
-    HIP_TRY(hipGraphLaunch(s->chunk_graph[with_diag], st));
-    return 0;
+    return s->chunks.launch(n_iters, with_diag, st, [&](hipStream_t cs) {
+      const int e = launch_wide(s, n_iters, with_diag, cs);
+      return e ? e : finish_chunk(s, with_diag, cs);
+    });
   }
-  if (n_iters > 1 && use_cu(s)) {
-    int e = launch_cu(s, n_iters, with_diag, st);
-    if (e) return e;
-    return with_diag ? launch_closing_diagnostics(s, st) : launch_post(s, s->p.P, 0, 0, 0, st);
-  }
-  int left = n_iters;
-  if (left >= s->iters_per_graph) {
-    if (!s->graph[with_diag]) { int e = build_graph(s, with_diag); if (e) return e; }
-    while (left >= s->iters_per_graph) {
-      HIP_TRY(hipGraphLaunch(s->graph[with_diag], st));
-      left -= s->iters_per_graph;
-    }
-  }
-  for (; left > 0; --left) { int e = launch_iteration(s, with_diag, st); if (e) return e; }
-  return (with_diag && n_iters > 0) ? launch_closing_diagnostics(s, st) : 0;
+  return enqueue_launch_path(s, n_iters, with_diag, st);
 }
 
 size_t ldc_batch_workspace_bytes(int n_trials) { return n_trials > 0 ? batch_bytes(n_trials) : 0; }
@@ -2864,102 +2798,56 @@ int ldc_batch_create(ldc_solver* const* solvers, int n_trials, void* workspace, 
   b->s.assign(solvers, solvers + n_trials);
   b->iters_per_graph = s0->iters_per_graph;
   b->graph[0] = b->graph[1] = nullptr;
-  b->capture_stream = nullptr;
-  memset(b->wchunk, 0, sizeof(b->wchunk));
-  b->wclock = 0;
   {
     const char* kn = getenv("LDC_BATCH_WIDE");
     b->wide_knob = (kn != nullptr && strcmp(kn, "1") == 0) ? 1 : 0;
   }
+  // The argument blocks, one per trial, in the order of batch_bytes(); the write-through policy of a launch over every
+  // trial counts the tiles of all of them
   auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
   char* w = static_cast<char*>(workspace);
-  auto carve = [&](size_t bytes) { char* r = w; w += up(bytes); return r; };
-  hipError_t he = hipSuccess;
-  auto put = [&](void* dst, const void* src, size_t bytes) {
-    if (he == hipSuccess) he = copy_now(dst, src, bytes, hipMemcpyHostToDevice);
+  auto carve = [&](auto*& dst, size_t count) {
+    dst = reinterpret_cast<std::remove_reference_t<decltype(dst)>>(w);
+    w += up(sizeof(*dst) * count);
   };
-  for (int k = 0; k < 4; ++k) {
-    std::vector<StageArgs> h(n_trials);
-    for (int q = 0; q < n_trials; ++q) {
-      h[q] = make_stage_args(solvers[q], k);
-      h[q].wt = write_through_policy(solvers[q], solvers[q]->nt * n_trials);
-    }
-    b->d_stage[k] = reinterpret_cast<StageArgs*>(carve(sizeof(StageArgs) * n_trials));
-    put(b->d_stage[k], h.data(), sizeof(StageArgs) * n_trials);
-  }
-  for (int wd = 0; wd < 2; ++wd) {
-    std::vector<PostArgs> h(n_trials);
-    for (int q = 0; q < n_trials; ++q) {
-      h[q] = make_post_args(solvers[q], solvers[q]->p.P, 0, 1, wd, &b->post_grid[wd]);
-      h[q].wt = write_through_policy(solvers[q], solvers[q]->nt * n_trials);
-    }
-    b->d_post[wd] = reinterpret_cast<PostArgs*>(carve(sizeof(PostArgs) * n_trials));
-    put(b->d_post[wd], h.data(), sizeof(PostArgs) * n_trials);
-  }
-  for (int ab = 0; ab < 2; ++ab) {
-    std::vector<PostArgs> h(n_trials);
-    for (int q = 0; q < n_trials; ++q) {
-      h[q] = make_post_args(solvers[q], ab == 0 ? solvers[q]->p.PA : solvers[q]->p.PB, 0, 0, 0, &b->postT_grid);
-      h[q].wt = write_through_policy(solvers[q], solvers[q]->nt * n_trials);
-    }
-    b->d_postT[ab] = reinterpret_cast<PostArgs*>(carve(sizeof(PostArgs) * n_trials));
-    put(b->d_postT[ab], h.data(), sizeof(PostArgs) * n_trials);
-  }
-  {
-    std::vector<PostArgs> hc(n_trials);
-    for (int q = 0; q < n_trials; ++q) hc[q] = make_post_args(solvers[q], solvers[q]->p.P, 1, 0, 0, &b->post_close_grid);
-    b->d_post_close = reinterpret_cast<PostArgs*>(carve(sizeof(PostArgs) * n_trials));
-    put(b->d_post_close, hc.data(), sizeof(PostArgs) * n_trials);
-    std::vector<PalinArgs> h(n_trials);
-    for (int q = 0; q < n_trials; ++q) h[q] = make_palin_args(solvers[q], 0);
-    b->d_palin = reinterpret_cast<PalinArgs*>(carve(sizeof(PalinArgs) * n_trials));
-    put(b->d_palin, h.data(), sizeof(PalinArgs) * n_trials);
-    std::vector<FinalArgs> f(n_trials);
-    for (int q = 0; q < n_trials; ++q) f[q] = make_final_args(solvers[q], 1, 0);
-    b->d_flush = reinterpret_cast<FinalArgs*>(carve(sizeof(FinalArgs) * n_trials));
-    put(b->d_flush, f.data(), sizeof(FinalArgs) * n_trials);
-  }
-  {
-    std::vector<PostArgs> hp(n_trials);
-    for (int q = 0; q < n_trials; ++q) {
-      hp[q] = make_post_args(solvers[q], solvers[q]->p.P, 0, 0, 0, &b->postP_grid);
-      hp[q].wt = write_through_policy(solvers[q], solvers[q]->nt * n_trials);
-    }
-    b->d_postP = reinterpret_cast<PostArgs*>(carve(sizeof(PostArgs) * n_trials));
-    put(b->d_postP, hp.data(), sizeof(PostArgs) * n_trials);
-    // the counter words first (their addresses go into the argument blocks), then the blocks themselves
-    char* xa0 = carve(sizeof(XArgs) * n_trials);
-    char* xa1 = carve(sizeof(XArgs) * n_trials);
-    b->d_xsync = reinterpret_cast<unsigned*>(carve(sizeof(uint32_t) * (XG_LEN + (size_t)XS_LEN * n_trials)));
-    for (int wd = 0; wd < 2; ++wd) {
-      std::vector<XArgs> hx(n_trials);
-      for (int q = 0; q < n_trials; ++q) hx[q] = make_xargs(solvers[q], wd, b->d_xsync + XG_LEN + (size_t)XS_LEN * q);
-      b->d_xargs[wd] = reinterpret_cast<XArgs*>(wd == 0 ? xa0 : xa1);
-      put(b->d_xargs[wd], hx.data(), sizeof(XArgs) * n_trials);
-    }
-    for (int wd = 0; wd < 2; ++wd) {
-      std::vector<CArgs> hc(n_trials);
-      for (int q = 0; q < n_trials; ++q) hc[q] = make_cargs(solvers[q], wd);
-      b->d_cargs[wd] = reinterpret_cast<CArgs*>(carve(sizeof(CArgs) * n_trials));
-      put(b->d_cargs[wd], hc.data(), sizeof(CArgs) * n_trials);
-    }
-    // the chip-wide kernel's blocks; every trial of a launch group must share the tiling and the layout (the kernel takes
-    // T from the group's first block), and the layout is the one of this moment (LDC_WIDE_LAYOUT) for the batch's life.
-    // Batches run the layout with index M-1 inside the tiles only: a batch in the tail layout (N=128, four trials per launch)
-    // once ended one trial's 300 iterations off the lone run's bits ("Batch form"); until that is explained a
-    // batch whose trials take the tail layout keeps today's rule.
-    b->wT = wide_tiles(s0); b->wtail = wide_tail(s0) ? 1 : 0;
-    bool wide_ok = b->wtail == 0;
-    for (int q = 0; q < n_trials; ++q)
-      wide_ok = wide_ok && wide_available(solvers[q]) && wide_tiles(solvers[q]) == b->wT && (wide_tail(solvers[q]) ? 1 : 0) == b->wtail;
-    b->wG = wide_ok ? wide_group_of(b->wT, s0->n_cus) : 0;
-    for (int wd = 0; wd < 2; ++wd) {
-      std::vector<WArgs> hw(n_trials);
-      for (int q = 0; q < n_trials; ++q) hw[q] = make_wargs(solvers[q], wd);
-      b->d_wargs[wd] = reinterpret_cast<WArgs*>(carve(sizeof(WArgs) * n_trials));
-      put(b->d_wargs[wd], hw.data(), sizeof(WArgs) * n_trials);
-    }
-  }
+  hipError_t he = hipSuccess;
+  auto put = [&](auto* dst, auto make) {      // make(trial, index) for every trial, copied to dst
+    std::vector<std::remove_pointer_t<decltype(dst)>> h(n_trials);
+    for (int q = 0; q < n_trials; ++q) h[q] = make(solvers[q], q);
+    if (he == hipSuccess) he = copy_now(dst, h.data(), sizeof(h[0]) * n_trials, hipMemcpyHostToDevice);
+  };
+  auto upload = [&](auto*& dst, auto make) { carve(dst, n_trials); put(dst, make); };
+  const int tiles = s0->nt * n_trials;
+  for (int k = 0; k < 4; ++k) upload(b->d_stage[k], [&](const ldc_solver* t, int) { return make_stage_args(t, k, tiles); });
+  for (int wd = 0; wd < 2; ++wd)
+    upload(b->d_post[wd], [&](const ldc_solver* t, int) { return make_post_args(t, t->p.P, 0, 1, wd, tiles, &b->post_grid[wd]); });
+  for (int ab = 0; ab < 2; ++ab)
+    upload(b->d_postT[ab], [&](const ldc_solver* t, int) {
+      return make_post_args(t, ab == 0 ? t->p.PA : t->p.PB, 0, 0, 0, tiles, &b->postT_grid);
+    });
+  // (the closing record's post launch keeps the lone trial's policy)
+  upload(b->d_post_close, [&](const ldc_solver* t, int) { return make_post_args(t, t->p.P, 1, 0, 0, t->nt, &b->post_close_grid); });
+  upload(b->d_palin, [](const ldc_solver* t, int) { return make_palin_args(t, 0); });
+  upload(b->d_flush, [](const ldc_solver* t, int) { return make_final_args(t, 1, 0); });
+  upload(b->d_postP, [&](const ldc_solver* t, int) { return make_post_args(t, t->p.P, 0, 0, 0, tiles, &b->postP_grid); });
+  // the counter words after the small-N kernel's blocks, whose addresses go into those blocks
+  carve(b->d_xargs[0], n_trials);
+  carve(b->d_xargs[1], n_trials);
+  carve(b->d_xsync, XG_LEN + (size_t)XS_LEN * n_trials);
+  for (int wd = 0; wd < 2; ++wd)
+    put(b->d_xargs[wd], [&](const ldc_solver* t, int q) { return make_xargs(t, wd, b->d_xsync + XG_LEN + (size_t)XS_LEN * q); });
+  for (int wd = 0; wd < 2; ++wd) upload(b->d_cargs[wd], [&](const ldc_solver* t, int) { return make_cargs(t, wd); });
+  // the chip-wide kernel's blocks; every trial of a launch group must share the tiling and the layout (the kernel takes
+  // T from the group's first block), and the layout is the one of this moment (LDC_WIDE_LAYOUT) for the batch's life.
+  // Batches run the layout with index M-1 inside the tiles only: a batch in the tail layout (N=128, four trials per launch)
+  // once ended one trial's 300 iterations off the lone run's bits ("Batch form"); until that is explained a
+  // batch whose trials take the tail layout keeps today's rule.
+  b->wT = wide_tiles(s0); b->wtail = wide_tail(s0) ? 1 : 0;
+  bool wide_ok = b->wtail == 0;
+  for (int q = 0; q < n_trials; ++q)
+    wide_ok = wide_ok && wide_available(solvers[q]) && wide_tiles(solvers[q]) == b->wT && (wide_tail(solvers[q]) ? 1 : 0) == b->wtail;
+  b->wG = wide_ok ? wide_group_of(b->wT, s0->n_cus) : 0;
+  for (int wd = 0; wd < 2; ++wd) upload(b->d_wargs[wd], [&](const ldc_solver* t, int) { return make_wargs(t, wd); });
   if (he != hipSuccess) { delete b; return (int)he; }
   *out = b;
   return 0;
@@ -2967,14 +2855,10 @@ int ldc_batch_create(ldc_solver* const* solvers, int n_trials, void* workspace, 
 
 int ldc_batch_destroy(ldc_batch* b) {
   if (!b) return LDC_E_STATE;
+  b->chunks.clear();
   {
     std::lock_guard<std::mutex> lock(g_setup_mutex);
     for (int q = 0; q < 2; ++q) if (b->graph[q]) (void)hipGraphExecDestroy(b->graph[q]);
-    for (int q = 0; q < 2; ++q)
-      for (WChunk& c : b->wchunk[q]) {
-        if (c.exec) { (void)hipEventSynchronize(c.done); (void)hipGraphExecDestroy(c.exec); }
-        if (c.done) (void)hipEventDestroy(c.done);
-      }
   }
   delete b;
   return 0;
@@ -3025,69 +2909,42 @@ int ldc_batch_enqueue(ldc_batch* b, int n_iters, int with_diag, void* stream) {
   { const int e = on_own_device(b->s[0]); if (e) return e; }
   with_diag = with_diag ? 1 : 0;
   hipStream_t st = as_stream(stream);
-  if (n_iters > 1 && batch_uses_cu(b)) {
-    // trial-per-CU kernel: one work-group per trial, the whole batch in one launch, then the transforms of the final
-    // pressures in the launch path's form
-    const ldc_solver* s0 = b->s[0];
+  const int mode = n_iters > 1 ? ldc_batch_mode(b) : 0;
+  const ldc_solver* s0 = b->s[0];
+  if (mode == 4) {
+    // trial-per-CU kernel: one work-group per trial, the whole batch in one launch
     CLaunch cl;
     memset(&cl, 0, sizeof(cl));
     cl.B = b->B; cl.n_iters = n_iters; cl.trials = b->d_cargs[with_diag];
-    { const int e = cu_launch_any(cl, s0, with_diag, st); if (e) return e; }
-    const PostArgs pdummy = {};
-    hipLaunchKernelGGL(post_kernel<true>, dim3(b->postP_grid, b->B), dim3(kThreads), 0, st, pdummy,
-                       (const PostArgs*)b->d_postP);
-    { const int e = (int)hipGetLastError(); if (e) return e; }
-    return with_diag ? batch_closing_diagnostics(b, st) : 0;
+    const int e = cu_launch(cl, s0, with_diag, st);
+    return e ? e : finish_chunk(b, with_diag, st);
   }
-  if (n_iters > 1 && batch_uses_wide(b)) {
+  if (mode == 5) {
     // chip-wide kernel, launch group after launch group, and the closing launches: one graph per chunk length
-    WChunk* c = nullptr;
-    { const int e = batch_wide_chunk(b, n_iters, with_diag, &c); if (e) return e; }
-    HIP_TRY(hipGraphLaunch(c->exec, st));
-    HIP_TRY(hipEventRecord(c->done, st));
-    c->used = ++b->wclock;
-    return 0;
+    return b->chunks.launch(n_iters, with_diag, st, [&](hipStream_t cs) { return enqueue_wide_batch_chunk(b, n_iters, with_diag, cs); });
   }
-  {
+  if (mode == 3) {
     // small-N trial kernel: every trial of the batch on an XCD of its own (as many trials per launch as the XCDs hold,
-    // the rest in further launches), then the transforms of the final pressures in the launch path's form
-    bool all_xcd = n_iters > 1;
-    for (const ldc_solver* t : b->s) all_xcd = all_xcd && use_xcd(t);
-    if (all_xcd) {
-      const ldc_solver* s0 = b->s[0];
-      const int T = xcd_tiles(s0), nwg = T * T;
-      const int slots = (s0->n_cus / s0->n_xcds) / nwg, per_launch = slots * s0->n_xcds;
-      HIP_TRY(hipMemsetAsync(b->d_xsync + XG_LEN, 0, sizeof(uint32_t) * (size_t)XS_LEN * b->B, st));
-      for (int lo = 0; lo < b->B; lo += per_launch) {
-        XLaunch xl;
-        memset(&xl, 0, sizeof(xl));
-        xl.B = (b->B - lo < per_launch) ? (b->B - lo) : per_launch;
-        // slots in use on every XCD in THIS launch: exactly what the trials need, so that the over-subscription (8 more
-        // work-groups per XCD than needed) can never open a slot that would not fill up
-        xl.n_iters = n_iters; xl.slots_per_xcd = (xl.B + s0->n_xcds - 1) / s0->n_xcds;
-        xl.gsync = b->d_xsync;
-        xl.trials = b->d_xargs[with_diag] + lo;
-        HIP_TRY(hipMemsetAsync(b->d_xsync, 0, sizeof(uint32_t) * XG_LEN, st));
-        const int e = xcd_launch_any(xl, s0->p.stage_pressure != 0, with_diag != 0, T, s0->n_xcds, st);
-        if (e) return e;
-      }
-      const PostArgs pdummy = {};
-      hipLaunchKernelGGL(post_kernel<true>, dim3(b->postP_grid, b->B), dim3(kThreads), 0, st, pdummy,
-                         (const PostArgs*)b->d_postP);
-      { const int e = (int)hipGetLastError(); if (e) return e; }
-      return with_diag ? batch_closing_diagnostics(b, st) : 0;
+    // the rest in further launches)
+    const int T = xcd_tiles(s0), nwg = T * T;
+    const int slots = (s0->n_cus / s0->n_xcds) / nwg, per_launch = slots * s0->n_xcds;
+    HIP_TRY(hipMemsetAsync(b->d_xsync + XG_LEN, 0, sizeof(uint32_t) * (size_t)XS_LEN * b->B, st));
+    for (int lo = 0; lo < b->B; lo += per_launch) {
+      XLaunch xl;
+      memset(&xl, 0, sizeof(xl));
+      xl.B = (b->B - lo < per_launch) ? (b->B - lo) : per_launch;
+      // slots in use on every XCD in THIS launch: exactly what the trials need, so that the over-subscription (8 more
+      // work-groups per XCD than needed) can never open a slot that would not fill up
+      xl.n_iters = n_iters; xl.slots_per_xcd = (xl.B + s0->n_xcds - 1) / s0->n_xcds;
+      xl.gsync = b->d_xsync;
+      xl.trials = b->d_xargs[with_diag] + lo;
+      HIP_TRY(hipMemsetAsync(b->d_xsync, 0, sizeof(uint32_t) * XG_LEN, st));
+      const int e = xcd_launch(xl, s0->p.stage_pressure != 0, with_diag != 0, T, s0->n_xcds, st);
+      if (e) return e;
     }
+    return finish_chunk(b, with_diag, st);
   }
-  int left = n_iters;
-  if (left >= b->iters_per_graph) {
-    if (!b->graph[with_diag]) { int e = batch_build_graph(b, with_diag); if (e) return e; }
-    while (left >= b->iters_per_graph) {
-      HIP_TRY(hipGraphLaunch(b->graph[with_diag], st));
-      left -= b->iters_per_graph;
-    }
-  }
-  for (; left > 0; --left) { int e = batch_launch_iteration(b, with_diag, st); if (e) return e; }
-  return (with_diag && n_iters > 0) ? batch_closing_diagnostics(b, st) : 0;
+  return enqueue_launch_path(b, n_iters, with_diag, st);
 }
 
 int ldc_wide_trials_per_launch(int nx, int ny, int stage_pressure, int n_cus) {
@@ -3120,9 +2977,9 @@ int ldc_residual_debug(ldc_solver* s, int which, double* const out[11], void* st
   hipStream_t st = as_stream(stream);
   int e = launch_post(s, s->p.P, 0, 0, 0, st);   // SG differentiates p^n whatever the stage (Q1)
   if (e) return e;
-  StageArgs a = make_stage_args(s, which == 0 ? 0 : which == 1 ? 1 : 2);
+  StageArgs a = make_stage_args(s, which == 0 ? 0 : which == 1 ? 1 : 2, s->nt);
   for (int q = 0; q < 11; ++q) a.dump[q] = out[q];
-  return launch_stage_kernel<true, false, true, false, 0>(a, nullptr, s->nt, 1, st, s->p.Mx != s->p.My);
+  return launch_stage_kernel(stage_variant(which, false, false, true, s->p.Mx != s->p.My, false), a, nullptr, s->nt, 1, st);
 }
 
 int ldc_gemm_nt(const double* A, const double* B, double* C, int R16, int K16, int LD, int transpose_out,

@@ -76,14 +76,16 @@ struct ldc_fv_problem {
 typedef struct ldc_fv ldc_fv;
 
 int ldc_fv_version(void);
-/* Validate (no device needed), then write the trial's descriptor into the tail of `work` (synchronous copy). */
+/* Validate (no device needed), then write the trial's descriptor into the tail of `work` (synchronous copy on the */
+/* library's own stream: work the caller has queued on `work` must have completed).                                 */
 int ldc_fv_create(const struct ldc_fv_problem *prob, ldc_fv **out);
 int ldc_fv_destroy(ldc_fv *h);
 /* Up to n_iters SIMPLE iterations (<= rec_cap) in one launch; stops early at the latch or a NaN. */
 int ldc_fv_enqueue(ldc_fv *h, int n_iters, void *stream);
 /* The same for n trials (any sizes and parameters, one device): one work-group each. */
 int ldc_fv_batch_enqueue(ldc_fv *const *hs, int n, int n_iters, void *stream);
-/* 0, or LDC_FV_E_NAN when the trial stopped on a NaN (reads ctrl; synchronises the device). */
+/* 0, or LDC_FV_E_NAN when the trial stopped on a NaN (reads ctrl through the library's own stream: wait for the */
+/* stream of the trial's launches first). */
 int ldc_fv_status(ldc_fv *h);
 /* One iteration, copying the intermediates selected by `which` into out[k] (device pointers). */
 int ldc_fv_step_debug(ldc_fv *h, int which, double *const *out, void *stream);

@@ -270,10 +270,11 @@ int ldc_batch_enqueue(ldc_batch *b, int n_iters, int with_diagnostics, void *str
 /* how ldc_batch_enqueue will advance more than one iteration: 0 shared launches per stage (blockIdx.y = trial), 3 the        */
 /* small-N kernel (every trial on an XCD of its own), 4 the trial-per-CU kernel (one work-group per trial), 5 the chip-wide   */
 /* kernel (a launch carries ldc_wide_trials_per_launch trials, T x T work-groups each, one per CU; further launches cover the  */
-/* rest of the batch).  Mode 5 captures each chunk length as a graph and keeps up to three lengths per diagnostics form; a    */
-/* graph is destroyed (evicted, or at ldc_batch_destroy) only after the event recorded behind its latest launch on the       */
-/* caller's stream has completed, so the caller need not wait between enqueues.  A mode-5 chunk needs its work-groups        */
-/* co-resident: a host that drives several streams keeps it from overlapping other launches of modes 3, 4 and 5.            */
+/* rest of the batch).  Mode 5 -- here and in ldc_solver_enqueue -- captures each chunk length as a graph and keeps up to    */
+/* three lengths per diagnostics form; a graph is destroyed (evicted, at ldc_solver_set_persistent, ldc_solver_destroy or    */
+/* ldc_batch_destroy) only after the event recorded behind its latest launch on the caller's stream has completed, so the    */
+/* caller need not wait between enqueues.  A mode-5 chunk needs its work-groups co-resident: a host that drives several    */
+/* streams keeps it from overlapping other launches of modes 3, 4 and 5.                                                    */
 int ldc_batch_mode(ldc_batch *b);
 /* trials per launch of the chip-wide kernel's batch form for an nx x ny grid built as the Python solver builds it      */
 /* (M = max(nx, ny) + 1) with or without stage pressures (the FSG smoother), on a device of n_cus CUs: floor(n_cus / T^2) */
