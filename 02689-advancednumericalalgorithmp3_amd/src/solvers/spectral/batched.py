@@ -18,21 +18,17 @@ which pins 3: one XCD per trial where the size fits, the launch path above).
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 import logging
 import time
 
 import numpy as np
 
-from . import ldc_lib as L
+from . import chunks, ldc_lib as L
 from .sg import SGSolver
 from ..base import WARMUP_ITERATIONS
 
 log = logging.getLogger(__name__)
-
-LATCH_CAPPED = 3      # ctrl[DONE] code set by the host when a trial of a batch reaches its own max_iterations
-
 
 class BatchedSGSolver:
     """``trials``: list of SGSolver keyword dicts with identical nx/ny (and device)."""
@@ -107,13 +103,9 @@ class BatchedSGSolver:
             s.close()
 
     def run_to_tolerance(self, tolerances, max_iter, diagnostics: bool = False) -> list:
-        """Every solver from its present state until ITS latch fires or ITS cap is reached (``max_iter``: one
-        int for all, or one per solver); returns per-solver (latch, iterations, records).  A trial that hits its
-        cap is latched on the device with code 3 (LATCH_CAPPED): its work-groups leave every later launch at
-        entry, exactly like a converged trial's, and its history stops there -- the same outcome as the
-        reference's one-process-per-trial runs with different ``max_iterations``.  Used by ``solve`` and by the
-        batched FSG levels."""
-        import torch
+        """Every solver from iteration 0 until ITS latch fires or ITS cap is reached (``max_iter``: one int for all, or
+        one per solver); returns per-solver (latch, iterations, records) -- chunks.run_to_tolerance, which latches a
+        capped trial on the device.  Used by ``solve`` and by the batched FSG levels."""
         n = len(self.solvers)
         caps = [int(max_iter)] * n if np.isscalar(max_iter) else [int(c) for c in max_iter]
         if len(caps) != n:
@@ -122,28 +114,7 @@ class BatchedSGSolver:
         for s in self.solvers:
             s.d["ctrl"].zero_()
             s._prime()
-        cap = min(s.rec_cap for s in self.solvers)
-        chunk = max(1, min(min(int(s.params.check_every) for s in self.solvers), cap))
-        blocks = [[] for _ in self.solvers]
-        state = [(0, 0)] * n
-        it = 0
-        while True:
-            live = [q for q in range(n) if not state[q][0]]
-            for q in live:
-                if it >= caps[q]:                                   # cap reached: latch it on the device
-                    self.solvers[q].d["ctrl"][L.CTRL_DONE] = LATCH_CAPPED
-                    state[q] = (LATCH_CAPPED, state[q][1])
-            live = [q for q in live if not state[q][0]]
-            if not live:
-                break
-            k = 1 if any(s._edge_fix_pending for s in self.solvers) else min(chunk, min(caps[q] for q in live) - it)
-            for q, (rows, done, total) in enumerate(self._advance(k, diagnostics)):
-                if state[q][0] != LATCH_CAPPED:
-                    blocks[q].append(rows)
-                    state[q] = (done, total)
-            it += k
-        self.solvers[0]._sync()
-        return [(d, t, np.concatenate(b, axis=0) if b else np.zeros((0, 8))) for (d, t), b in zip(state, blocks)]
+        return chunks.run_to_tolerance(self.solvers, lambda k: self._advance(k, diagnostics), caps, batch=True)
 
     def __del__(self):
         try:
@@ -153,51 +124,23 @@ class BatchedSGSolver:
 
     # ------------------------------------------------------------------------------------------------
     def _advance(self, n_iters: int, diagnostics: bool):
-        """Enqueue n_iters iterations for every trial; returns per-trial (rows, latch, total)."""
+        """Enqueue n_iters iterations for every trial; returns per-trial (rows, latch, total) (chunks.advance)."""
+        return chunks.advance(self.solvers, n_iters, diagnostics, self._enqueue, self.kernel_mode,
+                              self.solvers[0].device.index or 0)
+
+    def _enqueue(self, n_iters: int, diagnostics: bool):
         import torch
         dev = self.solvers[0].device
-        # (one device-side gather and ONE copy per kind of word for the whole batch: a blocking copy per trial and kind --
-        #  four of them -- was 12 ms of host time per chunk at 256 trials, as much as the chunk itself at N = 16)
-        def words(key):
-            return torch.stack([s.d[key] for s in self.solvers]).cpu().numpy()
-        starts = [int(x) for x in words("ctrl")[:, L.CTRL_ITER]]
-        resident = int(n_iters) > 1 and self.kernel_mode in (3, 4, 5)
-        lock = L.resident_lock(dev.index or 0) if resident else contextlib.nullcontext()
-        with lock, torch.cuda.device(dev):        # (see ldc_lib.resident_lock: co-resident launches one at a time per device)
+        with torch.cuda.device(dev):
             L.check(L.lib().ldc_batch_enqueue(self._batch, int(n_iters), int(bool(diagnostics)), L.stream_ptr(dev)),
                     "ldc_batch_enqueue")
-            self.solvers[0]._sync()
-        out = []
-        ctrl_all = words("ctrl")
-        gave_up = torch.stack([s.d["sync"][L.SYNC_GIVEUP] for s in self.solvers]).cpu().numpy()
-        same_cap = len({s.rec_cap for s in self.solvers}) == 1
-        rings = words("rec") if same_cap else None
-        for q, (s, start) in enumerate(zip(self.solvers, starts)):
-            end, done = int(ctrl_all[q, L.CTRL_ITER]), int(ctrl_all[q, L.CTRL_DONE])
-            ring = rings[q] if same_cap else s.d["rec"].cpu().numpy()
-            out.append((ring[np.arange(start, end) % s.rec_cap], done, end))
-            if int(gave_up[q]) != 0:
-                raise L.LdcError("a persistent launch gave up a barrier wait (a work-group was not resident); the "
-                                 "state of the batch is undefined -- rerun with persistent=0")
-            if s._edge_fix_pending and end > start:
-                s._write_boundary_edges(("U", "UT", "V", "VT"))
-                s._edge_fix_pending = False
-        return out
 
     def run_iterations(self, n: int, diagnostics: bool = True, tolerance: float = 0.0) -> list:
         """n more iterations for every trial (tolerance 0: no convergence stop); per-trial record arrays."""
         self._ensure_batch([tolerance] * len(self.solvers))
         for s in self.solvers:
             s._prime()
-        rows = [[] for _ in self.solvers]
-        left = int(n)
-        cap = min(s.rec_cap for s in self.solvers)
-        while left > 0:
-            k = 1 if any(s._edge_fix_pending for s in self.solvers) else min(left, cap)
-            for q, (r, _, _) in enumerate(self._advance(k, diagnostics)):
-                rows[q].append(r)
-            left -= k
-        return [np.concatenate(r, axis=0) for r in rows]
+        return chunks.run_iterations(self.solvers, lambda k: self._advance(k, diagnostics), n, batch=True)
 
     def solve(self, max_iter: int = None):
         """Every trial to its own tolerance or its own ``max_iterations``; fills each solver's metrics/fields.
@@ -282,45 +225,11 @@ class BatchedFSGSolver:
         return outs[0] + outs[1]
 
     def solve(self, max_iter: int = None):
-        t0 = time.perf_counter()
+        from .fsg import run_ladder
         fines = self.solvers
-        for s in fines:
-            s._smoother_mode()
-        ladders = [[s._make_level(n) for n in self.orders[:-1]] + [s] for s in fines]
-        nlev = len(self.orders)
-        alive = list(range(len(fines)))
-        total = [0] * len(fines)
-        last = [0] * len(fines)                       # latch of the last level each trial ran
-        for idx in range(nlev):
-            if not alive:          # every trial diverged on a coarser level (NaN latch): nothing goes up, as in FSGSolver.solve
-                break
-            group = [ladders[q][idx] for q in alive]
-            for q, lvl in zip(alive, group):
-                if idx == 0:
-                    lvl.reset_state()
-                else:
-                    fines[q]._prolongate(ladders[q][idx - 1], lvl)
-            tols = [fines[q].params.tolerance * fines[q].params.coarse_tolerance_factor ** (nlev - 1 - idx)
-                    for q in alive]
-            caps = [fines[q].params.max_iterations if max_iter is None else max_iter for q in alive]
-            out = self._run_level(group, tols, caps)
-            nxt = []
-            for q, (done, its, _) in zip(alive, out):
-                total[q] += its
-                last[q] = done
-                if done != 2:
-                    nxt.append(q)
-            log.info("batched FSG level %d (N=%d): %d trials, iterations %s", idx, self.orders[idx], len(alive),
-                     [o[1] for o in out])
-            alive = nxt
-        wall = time.perf_counter() - t0
-        self.batch_seconds, self.batch_size = wall, len(fines)
-        its_all = max(1, sum(total))
-        for q, s in enumerate(fines):
-            for lvl in ladders[q][:-1]:
-                lvl.close()
-            # wall-time share by iteration count, see BatchedSGSolver.solve
-            s._finish(s.params.tolerance, total[q], last[q] == 1 and q in alive, wall * total[q] / its_all)
+        caps = [s.params.max_iterations if max_iter is None else max_iter for s in fines]
+        self.batch_seconds = run_ladder(fines, self._run_level, [s.params.tolerance for s in fines], caps)
+        self.batch_size = len(fines)
         return [s.metrics for s in fines]
 
 

@@ -16,7 +16,7 @@ import time
 
 import numpy as np
 
-from . import ldc_lib as L
+from .chunks import run_to_tolerance
 from .operators.transfer_operators import prolongation_matrix
 from .sg import SGSolver
 from ..base import EN, PN, REL, RP, RU, RV, ZN
@@ -45,13 +45,10 @@ class FSGSolver(SGSolver):
             # every level; with nx != ny it has no defined behaviour to reproduce
             raise NotImplementedError("FSG needs nx == ny (the level hierarchy is built from one polynomial order)")
 
-    def _smoother_mode(self):
-        self._stage_pressure, self._warmup, self._nan_exit = 1, 0, True
-
     def _make_level(self, n: int) -> SGSolver:
         kw = dataclasses.asdict(dataclasses.replace(self.params, nx=n, ny=n))
         lvl = SGSolver(**kw)
-        lvl._stage_pressure, lvl._warmup, lvl._nan_exit = 1, 0, True
+        lvl._smoother_mode()
         return lvl
 
     # ------------------------------------------------------------------ prolongation (device)
@@ -111,38 +108,56 @@ class FSGSolver(SGSolver):
     def solve(self, tolerance: float = None, max_iter: int = None):
         tolerance = self.params.tolerance if tolerance is None else tolerance
         max_iter = self.params.max_iterations if max_iter is None else max_iter
-        p = self.params
-        t0 = time.perf_counter()
-        orders = hierarchy_orders(p.nx, p.n_levels)
-        log.info("Building %d-level hierarchy: N = %s", len(orders), orders)
-        self._smoother_mode()
-        levels = [self._make_level(n) for n in orders[:-1]] + [self]
-        chunk = max(1, int(p.check_every))
-        total, converged, diverged = 0, False, False
-        for idx, lvl in enumerate(levels):
-            tol = tolerance * p.coarse_tolerance_factor ** (len(levels) - 1 - idx)
+        wall = run_ladder([self], self._run_level, [tolerance], [max_iter])
+        log.info("FSG completed in %.2fs: %d iterations, converged=%s", wall, self.metrics.iterations,
+                 self.metrics.converged)
+
+    @staticmethod
+    def _run_level(group, tols, caps):
+        """One level of a lone FSG solve, through the level's own handle."""
+        (lvl,), (tol,) = group, tols
+        lvl._begin(tol)
+        return run_to_tolerance(group, lambda k: [lvl._advance(k, diagnostics=False)], caps, batch=False)
+
+
+def run_ladder(fines, run_level, tolerances, caps) -> float:
+    """FSG solves of ``fines`` (FSGSolvers of one hierarchy, fine tolerance and iteration cap per level each), level by level
+    (reference multigrid/fsg.py:1053-1221): every level runs in smoother mode to its own coarse tolerance, the coarsest from
+    rest, every other from the prolongation of the level below; a trial that diverges on a level (NaN latch) stops there,
+    the others go on.  ``run_level(group, tols, caps)`` advances the levels of the trials still alive and returns per-trial
+    (latch, iterations, records).  Fills each trial's one-point history (_finish); returns the wall time."""
+    t0 = time.perf_counter()
+    p0 = fines[0].params
+    orders = hierarchy_orders(p0.nx, p0.n_levels)
+    log.info("Building %d-level hierarchy: N = %s", len(orders), orders)
+    for s in fines:
+        s._smoother_mode()
+    ladders = [[s._make_level(n) for n in orders[:-1]] + [s] for s in fines]
+    nlev = len(orders)
+    alive = list(range(len(fines)))
+    total = [0] * len(fines)
+    last = [0] * len(fines)                       # latch of the last level each trial ran
+    for idx in range(nlev):
+        if not alive:          # every trial diverged on a coarser level: nothing goes up
+            break
+        group = [ladders[q][idx] for q in alive]
+        for q, lvl in zip(alive, group):
             if idx == 0:
                 lvl.reset_state()
             else:
-                self._prolongate(levels[idx - 1], lvl)
-            keep = lvl.params.diagnostics
-            lvl.params.diagnostics = False
-            try:
-                lvl._begin(float(tol))
-                done, it = 0, 0
-                while it < max_iter and not done:
-                    _, done, it = lvl._advance(min(chunk, max_iter - it))
-            finally:
-                lvl.params.diagnostics = keep
-            total += it
-            converged = done == 1
-            log.info("FSG level %d (N=%d): %d iterations, converged=%s", idx, lvl.params.nx, it, converged)
-            if done == 2:
-                diverged = True
-                break
-        for lvl in levels[:-1]:
+                fines[q]._prolongate(ladders[q][idx - 1], lvl)
+        tols = [tolerances[q] * fines[q].params.coarse_tolerance_factor ** (nlev - 1 - idx) for q in alive]
+        out = run_level(group, tols, [caps[q] for q in alive])
+        for q, (done, its, _) in zip(alive, out):
+            total[q] += its
+            last[q] = done
+        log.info("FSG level %d (N=%d): %d trials, iterations %s", idx, orders[idx], len(alive), [o[1] for o in out])
+        alive = [q for q, (done, _, _) in zip(alive, out) if done != 2]
+    wall = time.perf_counter() - t0
+    its_all = max(1, sum(total))
+    for q, s in enumerate(fines):
+        for lvl in ladders[q][:-1]:
             lvl.close()
-        wall = time.perf_counter() - t0
-        converged = bool(converged and not diverged)
-        self._finish(tolerance, total, converged, wall)
-        log.info("FSG completed in %.2fs: %d iterations, converged=%s", wall, total, converged)
+        # a trial's wall time is its share by iteration count (BatchedSGSolver.solve)
+        s._finish(tolerances[q], total[q], last[q] == 1, wall * total[q] / its_all)
+    return wall

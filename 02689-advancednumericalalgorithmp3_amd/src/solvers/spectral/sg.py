@@ -17,7 +17,7 @@ import numpy as np
 
 from ..base import LidDrivenCavitySolver
 from ..datastructures import SpectralParameters
-from . import ldc_lib as L
+from . import chunks, ldc_lib as L
 from .basis.spectral import ChebyshevLobattoBasis, LegendreLobattoBasis, inner_to_full_interpolation
 from .operators.corner import create_corner_treatment
 
@@ -129,10 +129,7 @@ class SGSolver(LidDrivenCavitySolver):
         self._handle = None
         self._handle_tol = None
         self._eig = None
-        # loop flavour: SG (reference sg.py/base.py) unless a subclass switches to the FSG smoother
-        self._stage_pressure = 0          # 1: every RK stage differentiates its own stage pressure
-        self._warmup = 10                 # iterations without convergence test (base.py:264, 283)
-        self._nan_exit = None             # None: follow params.nan_guard
+        self._smoother_mode(False)
         self._edge_fix_pending = False
         self.reset_state()
 
@@ -233,7 +230,6 @@ class SGSolver(LidDrivenCavitySolver):
 
     # ------------------------------------------------------------------ state transfer
     def _download_full(self, name: str) -> np.ndarray:
-        import torch
         self._sync()
         return self.d[name][: self.Mx, : self.My].cpu().numpy()
 
@@ -304,6 +300,12 @@ class SGSolver(LidDrivenCavitySolver):
         self.d["scal"].zero_()
 
     # ------------------------------------------------------------------ C-ABI plumbing
+    def _smoother_mode(self, on: bool = True):
+        """Loop flavour: SG (reference sg.py/base.py: p^n in every RK stage, 10 warm-up iterations without convergence test
+        (base.py:264, 283), NaN exit per params.nan_guard) or the FSG smoother (fsg.py: every stage differentiates its own
+        stage pressure, no warm-up, NaN/Inf exit).  Takes effect at the next handle (_ensure_handle)."""
+        self._stage_pressure, self._warmup, self._nan_exit = (1, 0, True) if on else (0, 10, None)
+
     def _problem(self, tol: float) -> L.Problem:
         p = self.params
         pr = L.Problem()
@@ -388,64 +390,26 @@ class SGSolver(LidDrivenCavitySolver):
             self.d["ctrl"].zero_()
         self._prime()
 
-    def _advance(self, n_iters: int):
-        import torch
-        ctrl0 = self.d["ctrl"].cpu().numpy()
-        start = int(ctrl0[L.CTRL_ITER])
-        n_iters = min(int(n_iters), self.rec_cap)
-        if self._edge_fix_pending and n_iters > 1:
-            # first iteration after an upload: afterwards phi^n carries its boundary values
-            rows1, done1, end1 = self._advance(1)
-            if done1 or n_iters == 1:
-                return rows1, done1, end1
-            rows2, done2, end2 = self._advance(n_iters - 1)
-            return np.concatenate([rows1, rows2], axis=0), done2, end2
-        if n_iters > 1 and L.lib().ldc_solver_mode(self._handle) != 0:
-            # a launch whose work-groups must be co-resident: one at a time per device (ldc_lib.resident_lock)
-            with L.resident_lock(self.device.index or 0):
-                self._abi("ldc_solver_enqueue", self._handle, n_iters, int(bool(self.params.diagnostics)))
-                self._sync()
-        else:
-            self._abi("ldc_solver_enqueue", self._handle, n_iters, int(bool(self.params.diagnostics)))
-            self._sync()
-        ctrl = self.d["ctrl"].cpu().numpy()
-        end, done = int(ctrl[L.CTRL_ITER]), int(ctrl[L.CTRL_DONE])
-        if int(self.d["sync"][L.SYNC_GIVEUP]) != 0:
-            raise L.LdcError("persistent trial kernel gave up a barrier wait (a work-group was not resident); "
-                             "the state is undefined -- rerun with persistent=0")
-        ring = self.d["rec"].cpu().numpy()
-        rows = ring[np.arange(start, end) % self.rec_cap]
-        if self._edge_fix_pending and end > start:
-            self._write_boundary_edges(("U", "UT", "V", "VT"))
-            self._edge_fix_pending = False
-        return rows, done, end
+    def _advance(self, n_iters: int, diagnostics: bool = None):
+        """One chunk through this solver's own handle (chunks.advance); ``diagnostics`` defaults to params.diagnostics."""
+        diag = self.params.diagnostics if diagnostics is None else diagnostics
+        return chunks.advance([self], n_iters, diag, self._enqueue, L.lib().ldc_solver_mode(self._handle),
+                              self.device.index or 0)[0]
+
+    def _enqueue(self, n_iters: int, diagnostics: bool):
+        self._abi("ldc_solver_enqueue", self._handle, n_iters, int(bool(diagnostics)))
 
     def step(self):
         """One pseudo-time step (4 RK stages + BCs) and the reductions that give the next dt."""
         self._begin(self.params.tolerance if self._handle_tol is None else self._handle_tol, restart=False)
-        self._advance_raw(1, diagnostics=False)
+        self._advance(1, diagnostics=False)
         return self.arrays.u, self.arrays.v, self.arrays.p
-
-    def _advance_raw(self, n, diagnostics):
-        keep = self.params.diagnostics
-        self.params.diagnostics = diagnostics
-        try:
-            return self._advance(n)
-        finally:
-            self.params.diagnostics = keep
 
     def run_iterations(self, n: int, diagnostics: bool = True, tolerance: float = 0.0,
                        restart: bool = False) -> np.ndarray:
         """Run n more iterations (tolerance 0 = no convergence stop); returns their records."""
         self._begin(tolerance, restart=restart)
-        out, left = [], int(n)
-        while left > 0:
-            rows, done, _ = self._advance_raw(min(left, self.rec_cap), diagnostics)
-            out.append(rows)
-            left -= len(rows)
-            if done or len(rows) == 0:
-                break
-        return np.concatenate(out, axis=0) if out else np.zeros((0, 8))
+        return chunks.run_iterations([self], lambda k: [self._advance(k, diagnostics)], n, batch=False)[0]
 
     # ------------------------------------------------------------------ results
     def _finalize_fields(self):
@@ -469,7 +433,6 @@ class SGSolver(LidDrivenCavitySolver):
 
     def residual_fields(self, which: int = 0) -> dict:
         """All intermediates of one residual evaluation (parity tests; reference sg.py:278-346)."""
-        import torch
         self._ensure_handle(self.params.tolerance if self._handle_tol is None else self._handle_tol)
         outs = [self.d[f"S{k}"] for k in range(11)]
         for t in outs:
@@ -485,7 +448,6 @@ class SGSolver(LidDrivenCavitySolver):
 
     def global_quantities(self) -> dict:
         """E, Z, P of the current state, computed on the device (reference sg.py:495-550)."""
-        import torch
         self._ensure_handle(self.params.tolerance if self._handle_tol is None else self._handle_tol)
         out = self.d["ext_val"]
         self._abi("ldc_global_quantities", self._handle, out.data_ptr())
@@ -495,7 +457,6 @@ class SGSolver(LidDrivenCavitySolver):
 
     # ---- vorticity / stream function / vortices (reference sg.py:510-743) --------------------
     def _compute_vorticity(self) -> np.ndarray:
-        import torch
         self._ensure_handle(self.params.tolerance if self._handle_tol is None else self._handle_tol)
         self._abi("ldc_diagnostics", self._handle)
         self._sync()
@@ -521,7 +482,6 @@ class SGSolver(LidDrivenCavitySolver):
 
     def _compute_streamfunction(self):
         """psi from lap(psi) = -omega, psi = 0 on the walls, by fast diagonalisation on the GPU."""
-        import torch
         Q = self._eigenbasis()
         self._compute_vorticity()
         Mx, My, Mi = self.Mx, self.My, self.M - 2          # (Mi: the larger inner block; the eigenbases are zero padded)
@@ -539,7 +499,6 @@ class SGSolver(LidDrivenCavitySolver):
         return full[:Mx, :My].cpu().numpy(), self.x_full, self.y_full
 
     def compute_vortex_metrics(self) -> dict:
-        import torch
         self._compute_streamfunction()          # leaves psi in S4 and omega in W
         self._abi("ldc_vortex_extrema_xy",
                   self.d["S4"].data_ptr(), self.d["W"].data_ptr(), self.d["x"].data_ptr(), self.d["y"].data_ptr(),

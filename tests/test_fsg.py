@@ -145,7 +145,7 @@ def test_gpu_smoother_matches_oracle_stage_pressure(N, K):
     from solvers.spectral.sg import SGSolver
     Re = 1000.0                          # SG diverges at N=32 with CFL 1.5 (quirk Q1); the smoother does not
     s = SGSolver(name="spectral", Re=Re, nx=N, ny=N, basis_type="chebyshev", CFL=1.5, check_every=256, graph_iters=8)
-    s._stage_pressure, s._warmup, s._nan_exit = 1, 0, True
+    s._smoother_mode()
     rec = s.run_iterations(K, diagnostics=False)
     o = orc.OracleSG(N, Re, stage_pressure=True)
     ref = oracle_records(o, K)

@@ -100,7 +100,7 @@ def test_cu_smoother_mode_vs_oracle(N, K):
     from test_fsg import oracle_records
     Re = 1000.0
     s = make(N, Re, check_every=256)
-    s._stage_pressure, s._warmup, s._nan_exit = 1, 0, True
+    s._smoother_mode()
     rec = s.run_iterations(K, diagnostics=False)
     assert mode_of(s) == 4
     o = orc.OracleSG(N, Re, stage_pressure=True)

@@ -91,7 +91,7 @@ def test_wide_sizes_it_does_not_cover_fall_back():
     assert mode_of(s) == 0
     s.close()
     s = make(256, 100.0)                     # smoother mode at N=256: no tail layout, 17 x 17 tiles do not fit
-    s._stage_pressure, s._warmup, s._nan_exit = 1, 0, True
+    s._smoother_mode()
     assert mode_of(s) == 0
     s.close()
 
@@ -102,7 +102,7 @@ def test_wide_smoother_mode_vs_oracle(N, K):
     from test_fsg import oracle_records
     Re = 1000.0
     s = make(N, Re, check_every=256)
-    s._stage_pressure, s._warmup, s._nan_exit = 1, 0, True
+    s._smoother_mode()
     assert mode_of(s) == 5
     rec = s.run_iterations(K, diagnostics=False)
     o = orc.OracleSG(N, Re, stage_pressure=True)

@@ -26,7 +26,7 @@ def rate(N, B, mode, K):
     b = BatchedSGSolver(trials)
     if kind == "smoother":
         for s in b.solvers:
-            s._stage_pressure, s._warmup, s._nan_exit = 1, 0, True
+            s._smoother_mode()
     b.run_iterations(64, diagnostics=diag)
     best = 0.0
     for _ in range(3):

@@ -37,7 +37,7 @@ for N in sizes:
         for mode in MODES:
             s = SGSolver(**kw(N, mode))
             if smoother:
-                s._stage_pressure, s._warmup, s._nan_exit = 1, 0, True
+                s._smoother_mode()
             s.run_iterations(256, diagnostics=diag)
             got = L.lib().ldc_solver_mode(s._handle)
             dt = timed(lambda: s.run_iterations(K, diagnostics=diag))

@@ -36,7 +36,7 @@ for N in sizes:
         for mode in (0, 3):
             s = SGSolver(**kw(N, mode, smoother=smoother))
             if smoother:
-                s._stage_pressure, s._warmup, s._nan_exit = 1, 0, True
+                s._smoother_mode()
             s.run_iterations(256, diagnostics=diag)
             dt = timed(lambda: s.run_iterations(K, diagnostics=diag))
             row.append(dt / K * 1e6)
@@ -48,7 +48,7 @@ for N in sizes:
             trials = [kw(N, mode, smoother=True, corner_smoothing=0.02 + 0.01 * q) for q in range(B)]
             b = BatchedSGSolver(trials)
             for s in b.solvers:
-                s._stage_pressure, s._warmup, s._nan_exit = 1, 0, True
+                s._smoother_mode()
             b.run_iterations(128, diagnostics=False)
             dt = timed(lambda: b.run_iterations(K, diagnostics=False), reps=2)
             row.append(B * K / dt)

@@ -23,7 +23,7 @@ trials = [dict(name="spectral", Re=1000.0 if kind == "smoother" else 400.0, nx=N
 b = BatchedSGSolver(trials)
 if kind == "smoother":
     for s in b.solvers:
-        s._stage_pressure, s._warmup, s._nan_exit = 1, 0, True
+        s._smoother_mode()
 diag = kind == "diag"
 b.run_iterations(256, diagnostics=diag)
 if any(int(L.lib().ldc_solver_mode(s._handle)) != 4 for s in b.solvers):

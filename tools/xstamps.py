@@ -21,7 +21,7 @@ kind = sys.argv[2] if len(sys.argv) > 2 else "sg"
 s = SGSolver(name="spectral", Re=1000.0 if kind == "smoother" else 400.0, nx=N, ny=N, basis_type="chebyshev", CFL=1.5,
              tolerance=0.0, max_iterations=10**9, check_every=1024, graph_iters=64, persistent=3)
 if kind == "smoother":
-    s._stage_pressure, s._warmup, s._nan_exit = 1, 0, True
+    s._smoother_mode()
 diag = kind == "diag"
 s.run_iterations(256, diagnostics=diag)
 T = (s.M + 15) // 16
