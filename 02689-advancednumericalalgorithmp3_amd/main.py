@@ -136,22 +136,71 @@ def one_wide_batch(cfgs: list, n_cus: int, knob: str = None) -> bool:
     return L.lib().ldc_wide_trials_per_launch(n, n, 1 if fsg else 0, int(n_cus)) >= 2
 
 
-def run_batches(groups: list, device: str = None) -> list:
-    """groups: [(cfgs, out_dirs)], each a set of SG (or FSG) trials of equal N that can share their launches.
-    Returns the record lists in the same order.
+SG, FSG, FV = "solvers.spectral.sg.SGSolver", "solvers.spectral.fsg.FSGSolver", "solvers.fv.solver.FVSolver"
+FV_LAUNCH_MAX = 256        # LDC_FV_LAUNCH_MAX (include/ldc_fv.h): one finite-volume work-group per CU of an MI355X
 
-    Every group is cut into two batches (solvers.spectral.batched); the batches of ALL groups then go, longest first,
+
+def batch_key(cfg: dict) -> tuple:
+    """What the trials of one batch must share.  Spectral trials: solver class, N, level hierarchy, diagnostics flag and
+    nx / ny (solver.ny=... overrides).  Finite-volume trials: the solver class alone -- the FV kernel advances any mix
+    of sizes, schemes and parameters in one launch (solvers.fv.batched)."""
+    sv = cfg["solver"]
+    if sv["_target_"] == FV:
+        return (FV,)
+    return (sv["_target_"], int(cfg["N"]), int(sv.get("n_levels", 0)), bool(sv.get("diagnostics", True)),
+            int(sv.get("nx", cfg["N"])), int(sv.get("ny", cfg["N"])))
+
+
+def batch_limit(launcher: dict = None, env=None) -> tuple:
+    """(max_batch, given): the cap on trials per batch from LDC_MAX_BATCH or hydra.launcher.batch_trials (the
+    environment wins), and whether either was given at all (else 64, which some kernels raise: batch_sizes)."""
+    env = os.environ if env is None else env
+    launcher = launcher or {}
+    given = "LDC_MAX_BATCH" in env or "batch_trials" in launcher
+    return int(env.get("LDC_MAX_BATCH", launcher.get("batch_trials", 64))), given
+
+
+def batch_sizes(key: tuple, count: int, max_batch: int, given: bool) -> list:
+    """Sizes of the batches that ``count`` trials sharing ``key`` (batch_key) are cut into, in order; [] when they run
+    one by one (fewer than two trials, LDC_MAX_BATCH=1, or a solver class that has no batch).
+
+    Without a cap from the user a batch is as large as the kernel takes at once where one work-group advances a trial:
+    256 for finite-volume trials and for the spectral sizes the trial-per-CU kernel holds (M = N + 1 <= 44)."""
+    target = key[0]
+    if target not in (SG, FSG, FV) or count < 2 or max_batch <= 1:
+        return []
+    if given or (target != FV and int(key[1]) + 1 > 44):
+        cap = max_batch
+    else:
+        cap = max(max_batch, FV_LAUNCH_MAX)
+    return [min(cap, count - lo) for lo in range(0, count, cap)]
+
+
+def run_batches(groups: list, device: str = None) -> list:
+    """groups: [(cfgs, out_dirs)], each a set of SG (or FSG) trials of equal N, or of finite-volume trials of any sizes,
+    that can share their launches.  Returns the record lists in the same order.
+
+    Every spectral group is cut into two batches (solvers.spectral.batched), a finite-volume group stays one
+    (solvers.fv.batched); the batches of ALL groups then go, longest first,
     through a pool of LDC_BATCH_STREAMS host threads (default 3: one per stream priority of the hardware), one HIP
     stream each.  The launches of the batch on one stream fill the ramp / drain / hand-over gaps of the
     batch on the other -- within one N (two halves of a batch: up to 1.3x) and across sizes (the small-N groups of a
-    grid run in the shadow of the large ones).  A batch that fails leaves error records for its trials only.
-    Records (validation, artefacts, MLflow) are made afterwards, in the caller's thread."""
+    grid run in the shadow of the large ones).  A finite-volume chunk and a spectral chunk whose work-groups must all be
+    resident (modes 3, 4, 5) take turns instead (ldc_lib.resident_lock, inside the solvers).  A batch that fails leaves
+    error records for its trials only, and so does a finite-volume trial that stops on a NaN.  Records (validation,
+    artefacts) are made on the worker right after its batch; with MLflow active afterwards, in the caller's thread."""
     import threading
     from solvers.spectral.batched import BatchedFSGSolver, BatchedSGSolver, run_concurrently
     n_workers = max(1, int(os.environ.get("LDC_BATCH_STREAMS", "3")))
     n_cus = _device_cus(device)      # decides whether a size fills the chip on its own (N >= 241 on 256 CUs)
     tasks = []
     for gi, (cfgs, _) in enumerate(groups):
+        if cfgs[0]["solver"]["_target_"] == FV:
+            # a finite-volume group is ONE batch: its work-groups are independent (one CU each, no waits), so halves on
+            # two streams gain nothing; it lasts as long as its longest trial, whatever the sizes in it
+            weight = max(trial_cost(dict(N=c["N"], Re=c["Re"]), solver=FV) for c in cfgs)
+            tasks.append((weight, gi, 0, len(cfgs)))
+            continue
         parts = max(1, min(2, n_workers, len(cfgs)))      # halves: more, smaller batches measured no better (N=128)
         # a trial whose tiles fill the chip on their own (N >= 241 on 256 CUs) gains nothing from sharing launches (two
         # N=256 trials batched: 20.4 k trial-iterations/s, one after the other 19.7 k) but overlaps well with another
@@ -178,6 +227,9 @@ def run_batches(groups: list, device: str = None) -> list:
     lock, done, early = threading.Lock(), {}, {}
     t0 = time.perf_counter()
 
+    def sizes_of(part):                   # "64" for a spectral batch, "64,128" for a finite-volume batch of mixed sizes
+        return ",".join(str(n) for n in sorted({int(c["N"]) for c in part}))
+
     def worker(_):
         while True:
             with lock:
@@ -195,13 +247,19 @@ def run_batches(groups: list, device: str = None) -> list:
                     #  modes -- are kept from overlapping each other by ldc_lib.resident_lock inside the solvers; the
                     #  launch-path batches of the other worker streams still run beside them)
                     nodes.append(node)
-                fsg = part[0]["solver"]["_target_"].endswith("FSGSolver")
+                target = part[0]["solver"]["_target_"]
                 if len(nodes) == 1:                 # alone on its stream: the single-trial kernels (no argument blocks in memory)
-                    batch = _OneTrial(C.instantiate(dict(nodes[0], _target_=part[0]["solver"]["_target_"])))
+                    batch = _OneTrial(C.instantiate(dict(nodes[0], _target_=target)))
+                elif target == FV:
+                    from solvers.fv.batched import BatchedFVSolver
+                    batch = BatchedFVSolver(nodes)
                 else:
-                    batch = (BatchedFSGSolver if fsg else BatchedSGSolver)(nodes)     # built on this worker's stream
+                    batch = (BatchedFSGSolver if target.endswith("FSGSolver") else BatchedSGSolver)(nodes)     # built on this worker's stream
                 batch.solve()
                 done[(gi, lo)] = batch
+                # trials of a finite-volume batch that stopped on a NaN: an error record each, as a lone run's LdcError
+                # leaves (run_group); the batch's other trials keep theirs
+                failed = getattr(batch, "errors", {})
                 # The records of this batch (validation, Ghia error, results.json, solution.vts: host work on the trials'
                 # own fields, ~45 ms each) right away, on this worker: the other workers' batches keep the GPU busy
                 # meanwhile.  (300 records made after the last batch of a round were 13 s of a 34-s round.)  With MLflow
@@ -209,11 +267,12 @@ def run_batches(groups: list, device: str = None) -> list:
                 if _mlflow() is None:
                     cfgs_g, dirs_g = groups[gi]
                     try:
-                        early[(gi, lo)] = [make_record(cfgs_g[lo + q], s, dirs_g[lo + q], t0) for q, s in enumerate(batch.solvers)]
+                        early[(gi, lo)] = [make_record(cfgs_g[lo + q], s, dirs_g[lo + q], t0) if q not in failed else None
+                                           for q, s in enumerate(batch.solvers)]
                     except Exception:                # the solve stands; its records are tried again, one by one, afterwards
-                        log.exception("records of a batch of %d trials at N=%s failed on the worker", len(part), part[0]["N"])
+                        log.exception("records of a batch of %d trials at N=%s failed on the worker", len(part), sizes_of(part))
             except Exception as exc:                # the other batches go on; the farm reports the failure
-                log.exception("batch of %d trials at N=%s failed", len(part), part[0]["N"])
+                log.exception("batch of %d trials at N=%s failed", len(part), sizes_of(part))
                 done[(gi, lo)] = exc
 
     wall = run_concurrently(list(range(n_threads)), worker, device)
@@ -228,6 +287,10 @@ def run_batches(groups: list, device: str = None) -> list:
                 recs += [dict(error=repr(batch), objective=math.inf) for _ in range(lo, hi)]
                 continue
             for q, s in enumerate(batch.solvers):
+                if q in getattr(batch, "errors", {}):
+                    log.error("trial %d of a batch of %d failed: %s", lo + q, len(batch), batch.errors[q])
+                    recs.append(dict(error=repr(batch.errors[q]), objective=math.inf))
+                    continue
                 scale = wall / busy if (n_threads > 1 and busy > 0) else 1.0      # the shares of all trials add up to the pool's wall time
                 s.metrics.wall_time_seconds *= scale
                 if (gi, lo) in early:               # made on the worker: bring the wall-time share up to date
@@ -383,9 +446,7 @@ def main(argv=None) -> float | None:
     root_dir = time.strftime(str(root_tpl).replace("${now:", "").replace("}", ""), time.localtime())
     root_dir = Path(dist.all_gather_object(root_dir)[0])          # every rank uses rank 0's timestamp
 
-    SG, FSG = "solvers.spectral.sg.SGSolver", "solvers.spectral.fsg.FSGSolver"
-    batch_cap_given = "LDC_MAX_BATCH" in os.environ or "batch_trials" in (stamp_cfg.get("hydra", {}).get("launcher", {}) or {})
-    max_batch = int(os.environ.get("LDC_MAX_BATCH", stamp_cfg.get("hydra", {}).get("launcher", {}).get("batch_trials", 64)))
+    max_batch, batch_cap_given = batch_limit(stamp_cfg.get("hydra", {}).get("launcher", {}))
 
     # Which kernel advances a trial depends, in auto mode, on the size AND on how many trials share its batch (batched.py);
     # the kernels agree to rounding, so an iteration count at the stopping threshold can move by one with LDC_MAX_BATCH, the
@@ -413,25 +474,27 @@ def main(argv=None) -> float | None:
 
     def run_group(items, jobs, offset=0):
         """items: [(index, trial)] owned by this rank with one group key.  Trials that can share their launches
-        -- same solver class, N, level hierarchy and diagnostics flag -- are advanced together; each keeps its
-        own Re / lid / tolerance / max_iterations (solvers.spectral.batched)."""
+        -- spectral: same solver class, N, level hierarchy and diagnostics flag; finite-volume: all of them
+        (batch_key) -- are advanced together; each keeps its own Re / lid / tolerance / max_iterations
+        (solvers.spectral.batched, solvers.fv.batched)."""
         cfgs = [job_cfg(jobs[i], offset + i) for i, _ in items]
         out = [None] * len(cfgs)
         share = {}
         for q, c in enumerate(cfgs):
-            sv = c["solver"]
-            share.setdefault((sv["_target_"], int(c["N"]), int(sv.get("n_levels", 0)), bool(sv.get("diagnostics", True)),
-                              int(sv.get("nx", c["N"])), int(sv.get("ny", c["N"]))), []).append(q)      # (nx, ny: solver.ny=... overrides)
+            share.setdefault(batch_key(c), []).append(q)
         groups, where = [], []
-        for (target, _, _, _, _, _), members in share.items():
-            if target in (SG, FSG) and len(members) > 1 and max_batch > 1:
-                # sizes the trial-per-CU kernel holds (M <= 44): one work-group per trial, 256 advance at once -- a larger
-                # batch is a better batch there (unless LDC_MAX_BATCH / hydra.launcher.batch_trials says otherwise)
-                n_of = int(cfgs[members[0]]["N"])
-                cap = max_batch if (batch_cap_given or n_of + 1 > 44) else max(max_batch, 256)
-                for lo in range(0, len(members), cap):
-                    part = members[lo: lo + cap]
-                    log.info("batch of %d trials at N=%s on %s", len(part), cfgs[part[0]]["N"], device or "cuda:0")
+        for key, members in share.items():
+            # sizes the trial-per-CU kernel holds (M <= 44) and finite-volume trials: one work-group per trial, 256 advance
+            # at once -- a larger batch is a better batch there (unless LDC_MAX_BATCH / hydra.launcher.batch_trials says
+            # otherwise: batch_sizes)
+            sizes = batch_sizes(key, len(members), max_batch, batch_cap_given)
+            if sizes:
+                lo = 0
+                for size in sizes:
+                    part = members[lo: lo + size]
+                    lo += size
+                    log.info("batch of %d trials at N=%s on %s", len(part),
+                             ",".join(str(n) for n in sorted({int(cfgs[q]["N"]) for q in part})), device or "cuda:0")
                     groups.append(([cfgs[q] for q in part], [root_dir / str(offset + items[q][0]) for q in part]))
                     where.append(part)
             else:

@@ -1,0 +1,161 @@
+"""Batched finite-volume trials: independent FV solves advanced by the same launches, one work-group (one CU) each.
+
+The reference's only parallel axis is the trial (conf/machine/local.yaml:5-9, scripts/hpc_submit.py:103-107).  An FV
+trial is ONE work-group for its whole life (include/ldc_fv.h), so a lone trial uses 1/256 of an MI355X;
+``ldc_fv_batch_enqueue`` launches up to ``LDC_FV_LAUNCH_MAX`` = 256 of them per launch, of ANY sizes and parameters.
+The work-groups never wait for each other (no flags, no spins, no co-residency among them), and the kernel
+keeps no state between launches other than the trial's own arrays, with reductions in a fixed order.  So every trial's
+fields, record rows, iteration count, latch and counters are bit-identical to its lone ``FVSolver.solve()``, whatever
+else is in the batch and wherever the chunk boundaries fall (tests/test_gpu_fv_batched.py).
+
+An FV work-group needs nobody, but it HOLDS its CU for a whole chunk (175 VGPRs x 8 waves: nothing of the spectral
+kernels' co-resident work-groups fits beside it), and the spectral kernels of modes 3, 4 and 5 need all their
+work-groups resident at once and give up after a bounded spin.  So every FV chunk runs under the device's
+``ldc_lib.resident_lock``, like those launches do: in a mixed sweep an FV chunk and a co-resident spectral chunk take
+turns, while launch-path spectral batches of other streams still run beside either.
+"""
+from __future__ import annotations
+
+import logging
+import time
+
+import numpy as np
+
+from ..base import WARMUP_ITERATIONS
+from ..spectral import ldc_lib as L
+from . import ldc_fv_lib as F
+from .solver import FVSolver
+
+log = logging.getLogger(__name__)
+
+
+def run_chunks(rec_caps, caps, step):
+    """Every trial from iteration 0 to ITS latch, ITS cap or a NaN, chunk by chunk; per-trial (latch, nan, iterations,
+    record rows).
+
+    ``step(live, k)`` advances the trials ``live`` (indices, ascending) by up to ``k`` iterations in one launch and
+    returns, in the same order, (rows of the new iterations, latch, nan, iteration count).  A trial that latched, went
+    NaN or reached its cap leaves the live list and is never passed to ``step`` again: its work-group is not launched
+    at all (the spectral batches latch such a trial on the device instead, chunks.LATCH_CAPPED).  All trials start at 0,
+    so the live ones are in step, and a chunk is as long as the smallest record ring and the smallest remaining cap
+    among them allow."""
+    n = len(caps)
+    state = [(0, 0, 0)] * n                   # (latch, nan, iterations)
+    blocks = [[] for _ in range(n)]
+    live = [q for q in range(n) if caps[q] > 0]
+    it = 0
+    while live:
+        k = min(min(rec_caps[q] for q in live), min(caps[q] for q in live) - it)
+        out = step(list(live), k)
+        if len(out) != len(live):
+            raise RuntimeError("one result per live trial expected")
+        for q, (rows, latch, nan, total) in zip(live, out):
+            if total == it and not (latch or nan):
+                raise RuntimeError("device loop made no progress")
+            blocks[q].append(rows)
+            state[q] = (int(latch), int(nan), int(total))
+        it += k
+        live = [q for q in live if not (state[q][0] or state[q][1]) and state[q][2] < caps[q]]
+    return [(latch, nan, total, np.concatenate(b, axis=0) if b else np.zeros((0, F.REC_LEN)))
+            for (latch, nan, total), b in zip(state, blocks)]
+
+
+def _words(tensors):
+    """ONE device-to-host copy of a block of every trial (the idiom of solvers.spectral.chunks._words: a blocking copy
+    per trial was measured there to cost as much as the chunk itself at 256 trials)."""
+    import torch
+    return (tensors[0][None] if len(tensors) == 1 else torch.stack(tensors)).cpu().numpy()
+
+
+class BatchedFVSolver:
+    """``trials``: list of FVSolver keyword dicts, all on one device.  They need not share nx / ny, scheme,
+    relaxation, lid treatment, tolerance, ``max_iterations`` or ``check_every``: the kernel takes any mix.
+
+    ``solve()`` fills every solver's history / metrics / fields as its lone ``solve()`` would.  A trial whose kernel
+    reports a NaN ends as a lone run ends -- with the ``LdcError`` of ``ldc_fv_status`` -- but here the exception is
+    kept in ``errors[index]`` instead of raised, and the other trials are not disturbed."""
+
+    def __init__(self, trials: list):
+        if not trials:
+            raise ValueError("BatchedFVSolver needs at least one trial")
+        self.solvers = []
+        try:
+            for t in trials:
+                self.solvers.append(FVSolver(**t))
+        except BaseException:                 # the handles of the trials already built
+            self.close()
+            raise
+        import torch
+        devs = {(d.type, torch.cuda.current_device() if d.index is None else d.index)
+                for d in (s.device for s in self.solvers)}
+        if len(devs) != 1:
+            self.close()
+            raise ValueError(f"all trials of a batch must be on one device, got {sorted(devs)}")
+        self.errors = {}
+        self.batch_seconds, self.batch_size = 0.0, len(self.solvers)
+        self._iters = [0] * len(self.solvers)
+
+    def __len__(self):
+        return len(self.solvers)
+
+    def close(self):
+        for s in self.solvers:
+            s.close()
+
+    def _step(self, live, k):
+        """One ``ldc_fv_batch_enqueue`` over the live trials, then ONE copy of their ctrl words and ONE of the first
+        ``k`` rows of their record rings (k <= every ring, so the slices stack whatever the rings' own lengths).  Launch
+        and wait hold the device's resident lock (module docstring)."""
+        import torch
+        trials = [self.solvers[q] for q in live]
+        dev = trials[0].device
+        index = torch.cuda.current_device() if dev.index is None else dev.index
+        with torch.cuda.device(dev):
+            with L.resident_lock(index):
+                F.batch_enqueue([s.handle for s in trials], k, torch.cuda.current_stream(dev).cuda_stream)
+                ctrl = _words([s.t["ctrl"] for s in trials])        # (synchronises the stream)
+            rings = _words([s.t["rec"][:k] for s in trials])
+        out = []
+        for q, c, ring in zip(live, ctrl, rings):
+            total = int(c[F.CTRL_ITER])
+            out.append((ring[: total - self._iters[q]].copy(), int(c[F.CTRL_DONE]), int(c[F.CTRL_NAN]), total))
+            self._iters[q] = total
+        return out
+
+    def solve(self, max_iter: int = None):
+        """Every trial to its own tolerance or its own ``max_iterations`` (``max_iter``: one cap for all).
+
+        Only the batch has a wall time of its own (``batch_seconds``).  A trial's ``metrics.wall_time_seconds`` is
+        its share of it in proportion to its work, iterations x nx x ny; the shares of the trials that finished add
+        up to ``batch_seconds``.  No live MLflow metrics per chunk, as in the spectral batches.  Returns the trials'
+        metrics in order, None for a trial listed in ``errors`` (its solver keeps the metrics it was built with)."""
+        ps = [s.params for s in self.solvers]
+        caps = [int(p.max_iterations if max_iter is None else max_iter) for p in ps]
+        for s, p in zip(self.solvers, ps):
+            s._begin(p.tolerance)
+        self._iters = _words([s.t["ctrl"] for s in self.solvers])[:, F.CTRL_ITER].tolist()
+        if any(self._iters):
+            raise ValueError("BatchedFVSolver.solve() starts every trial at iteration 0; build a new batch to solve again")
+        self.errors = {}
+        t0 = time.perf_counter()
+        out = run_chunks([s.rec_cap for s in self.solvers], caps, self._step)
+        wall = time.perf_counter() - t0
+        self.batch_seconds, self.batch_size = wall, len(self.solvers)
+        for q, (s, (_, nan, total, _)) in enumerate(zip(self.solvers, out)):
+            if nan:                           # what a lone _advance raises (ldc_fv_status -> LDC_FV_E_NAN)
+                try:
+                    F.check(F.lib().ldc_fv_status(s.handle), f"FV trial at iteration {total}")
+                    raise RuntimeError(f"FV trial at iteration {total}: ctrl reports a NaN, ldc_fv_status does not")
+                except Exception as exc:
+                    self.errors[q] = exc
+        work = [0 if q in self.errors else total * s.nx * s.ny
+                for q, (s, (_, _, total, _)) in enumerate(zip(self.solvers, out))]
+        work_all = max(1, sum(work))
+        for q, (s, (done, _, total, hist)) in enumerate(zip(self.solvers, out)):
+            if q in self.errors:
+                continue
+            s.history = hist
+            s._store_results(hist[WARMUP_ITERATIONS:], total, done == 1, wall * work[q] / work_all)
+        log.info("batched solve of %d FV trials finished in %.2f s (%d stopped on a NaN)", len(self.solvers), wall,
+                 len(self.errors))
+        return [None if q in self.errors else s.metrics for q, s in enumerate(self.solvers)]

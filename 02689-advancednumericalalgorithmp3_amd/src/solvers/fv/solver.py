@@ -183,7 +183,11 @@ class FVSolver(LidDrivenCavitySolver):
         import torch
         n_iters = max(1, min(int(n_iters), self.rec_cap))
         before = int(self.t["ctrl"][F.CTRL_ITER].item())
-        with torch.cuda.device(self.device):
+        from solvers.spectral import ldc_lib
+        index = torch.cuda.current_device() if self.device.index is None else self.device.index
+        # the work-group holds its CU for the whole chunk: not beside a launch whose work-groups must all be resident
+        # (a lone trial in the launcher's pool of streams, next to spectral batches; solvers.fv.batched)
+        with torch.cuda.device(self.device), ldc_lib.resident_lock(index):
             F.check(F.lib().ldc_fv_enqueue(self._handle, n_iters, C.c_void_p(self._stream())), "ldc_fv_enqueue")
             ctrl = self.t["ctrl"].cpu().numpy()            # (synchronises the stream)
         total = int(ctrl[F.CTRL_ITER])

@@ -98,6 +98,8 @@ def trial_cost(trial: dict, solver: str = None, batch: int = 1) -> float:
     n, re = float(t.get("N", 32)), float(t.get("Re", 100))
     kind = str(t.get("solver", solver or "")).lower()
     if "solvers.fv" in kind or kind == "fv":
+        # ``batch`` does not enter: every FV trial of a batch has a work-group (a CU) of its own (solvers.fv.batched), so
+        # up to 256 trials per card a trial costs what it costs alone, and a batch lasts as long as its longest trial
         res = sorted({r for _, r in _FV_ITERATIONS})
         r = min(res, key=lambda q: abs(math.log(q / max(re, 1e-9))))
         its = _FV_ITERATIONS[(128, r)] * (n / 128.0)           # SIMPLE iterations grow about linearly in N

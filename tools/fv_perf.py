@@ -4,10 +4,21 @@
 BiCGSTAB iterations per momentum solve.  Prints one JSON line per measurement.
 
     python tools/fv_perf.py [--iters 200] [--batch 256] [--batch-n 64]
+
+``--sweep`` times a whole finite-volume sweep through the launcher instead: the grid N = 64, 128 x Re = 100, 400, 1000
+(TVD, tolerance 1e-6, max_iterations 20000 so that no trial can run away) in a fresh child process, and prints one line
+with the wall time of the process, the launcher's own time inside the solves and every trial's iterations and time.
+``--main`` points at the main.py of another checkout (a worktree of the parent commit, built there) for an A/B on one
+card; ``--max-batch 1`` runs this checkout's trials one by one.
+
+    python tools/fv_perf.py --sweep [--label head] [--main /path/to/other/checkout/02689-.../main.py] [--max-batch 1]
 """
 import argparse
 import json
+import os
+import subprocess
 import sys
+import tempfile
 import time
 from pathlib import Path
 
@@ -15,14 +26,49 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path[:0] = [str(ROOT), str(ROOT / "02689-advancednumericalalgorithmp3_amd" / "src")]
 
 
+SWEEP = ["-m", "solver=fv", "N=64,128", "Re=100,400,1000", "tolerance=1e-6", "max_iterations=20000"]
+
+
+def sweep(a):
+    main_py = Path(a.main).resolve() if a.main else ROOT / "02689-advancednumericalalgorithmp3_amd" / "main.py"
+    env = {k: v for k, v in os.environ.items() if k != "LDC_MAX_BATCH"}
+    if a.max_batch is not None:
+        env["LDC_MAX_BATCH"] = str(a.max_batch)
+    with tempfile.TemporaryDirectory() as tmp:
+        t0 = time.perf_counter()
+        r = subprocess.run([sys.executable, str(main_py)] + SWEEP, cwd=tmp, env=env, capture_output=True, text=True,
+                           timeout=a.timeout)
+        wall = time.perf_counter() - t0
+        if r.returncode != 0:
+            sys.exit(f"the sweep failed ({r.returncode}):\n{r.stderr[-3000:]}")
+        recs = json.loads(next(Path(tmp).rglob("sweep_results.json")).read_text())
+    trials = [dict(N=x["N"], Re=x["Re"], iterations=x["metrics"]["iterations"], converged=x["metrics"]["converged"],
+                   seconds=round(x["metrics"]["wall_time_seconds"], 3), batch_size=x.get("solve_batch_size", 1),
+                   record_seconds=round(x["total_seconds"], 3)) for x in recs]
+    print(json.dumps(dict(what="sweep", label=a.label, max_batch=a.max_batch, trials=len(trials),
+                          wall_seconds=round(wall, 2),
+                          # inside the solves: the batch's own wall time, or the sum of the lone solves
+                          solve_seconds=round(max((x.get("solve_batch_seconds", 0.0) for x in recs), default=0.0)
+                                              or sum(t["seconds"] for t in trials), 2),
+                          slowest_trial_seconds=max(t["seconds"] for t in trials) if all(t["batch_size"] == 1 for t in trials) else None,
+                          per_trial=trials)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sweep", action="store_true", help="time the N = 64, 128 x Re = 100, 400, 1000 sweep through main.py")
+    ap.add_argument("--label", default="head")
+    ap.add_argument("--main", default=None, help="main.py of another (built) checkout")
+    ap.add_argument("--max-batch", type=int, default=None, help="LDC_MAX_BATCH of the child process")
+    ap.add_argument("--timeout", type=float, default=900.0)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warm", type=int, default=300)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--batch-n", type=int, default=64)
     ap.add_argument("--sizes", default="64,128,256")
     a = ap.parse_args()
+    if a.sweep:
+        return sweep(a)
     import torch
     import __graft_entry__ as g
     g.build()
