@@ -71,9 +71,10 @@ class BatchedFVSolver:
     """``trials``: list of FVSolver keyword dicts, all on one device.  They need not share nx / ny, scheme,
     relaxation, lid treatment, tolerance, ``max_iterations`` or ``check_every``: the kernel takes any mix.
 
-    ``solve()`` fills every solver's history / metrics / fields as its lone ``solve()`` would.  A trial whose kernel
-    reports a NaN ends as a lone run ends -- with the ``LdcError`` of ``ldc_fv_status`` -- but here the exception is
-    kept in ``errors[index]`` instead of raised, and the other trials are not disturbed."""
+    ``solve()`` fills every solver's history / metrics / fields as its lone ``solve()`` would; called again, it goes
+    on from the fields the trials hold, counting from 0 with a new warm-up, as a lone repeat solve does.  A trial whose
+    kernel reports a NaN ends as a lone run ends -- with the ``LdcError`` of ``ldc_fv_status`` -- but here the exception
+    is kept in ``errors[index]`` instead of raised, and the other trials are not disturbed."""
 
     def __init__(self, trials: list):
         if not trials:
@@ -132,10 +133,8 @@ class BatchedFVSolver:
         ps = [s.params for s in self.solvers]
         caps = [int(p.max_iterations if max_iter is None else max_iter) for p in ps]
         for s, p in zip(self.solvers, ps):
-            s._begin(p.tolerance)
-        self._iters = _words([s.t["ctrl"] for s in self.solvers])[:, F.CTRL_ITER].tolist()
-        if any(self._iters):
-            raise ValueError("BatchedFVSolver.solve() starts every trial at iteration 0; build a new batch to solve again")
+            s._begin(p.tolerance)             # control words to zero: every trial counts from 0 on its current fields
+        self._iters = [0] * len(self.solvers)
         self.errors = {}
         t0 = time.perf_counter()
         out = run_chunks([s.rec_cap for s in self.solvers], caps, self._step)

@@ -176,8 +176,11 @@ class FVSolver(LidDrivenCavitySolver):
 
     # ---- LidDrivenCavitySolver hooks --------------------------------------------------------------------
     def _begin(self, tolerance: float):
+        """A new solve: the trial's control words start at zero (latch, iteration count, NaN flag, the linear-solver
+        counters), the fields stay.  Like the reference's loop (base.py:243) and the spectral solvers, every
+        ``solve()`` counts from 0 on the current state, with its own warm-up, history and iteration count."""
         self._make_handle(tolerance)
-        self.t["ctrl"][F.CTRL_DONE] = 0
+        self.t["ctrl"].zero_()
 
     def _advance(self, n_iters: int):
         import torch

@@ -15,7 +15,11 @@
  *    rel_change, |u'|, |v'|, |div mdot|, E, Z, P, 0   (the record of include/ldc_hip.h with DT = 0);
  *  - ctrl: LDC_FV_CTRL_LEN int64: [0] converged latch, [1] iterations done, [2] NaN seen (the trial stopped),
  *    [3] momentum solves that hit max_lin_iters (accepted, as the reference does), [4] BiCGSTAB iterations of all
- *    momentum solves, [5] momentum solves.  Zero it before the first enqueue.
+ *    momentum solves, [5] momentum solves.  Zero ALL of it to start a solve, before the first enqueue and again
+ *    before every later solve on the same handle: the kernel counts on from ctrl[1], tests the latch only once
+ *    ctrl[1] >= warmup and adds to [3..5], so words left from a finished solve would skip the warm-up and report
+ *    running totals.  The state (u, v, p, mdot) is not touched by that: a new solve continues from the fields.
+ *    Between the enqueues of ONE solve leave ctrl alone.
  *  - functions return 0, a negative LDC_E_* code of ldc_hip.h, LDC_FV_E_NAN, or a positive hipError_t.
  */
 #ifndef LDC_FV_H

@@ -6,8 +6,9 @@ cover (DESIGN.md FV-Q1).  Same layouts as include/ldc_fv.h: cells ``c = j*nx + i
 ``fx`` (ny, nx+1) in +x and ``fy`` (ny+1, nx) in +y; the momentum matrix as five diagonals.
 
 The linear solves are the kernel's: Jacobi-preconditioned BiCGSTAB with SciPy's iteration and stopping rule
-(rtol relative to |b|, atol = 0, x0 = 0, 1000 iterations, non-convergence accepted), and the pinned pressure
-correction by fast diagonalisation.
+(rtol relative to |b|, atol = 0, x0 = 0, ``max_lin_iters`` = 1000 iterations, non-convergence accepted; ``iters``
+and ``exits`` record each solve's count and which test ended it), and the pinned pressure correction by fast
+diagonalisation.
 
 ``psi_up`` selects the TVD limiter value for faces with mdot >= 0 (FV-Q1): "muscl" (the product), "zero" or "one".
 """
@@ -48,7 +49,7 @@ def muscl(r):
 class FVState:
     def __init__(self, nx, ny, Re, Lx=1.0, Ly=1.0, lid_velocity=1.0, corner_treatment="none",
                  corner_smoothing=0.15, alpha_uv=0.4, alpha_p=0.2, linear_solver_tol=1e-9,
-                 convection_scheme="TVD", psi_up="muscl", rho=1.0):
+                 convection_scheme="TVD", psi_up="muscl", rho=1.0, max_lin_iters=1000):
         self.nx, self.ny = nx, ny
         self.dx, self.dy = Lx / nx, Ly / ny
         self.V = self.dx * self.dy
@@ -71,7 +72,9 @@ class FVState:
         den[0, 0] = 1.0
         self.inv_den = 1.0 / den
         self.inv_den[0, 0] = 0.0
+        self.max_lin_iters = max_lin_iters
         self.iters = []                     # BiCGSTAB iterations of each momentum solve
+        self.exits = []                     # and why each stopped: b0, r, s, rho, omega, rv or cap
 
     # ------------------------------------------------------------------ pieces
     def gradient(self, f):
@@ -161,11 +164,13 @@ class FVState:
         y[:-1, :] += d[4][:-1, :] * x[1:, :]
         return y
 
-    def bicgstab(self, d, diagP, b, maxiter=1000):
+    def bicgstab(self, d, diagP, b, maxiter=None):
         """SciPy's BiCGSTAB (right preconditioning) with a Jacobi preconditioner; non-convergence accepted."""
+        maxiter = self.max_lin_iters if maxiter is None else maxiter
         bn = np.linalg.norm(b)
         if bn == 0:
             self.iters.append(0)
+            self.exits.append("b0")
             return np.zeros_like(b)
         atol = self.tol * bn
         x = np.zeros_like(b)
@@ -175,14 +180,18 @@ class FVState:
         rho_prev = omega = alpha = None
         p = v = None
         it = 0
+        why = "cap"
         for it in range(maxiter):
             if np.linalg.norm(r) < atol:
+                why = "r"
                 break
             rho = np.vdot(rt, r)
             if abs(rho) < rhotol:
+                why = "rho"
                 break
             if it > 0:
                 if abs(omega) < rhotol:
+                    why = "omega"
                     break
                 beta = (rho / rho_prev) * (alpha / omega)
                 p = r + beta * (p - omega * v)
@@ -192,12 +201,14 @@ class FVState:
             v = self.matvec(d, diagP, phat)
             rv = np.vdot(rt, v)
             if rv == 0:
+                why = "rv"
                 break
             alpha = rho / rv
             s = r - alpha * v
             if np.linalg.norm(s) < atol:
                 x = x + alpha * phat
                 it += 1
+                why = "s"
                 break
             shat = s / diagP
             t = self.matvec(d, diagP, shat)
@@ -208,6 +219,7 @@ class FVState:
         else:
             it = maxiter
         self.iters.append(it)
+        self.exits.append(why)
         return x
 
     def pressure_solve(self, b):

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Generate the g14 fixtures of the finite-volume (SIMPLE) solver by running the *reference* FV solver here.
+"""Generate the g14 and g15 fixtures of the finite-volume (SIMPLE) solver by running the *reference* FV solver.
 
 TEST INFRASTRUCTURE, like make_golden.py: the reference is imported read-only, by path, and only the numbers it
-produces are written (``g14_fv_*.npz`` / ``.json`` next to this file).  Stand-ins registered before the import:
+produces are written (``g14_fv_*`` / ``g15_fv_*`` ``.npz`` / ``.json`` next to this file).  Stand-ins registered before the import:
 
 * ``numba``: ``njit`` / ``jitclass`` are identities, ``prange`` is ``range``, ``numba.types`` accepts any spec;
 * ``pyamg``: ``smoothed_aggregation_solver(A).aspreconditioner()`` becomes an exact sparse LU solve (SciPy
@@ -17,7 +17,7 @@ Layouts of the stored arrays (the product's own, include/ldc_fv.h): cells ``c = 
 ``fx[j][i]`` (i = 0..nx, flux in +x through the face at x_i) then ``fy[j][i]`` (j = 0..ny, flux in +y); the momentum
 matrix as five diagonals ``aP, aW, aE, aS, aN`` (aP unrelaxed).
 
-Usage:  python tests/golden/make_golden_fv.py
+Usage:  python tests/golden/make_golden_fv.py [--only g14|g15]
 """
 from __future__ import annotations
 
@@ -174,10 +174,14 @@ def seed_state(s, rng):
 # --------------------------------------------------------------------------- groups
 def g14_step():
     """One iteration's intermediates at N = 16 (and 12 x 20) from a seeded smooth state."""
+    _step_group("g14_fv_step", 14, (("N16", 16, 16, 100.0, {}), ("12x20", 12, 20, 400.0, {})))
+
+
+def _step_group(name, seed, cases):
     out, meta = {}, {}
-    for tag, nx, ny, Re in (("N16", 16, 16, 100.0), ("12x20", 12, 20, 400.0)):
-        mod, s = make_fv(nx, ny, Re)
-        rng = np.random.default_rng(14)
+    for tag, nx, ny, Re, kw in cases:
+        mod, s = make_fv(nx, ny, Re, **kw)
+        rng = np.random.default_rng(seed)
         u0, v0, p0, m0 = seed_state(s, rng)
         cap = {"asm": [], "solve": []}
         real_asm, real_solve = mod.assemble_diffusion_convection_matrix, mod.scipy_solver
@@ -210,9 +214,9 @@ def g14_step():
             f"{tag}_p_prime": cap["solve"][2][1], f"{tag}_u_prime": a.u_prime.copy(), f"{tag}_v_prime": a.v_prime.copy(),
             f"{tag}_mdot": faces_to_structured(s, a.mdot), f"{tag}_u": a.u.copy(), f"{tag}_v": a.v.copy(),
             f"{tag}_p": a.p.copy()})
-        meta[tag] = dict(nx=nx, ny=ny, Re=Re, lid="none", mu=s.mu, **PARAMS)
-    np.savez_compressed(OUT / "g14_fv_step.npz", **out)
-    (OUT / "g14_fv_step.json").write_text(json.dumps(meta, indent=1))
+        meta[tag] = dict(nx=nx, ny=ny, Re=Re, lid="none", mu=s.mu, **PARAMS, **kw)
+    np.savez_compressed(OUT / f"{name}.npz", **out)
+    (OUT / f"{name}.json").write_text(json.dumps(meta, indent=1))
 
 
 def g14_trajectories():
@@ -227,8 +231,8 @@ def g14_trajectories():
     (OUT / "g14_fv_traj.json").write_text(json.dumps(meta, indent=1))
 
 
-def _run(out, meta, nx, ny, Re, K, lid):
-    _, s = make_fv(nx, ny, Re, lid=lid)
+def _run(out, meta, nx, ny, Re, K, lid, **kw):
+    _, s = make_fv(nx, ny, Re, lid=lid, **kw)
     tag = f"nx{nx}_ny{ny}_Re{Re}_{lid}_K{K}"
     a = s.arrays
     u_prev, v_prev = a.u.copy(), a.v.copy()
@@ -239,10 +243,78 @@ def _run(out, meta, nx, ny, Re, K, lid):
         u_prev, v_prev = a.u.copy(), a.v.copy()
     out.update({f"{tag}_rec": np.array(rows), f"{tag}_u": a.u.copy(), f"{tag}_v": a.v.copy(),
                 f"{tag}_p": a.p.copy(), f"{tag}_mdot": faces_to_structured(s, a.mdot)})
-    meta[tag] = dict(nx=nx, ny=ny, Re=float(Re), K=K, lid=lid, mu=s.mu, **PARAMS)
+    meta[tag] = dict(nx=nx, ny=ny, Re=float(Re), K=K, lid=lid, mu=s.mu, **PARAMS, **kw)
     print(tag, "rel", rows[-1][0])
 
 
+# --------------------------------------------------------------------------- g15: odd sizes, Lx != Ly, lid != 1
+WIDE = dict(Lx=2.0, Ly=0.5, lid_velocity=2.0)       # the 37 x 50 cases
+
+
+def g15_step():
+    """One iteration's intermediates at 13 x 17 and at 37 x 50 cells (1850: more than three strides of the kernel's
+    512 threads) on a 2 x 0.5 cavity with lid speed 2."""
+    _step_group("g15_fv_step", 15, (("13x17", 13, 17, 100.0, {}), ("37x50", 37, 50, 400.0, WIDE)))
+
+
+def g15_trajectories():
+    """Trajectories from rest at sizes that are no multiple of 4 (nor of the 16 x 16 tile), a thin rectangle, and the
+    wide cavity with the smoothed lid."""
+    out, meta = {}, {}
+    _run(out, meta, 13, 17, 100, 40, "none")
+    _run(out, meta, 9, 30, 400, 30, "none")
+    _run(out, meta, 8, 67, 100, 30, "none")
+    _run(out, meta, 37, 50, 400, 25, "smoothing", **WIDE)
+    np.savez_compressed(OUT / "g15_fv_traj.npz", **out)
+    (OUT / "g15_fv_traj.json").write_text(json.dumps(meta, indent=1))
+
+
+def g15_converged(nx=13, ny=17, Re=100.0, tolerance=1e-4, margin=1e-4):
+    """The reference's own solve() to its stopping rule: iteration count, metrics, time series and final fields.
+
+    The count is only a fair demand on another implementation if rounding cannot move it: rel at the stopping
+    iteration and at the one before must each be ``margin`` (relative) away from the tolerance."""
+    _, s = make_fv(nx, ny, Re, tolerance=tolerance, max_iterations=5000)
+    s.solve()
+    m = {k: (v.item() if isinstance(v, np.generic) else v) for k, v in s.metrics.__dict__.items()}
+    m["wall_time_seconds"] = float(m["wall_time_seconds"])
+    ts = {k: list(map(float, v)) if v else [] for k, v in s.time_series.__dict__.items()}
+    rel = ts["rel_iter_residual"]
+    assert m["converged"] and len(rel) == m["iterations"] - 10, "every recorded iteration kept (no downsampling)"
+    margins = dict(at_stop=(tolerance - rel[-1]) / tolerance, before_stop=(rel[-2] - tolerance) / tolerance)
+    assert margins["at_stop"] >= margin and margins["before_stop"] >= margin, margins
+    a = s.arrays
+    meta = dict(nx=nx, ny=ny, Re=Re, lid="none", tolerance=tolerance, mu=s.mu, **PARAMS, metrics=m, margins=margins,
+                time_series_len={k: len(v) for k, v in ts.items()})
+    (OUT / "g15_fv_converged.json").write_text(json.dumps(meta, indent=1))
+    np.savez_compressed(OUT / "g15_fv_converged.npz", u=s.fields.u, v=s.fields.v, p=s.fields.p,
+                        mdot=faces_to_structured(s, a.mdot), **{f"ts_{k}": np.array(v) for k, v in ts.items()})
+    print("converged", nx, ny, Re, "iterations", m["iterations"], "margins", margins)
+
+
+def g15_lid_profiles(nx=13, ny=8, Lx=2.0, lid_velocity=2.0):
+    """u on the lid faces, as the reference's mesh builder sets it, west to east."""
+    _install_shims()
+    from shared.meshing.simple_structured import create_structured_mesh_2d
+    out = {}
+    for lid in ("none", "saad", "smoothing"):
+        m = create_structured_mesh_2d(nx=nx, ny=ny, Lx=Lx, Ly=1.0, lid_velocity=lid_velocity, corner_treatment=lid,
+                                      corner_smoothing=0.15)
+        top = [f for f in m.boundary_faces if abs(m.face_centers[f][1] - 1.0) < 1e-10]
+        top.sort(key=lambda f: m.face_centers[f][0])
+        assert len(top) == nx
+        out[lid] = np.array([m.boundary_values[f][0] for f in top])
+    np.savez_compressed(OUT / "g15_fv_lid.npz", **out)
+    meta = dict(nx=nx, Lx=Lx, lid_velocity=lid_velocity, corner_smoothing=0.15)
+    (OUT / "g15_fv_lid.json").write_text(json.dumps(meta, indent=1))
+
+
+GROUPS = {"g14": (g14_step, g14_trajectories), "g15": (g15_step, g15_trajectories, g15_converged, g15_lid_profiles)}
+
 if __name__ == "__main__":
-    g14_step()
-    g14_trajectories()
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", choices=sorted(GROUPS), help="one group (default: all)")
+    for name in ([ap.parse_args().only] if ap.parse_args().only else sorted(GROUPS)):
+        for fn in GROUPS[name]:
+            fn()
