@@ -22,9 +22,8 @@ import time
 import numpy as np
 
 from ..base import WARMUP_ITERATIONS
-from ..spectral import ldc_lib as L
 from . import ldc_fv_lib as F
-from .solver import FVSolver
+from .solver import FVSolver, advance
 
 log = logging.getLogger(__name__)
 
@@ -60,13 +59,6 @@ def run_chunks(rec_caps, caps, step):
             for (latch, nan, total), b in zip(state, blocks)]
 
 
-def _words(tensors):
-    """ONE device-to-host copy of a block of every trial (the idiom of solvers.spectral.chunks._words: a blocking copy
-    per trial was measured there to cost as much as the chunk itself at 256 trials)."""
-    import torch
-    return (tensors[0][None] if len(tensors) == 1 else torch.stack(tensors)).cpu().numpy()
-
-
 class BatchedFVSolver:
     """``trials``: list of FVSolver keyword dicts, all on one device.  They need not share nx / ny, scheme,
     relaxation, lid treatment, tolerance, ``max_iterations`` or ``check_every``: the kernel takes any mix.
@@ -94,7 +86,6 @@ class BatchedFVSolver:
             raise ValueError(f"all trials of a batch must be on one device, got {sorted(devs)}")
         self.errors = {}
         self.batch_seconds, self.batch_size = 0.0, len(self.solvers)
-        self._iters = [0] * len(self.solvers)
 
     def __len__(self):
         return len(self.solvers)
@@ -104,24 +95,8 @@ class BatchedFVSolver:
             s.close()
 
     def _step(self, live, k):
-        """One ``ldc_fv_batch_enqueue`` over the live trials, then ONE copy of their ctrl words and ONE of the first
-        ``k`` rows of their record rings (k <= every ring, so the slices stack whatever the rings' own lengths).  Launch
-        and wait hold the device's resident lock (module docstring)."""
-        import torch
-        trials = [self.solvers[q] for q in live]
-        dev = trials[0].device
-        index = torch.cuda.current_device() if dev.index is None else dev.index
-        with torch.cuda.device(dev):
-            with L.resident_lock(index):
-                F.batch_enqueue([s.handle for s in trials], k, torch.cuda.current_stream(dev).cuda_stream)
-                ctrl = _words([s.t["ctrl"] for s in trials])        # (synchronises the stream)
-            rings = _words([s.t["rec"][:k] for s in trials])
-        out = []
-        for q, c, ring in zip(live, ctrl, rings):
-            total = int(c[F.CTRL_ITER])
-            out.append((ring[: total - self._iters[q]].copy(), int(c[F.CTRL_DONE]), int(c[F.CTRL_NAN]), total))
-            self._iters[q] = total
-        return out
+        """One chunk of the live trials (solver.advance: one launch, one copy of the ctrl words, one of the rows)."""
+        return advance([self.solvers[q] for q in live], k)
 
     def solve(self, max_iter: int = None):
         """Every trial to its own tolerance or its own ``max_iterations`` (``max_iter``: one cap for all).
@@ -134,7 +109,6 @@ class BatchedFVSolver:
         caps = [int(p.max_iterations if max_iter is None else max_iter) for p in ps]
         for s, p in zip(self.solvers, ps):
             s._begin(p.tolerance)             # control words to zero: every trial counts from 0 on its current fields
-        self._iters = [0] * len(self.solvers)
         self.errors = {}
         t0 = time.perf_counter()
         out = run_chunks([s.rec_cap for s in self.solvers], caps, self._step)

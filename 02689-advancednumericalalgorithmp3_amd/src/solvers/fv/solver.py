@@ -51,6 +51,30 @@ def neumann_eig(n: int):
     return lam, Q
 
 
+def advance(trials, k):
+    """One chunk for lone trials and batches alike: ``k`` iterations (at most every trial's record ring) for each of
+    ``trials`` (FVSolvers on one device) in ONE launch, one work-group each, then ONE copy of their ctrl words and ONE of
+    the first ``k`` rows of their record rings (the slices stack whatever the rings' own lengths); per trial (rows of the
+    new iterations, latch, nan, iteration count).
+
+    A work-group holds its CU for the whole chunk, so launch and wait hold the device's resident lock: not beside a
+    launch whose work-groups must all be resident (a lone trial in the launcher's pool of streams, next to spectral
+    batches; solvers.fv.batched)."""
+    import torch
+    from solvers.spectral import ldc_lib
+    from solvers.spectral.chunks import _words
+    dev = trials[0].device
+    index = torch.cuda.current_device() if dev.index is None else dev.index
+    with torch.cuda.device(dev):
+        starts = _words([s.t["ctrl"] for s in trials])[:, F.CTRL_ITER]
+        with ldc_lib.resident_lock(index):
+            F.batch_enqueue([s.handle for s in trials], k, torch.cuda.current_stream(dev).cuda_stream)
+            ctrl = _words([s.t["ctrl"] for s in trials])        # (synchronises the stream)
+        rings = _words([s.t["rec"][:k] for s in trials])
+    return [(ring[: int(c[F.CTRL_ITER] - start)].copy(), int(c[F.CTRL_DONE]), int(c[F.CTRL_NAN]), int(c[F.CTRL_ITER]))
+            for start, c, ring in zip(starts, ctrl, rings)]
+
+
 class FVSolver(LidDrivenCavitySolver):
     """Collocated finite-volume SIMPLE solver; ``nx`` x ``ny`` cells (8 ... 256 each)."""
 
@@ -183,21 +207,11 @@ class FVSolver(LidDrivenCavitySolver):
         self.t["ctrl"].zero_()
 
     def _advance(self, n_iters: int):
-        import torch
         n_iters = max(1, min(int(n_iters), self.rec_cap))
-        before = int(self.t["ctrl"][F.CTRL_ITER].item())
-        from solvers.spectral import ldc_lib
-        index = torch.cuda.current_device() if self.device.index is None else self.device.index
-        # the work-group holds its CU for the whole chunk: not beside a launch whose work-groups must all be resident
-        # (a lone trial in the launcher's pool of streams, next to spectral batches; solvers.fv.batched)
-        with torch.cuda.device(self.device), ldc_lib.resident_lock(index):
-            F.check(F.lib().ldc_fv_enqueue(self._handle, n_iters, C.c_void_p(self._stream())), "ldc_fv_enqueue")
-            ctrl = self.t["ctrl"].cpu().numpy()            # (synchronises the stream)
-        total = int(ctrl[F.CTRL_ITER])
-        rows = self.t["rec"][: total - before].cpu().numpy().copy()
-        if ctrl[F.CTRL_NAN]:
+        rows, done, nan, total = advance([self], n_iters)[0]
+        if nan:
             F.check(F.lib().ldc_fv_status(self._handle), f"FV trial at iteration {total}")
-        return rows, int(ctrl[F.CTRL_DONE]), total
+        return rows, done, total
 
     def _finalize_fields(self):
         st = self.state()

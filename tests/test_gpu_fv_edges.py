@@ -103,6 +103,44 @@ def test_step_debug_matches_reference_at_odd_sizes(fv, tag):
     s.close()
 
 
+@pytest.mark.parametrize("tag", ["13x17", "37x50"])
+def test_production_and_debug_kernels_leave_the_same_bits(fv, tag):
+    """The production kernel and ldc_fv_step_debug's are two instantiations of one template (csrc/ldc_fv_kernel.inc).
+    One iteration from the seeded state of g15_fv_step through ``_advance(1)`` (production), ``step_debug()`` with
+    every output selected and ``ldc_fv_step_debug`` with ``which = 0`` (debug, all copies and none): the same
+    arithmetic, so u, v, p, mdot, record row 0 and the six ctrl words are equal bit for bit."""
+    import torch
+    from solvers.fv import ldc_fv_lib as F
+    g = np.load(GOLD / "g15_fv_step.npz")
+    m = json.loads((GOLD / "g15_fv_step.json").read_text())[tag]
+    seed = [g[f"{tag}_{k}0"] for k in ("u", "v", "p", "mdot")]
+
+    def production(s):
+        s._advance(1)
+
+    def debug_all(s):
+        assert set(s.step_debug()) == set(F.DBG)
+
+    def debug_none(s):
+        with torch.cuda.device(s.device):
+            F.check(F.lib().ldc_fv_step_debug(s.handle, 0, None, C.c_void_p(s._stream())), "ldc_fv_step_debug")
+            torch.cuda.current_stream(s.device).synchronize()
+
+    left = []
+    for step in (production, debug_all, debug_none):
+        s = fv[0](**_kwargs(m))
+        s.set_state(*seed)
+        step(s)
+        left.append(dict(s.state(), row=s.t["rec"][0].cpu().numpy(), ctrl=s.t["ctrl"][:6].cpu().numpy()))
+        s.close()
+    ref = left[0]
+    assert ref["ctrl"].tolist()[:3] == [0, 1, 0] and ref["ctrl"][5] == 2 and ref["ctrl"][4] > 0
+    assert np.all(np.isfinite(ref["row"][:7])) and ref["row"][0] > 0
+    for name, got in zip(("step_debug, all outputs", "ldc_fv_step_debug, which = 0"), left[1:]):
+        for k in ("u", "v", "p", "mdot", "row", "ctrl"):
+            assert np.array_equal(got[k], ref[k]), (name, k)
+
+
 def test_upwind_trajectories_match_reference_at_odd_sizes(fv):
     """g15_fv_traj, each trial alone and all four as one batch: 1e-8, as test_upwind_trajectories_match_reference."""
     FVSolver, BatchedFVSolver = fv
