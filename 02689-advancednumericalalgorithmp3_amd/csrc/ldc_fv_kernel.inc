@@ -30,32 +30,11 @@
 // Pressure correction: the pinned Neumann Laplacian is solved exactly by fast diagonalisation, four GEMMs on fp64 MFMA
 // (v_mfma_f64_16x16x4_f64) with the eigenvectors the host computed once.
 
-#include "ldc_fv.h"
+// (kFvThreads, kFvWaves, FvVec, FvDesc and struct ldc_fv: ldc_fv_common.inc, shared with ldc_fv_post.hip)
 
 namespace {
 
-constexpr int kFvThreads = 512;
-constexpr int kFvWaves = kFvThreads / 64;
 constexpr int kFvRed = 10;                  // most values one reduction carries
-
-// work vectors (n doubles each), in the order of LDC_FV_NWORK
-enum FvVec {
-  FV_GPX, FV_GPY, FV_AP, FV_AW, FV_AE, FV_AS, FV_AN,
-  FV_XU, FV_XV, FV_RU, FV_RV, FV_RTU, FV_RTV, FV_PU, FV_PV, FV_VU, FV_VV,
-  FV_PHU, FV_PHV, FV_SHU, FV_SHV, FV_TU, FV_TV,
-  FV_C, FV_W1, FV_W2, FV_Y, FV_UP, FV_VP, FV_OMEGA, FV_BU, FV_BV,
-  FV_NVEC
-};
-static_assert(FV_NVEC == LDC_FV_NWORK, "work vectors");
-
-struct FvDesc {
-  int nx, ny, scheme, rec_cap, warmup, maxit;
-  double dx, dy, rho, mu, alpha_uv, alpha_p, lin_tol, tol, lid;
-  const double *ulid, *Qx, *lamx, *Qy, *lamy;
-  double *u, *v, *p, *mdot, *work, *rec;
-  long long *ctrl;
-};
-static_assert(sizeof(FvDesc) <= LDC_FV_DESC_DOUBLES * sizeof(double), "descriptor slot");
 
 struct FvLaunch {
   const FvDesc* d[LDC_FV_LAUNCH_MAX];
@@ -598,13 +577,6 @@ template __global__ void fv_kernel<false>(FvLaunch, FvDebug);
 template __global__ void fv_kernel<true>(FvLaunch, FvDebug);
 
 }  // namespace
-
-struct ldc_fv {
-  FvDesc* dev;              // the descriptor in the tail of the trial's work buffer
-  long long* ctrl;
-  int rec_cap;
-  int device;
-};
 
 namespace {
 

@@ -1,0 +1,258 @@
+// ldc_fv_post.hip -- streamfunction and vortex metrics of finite-volume trials on the device (include/ldc_fv.h,
+// ldc_fv_post_enqueue).  A translation unit of its own, linked into libldc_hip.so beside ldc_kernels.hip: its kernels
+// live in their own code object, so the code object of the solve kernels is the same with and without this file.
+//
+// Reference: base.py:569-760 (streamfunction and vortex extrema), as solvers/fv/solver.py restates them on the host.
+//
+// Mapping: ONE work-group of 512 threads post-processes ONE trial; a launch of B trials is B independent work-groups
+// (no flags, no spins, nobody waits for anybody).  fv_post_kernel reads the trial's descriptor and its post block
+// (both in the slot in the tail of the trial's work buffer) and runs four phases, each ending on the barrier the next
+// one needs:
+//   1. fv_post_vorticity   omega at every cell by ghost cells (the arithmetic of fv_flux_vorticity), the psi ring = 0
+//   2. fv_post_psi         psi on the interior cells: the 5-point Dirichlet problem solved exactly by fast
+//                          diagonalisation with the analytic sine eigenvectors, four GEMMs on v_mfma_f64_16x16x4_f64
+//   3. fv_post_extrema     argmin psi, argmax |omega|, argmax psi inside BR, BL, TL: ties to the lowest cell index
+//   4. the result block    LDC_FV_POST_* of ldc_fv.h
+// The interior is mx x my = (nx - 2) x (ny - 2); with T = tridiag(-1, 2, -1), cx = 1 / dx^2, cy = 1 / dy^2 the host's
+// system is (cx Tx + cy Ty) psi = omega, and T = S diag(lam) S^T with S the sine vectors, so
+//   psi = Sy ((Sy^T F Sx) / (cy lamy[a] + cx lamx[b])) Sx^T,   F = omega on the interior.
+// Scratch: the trial's work vectors FV_W1 and FV_W2 (work vectors carry nothing between launches of the solve kernel,
+// and the trial is not in flight while it is post-processed).
+//
+// The post blocks reach the device through fv_post_stage_kernel: the structs travel as kernel arguments and one thread
+// per trial writes them behind the descriptor.  Stream-ordered, no host synchronisation, no library-owned staging.
+
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+
+#include "ldc_hip.h"
+#include "ldc_fv_common.inc"
+
+namespace {
+
+typedef const __attribute__((address_space(4))) char* kernarg_ptr;
+
+// the post block on the device, at byte kFvPostOffset of the descriptor slot
+struct FvPost {
+  const double *Sx, *lamx, *Sy, *lamy;
+  double *psi, *omega, *result;
+  int ix_lt, ix_gt, jy_lt, jy_gt;
+};
+constexpr int kFvPostOffset = 256;
+static_assert(sizeof(FvDesc) <= kFvPostOffset, "the post block sits behind the descriptor");
+static_assert(kFvPostOffset + sizeof(FvPost) <= LDC_FV_DESC_DOUBLES * sizeof(double), "descriptor slot");
+
+__host__ __device__ inline FvPost* fv_post_slot(const FvDesc* d) {
+  return reinterpret_cast<FvPost*>(reinterpret_cast<char*>(const_cast<FvDesc*>(d)) + kFvPostOffset);
+}
+
+constexpr int kFvStageMax = 40;              // post blocks per staging launch: 40 x (8 + 72) bytes of arguments
+struct FvPostStage {
+  const FvDesc* d[kFvStageMax];
+  FvPost p[kFvStageMax];
+};
+static_assert(sizeof(FvPostStage) <= 3600, "kernel arguments");
+
+__global__ __launch_bounds__(64) void fv_post_stage_kernel(FvPostStage S, int n) {
+  const int q = threadIdx.x;
+  if (q < n) *fv_post_slot(S.d[q]) = S.p[q];
+}
+
+struct FvPostLaunch {
+  const FvDesc* d[LDC_FV_LAUNCH_MAX];
+};
+
+// C[r*ldc + c] = sum_k A(r, k) B(k, c) (M x N), A(r, k) = A[r*sar + k*sak], B(k, c) = B[k*sbk + c*sbc]: fv_gemm of
+// the solve kernel (one wave per 16 x 16 tile, round-robin; operands from L2, zero fill at the edges) with a leading
+// dimension for C and the Dirichlet epilogue.  SCALE: C[a][b] /= cx*lamx[b] + cy*lamy[a]; every mode is kept.
+template <bool SCALE>
+__device__ void fv_post_gemm(const double* A, int sar, int sak, const double* B, int sbk, int sbc, double* Cm, int ldc,
+                             int M, int N, int K, const double* lamx, const double* lamy, double cx, double cy) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int tn = (N + 15) >> 4, tiles = ((M + 15) >> 4) * tn;
+  for (int t = w; t < tiles; t += kFvWaves) {
+    const int r0 = (t / tn) * 16, c0 = (t % tn) * 16;
+    const int ar = r0 + (lane & 15), bc = c0 + (lane & 15), kq = lane >> 4;
+    v4d acc = {0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < K; k0 += 4) {
+      const int k = k0 + kq;
+      const double a = (ar < M && k < K) ? A[ar * sar + k * sak] : 0.0;
+      const double b = (bc < N && k < K) ? B[k * sbk + bc * sbc] : 0.0;
+      acc = MFMA_F64(a, b, acc);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int row = r0 + (lane >> 4) + 4 * q, col = c0 + (lane & 15);
+      if (row < M && col < N) {
+        double val = acc[q];
+        if (SCALE) val = val / (cx * lamx[col] + cy * lamy[row]);
+        Cm[row * ldc + col] = val;
+      }
+    }
+  }
+}
+
+// ---- 1. omega with ghost cells (-f at the walls, 2 lid - u at the lid), psi = 0 on the boundary ring; true if this
+//         thread saw a value that is not finite
+__device__ __forceinline__ bool fv_post_vorticity(const FvDesc& d, const FvPost& P) {
+  const int nx = d.nx, ny = d.ny, n = nx * ny;
+  const double dx = d.dx, dy = d.dy, lid = d.lid;
+  const double *u = d.u, *v = d.v;
+  bool bad = false;
+  for (int c = threadIdx.x; c < n; c += kFvThreads) {
+    const int i = c % nx, j = c / nx;
+    const double vE = i < nx - 1 ? v[c + 1] : -v[c], vW = i > 0 ? v[c - 1] : -v[c];
+    const double uN = j < ny - 1 ? u[c + nx] : 2 * lid - u[c], uS = j > 0 ? u[c - nx] : -u[c];
+    const double wc = (vE - vW) / (2 * dx) - (uN - uS) / (2 * dy);
+    P.omega[c] = wc;
+    bad |= !(fabs(wc) <= 1.7976931348623157e308);
+    if (i == 0 || i == nx - 1 || j == 0 || j == ny - 1) P.psi[c] = 0.0;
+  }
+  __syncthreads();
+  return bad;
+}
+
+// ---- 2. psi on the interior: W1 = Sy^T F, W2 = W1 Sx / Lambda, W1 = Sy W2, psi = W1 Sx^T
+__device__ __forceinline__ void fv_post_psi(const FvDesc& d, const FvPost& P) {
+  const int nx = d.nx, mx = d.nx - 2, my = d.ny - 2, n = d.nx * d.ny;
+  const double cx = 1.0 / (d.dx * d.dx), cy = 1.0 / (d.dy * d.dy);
+  double *W1 = d.work + FV_W1 * n, *W2 = d.work + FV_W2 * n;
+  const double* F = P.omega + nx + 1;
+  fv_post_gemm<false>(P.Sy, 1, my, F, nx, 1, W1, mx, my, mx, my, nullptr, nullptr, 0, 0);
+  __syncthreads();
+  fv_post_gemm<true>(W1, mx, 1, P.Sx, mx, 1, W2, mx, my, mx, mx, P.lamx, P.lamy, cx, cy);
+  __syncthreads();
+  fv_post_gemm<false>(P.Sy, my, 1, W2, mx, 1, W1, mx, my, mx, my, nullptr, nullptr, 0, 0);
+  __syncthreads();
+  fv_post_gemm<false>(W1, mx, 1, P.Sx, 1, mx, P.psi + nx + 1, nx, my, mx, mx, nullptr, nullptr, 0, 0);
+  __syncthreads();
+}
+
+// an extremum candidate: the largest key, among equal keys the lowest cell index
+struct FvBest {
+  double key;
+  int idx;
+  __device__ __forceinline__ void scan(double k, int c) { if (k > key) { key = k; idx = c; } }     // increasing c
+  __device__ __forceinline__ void merge(double k, int c) { if (k > key || (k == key && c < idx)) { key = k; idx = c; } }
+};
+constexpr int kFvPostBest = 5;               // -psi, |omega|, psi in BR, BL, TL
+enum { FVP_PSI_MIN, FVP_OMEGA_MAX, FVP_BR, FVP_BL, FVP_TL };
+
+// ---- 3. the five extrema over the work-group, in a fixed order; every thread gets the same winners
+__device__ __forceinline__ bool fv_post_extrema(const FvDesc& d, const FvPost& P, FvBest (&best)[kFvPostBest],
+                                                double (*lkey)[kFvPostBest], int (*lidx)[kFvPostBest]) {
+  const int nx = d.nx, n = d.nx * d.ny;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  bool bad = false;
+#pragma unroll
+  for (int q = 0; q < kFvPostBest; ++q) { best[q].key = -HUGE_VAL; best[q].idx = INT_MAX; }
+  for (int c = threadIdx.x; c < n; c += kFvThreads) {
+    const int i = c % nx, j = c / nx;
+    const double ps = P.psi[c], om = P.omega[c];
+    bad |= !(fabs(ps) <= 1.7976931348623157e308);
+    best[FVP_PSI_MIN].scan(-ps, c);
+    best[FVP_OMEGA_MAX].scan(fabs(om), c);
+    const bool left = i < P.ix_lt, right = i >= P.ix_gt, low = j < P.jy_lt, high = j >= P.jy_gt;
+    if (right && low) best[FVP_BR].scan(ps, c);
+    if (left && low) best[FVP_BL].scan(ps, c);
+    if (left && high) best[FVP_TL].scan(ps, c);
+  }
+#pragma unroll
+  for (int q = 0; q < kFvPostBest; ++q) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const double k = __shfl_xor(best[q].key, off);
+      const int c = __shfl_xor(best[q].idx, off);
+      best[q].merge(k, c);
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < kFvPostBest; ++q) { lkey[w][q] = best[q].key; lidx[w][q] = best[q].idx; }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < kFvPostBest; ++q) {
+    best[q].key = lkey[0][q]; best[q].idx = lidx[0][q];
+    for (int v = 1; v < kFvWaves; ++v) best[q].merge(lkey[v][q], lidx[v][q]);
+  }
+  return bad;
+}
+
+__global__ __launch_bounds__(kFvThreads) void fv_post_kernel(FvPostLaunch) {
+  __shared__ double lkey[kFvWaves][kFvPostBest];
+  __shared__ int lidx[kFvWaves][kFvPostBest];
+  // (the descriptor pointer straight from the kernarg segment, as fv_kernel reads it)
+  typedef const FvDesc* FvDescPtr;
+  const FvDesc& d = **(const __attribute__((address_space(4))) FvDescPtr*)((kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr() +
+                                                                           __builtin_offsetof(FvPostLaunch, d) + blockIdx.x * sizeof(FvDescPtr));
+  const FvPost P = *fv_post_slot(&d);        // (by value: nothing writes the block while the kernel runs)
+  bool bad = fv_post_vorticity(d, P);
+  fv_post_psi(d, P);
+  FvBest best[kFvPostBest];
+  bad |= fv_post_extrema(d, P, best, lkey, lidx);
+  const int any_bad = __syncthreads_or(bad ? 1 : 0);
+  if (threadIdx.x == 0) {
+    double* r = P.result;
+    const int cmin = best[FVP_PSI_MIN].idx, cmax = best[FVP_OMEGA_MAX].idx;
+    const int n = d.nx * d.ny;
+    const bool ok = cmin < n && cmax < n;      // (a NaN field leaves a candidate empty; the flag below says so)
+    r[LDC_FV_POST_PSI_MIN] = ok ? P.psi[cmin] : 0.0;
+    r[LDC_FV_POST_OMEGA_CENTER] = ok ? P.omega[cmin] : 0.0;
+    r[LDC_FV_POST_OMEGA_MAX] = ok ? P.omega[cmax] : 0.0;
+    r[LDC_FV_POST_PSI_MIN_CELL] = ok ? cmin : -1;
+    r[LDC_FV_POST_OMEGA_MAX_CELL] = ok ? cmax : -1;
+    for (int q = 0; q < 3; ++q) {              // BR, BL, TL; an empty region: value -inf, cell -1
+      const FvBest& b = best[FVP_BR + q];
+      r[LDC_FV_POST_PSI_BR + q] = b.key;
+      r[LDC_FV_POST_PSI_BR_CELL + q] = b.idx < n ? b.idx : -1;
+    }
+    r[LDC_FV_POST_NONFINITE] = (any_bad || !ok) ? 1.0 : 0.0;
+    for (int q = LDC_FV_POST_NONFINITE + 1; q < LDC_FV_POST_RESULT_LEN; ++q) r[q] = 0.0;
+  }
+}
+
+inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+}  // namespace
+
+extern "C" {
+
+int ldc_fv_post_enqueue(ldc_fv* const* hs, const struct ldc_fv_post* posts, int n, void* stream) {
+  if (!hs || !posts || n < 1) return LDC_E_ARG;
+  for (int q = 0; q < n; ++q) {
+    if (!hs[q]) return LDC_E_STATE;
+    const struct ldc_fv_post& p = posts[q];
+    const void* req[] = {p.Sx, p.lamx, p.Sy, p.lamy, p.psi, p.omega, p.result};
+    for (const void* x : req) if (!x) return LDC_E_ARG;
+    if (p.ix_lt < 0 || p.ix_gt < 0 || p.jy_lt < 0 || p.jy_gt < 0) return LDC_E_ARG;
+  }
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
+  for (int q = 0; q < n; ++q) if (hs[q]->device != dev) return LDC_E_STATE;
+  for (int lo = 0; lo < n; lo += kFvStageMax) {
+    FvPostStage S;
+    const int b = n - lo < kFvStageMax ? n - lo : kFvStageMax;
+    for (int q = 0; q < kFvStageMax; ++q) {
+      const int t = lo + (q < b ? q : 0);
+      const struct ldc_fv_post& p = posts[t];
+      S.d[q] = hs[t]->dev;
+      S.p[q] = FvPost{p.Sx, p.lamx, p.Sy, p.lamy, p.psi, p.omega, p.result, p.ix_lt, p.ix_gt, p.jy_lt, p.jy_gt};
+    }
+    hipLaunchKernelGGL(fv_post_stage_kernel, dim3(1), dim3(64), 0, as_stream(stream), S, b);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  for (int lo = 0; lo < n; lo += LDC_FV_LAUNCH_MAX) {
+    FvPostLaunch L;
+    const int b = n - lo < LDC_FV_LAUNCH_MAX ? n - lo : LDC_FV_LAUNCH_MAX;
+    for (int q = 0; q < LDC_FV_LAUNCH_MAX; ++q) L.d[q] = q < b ? hs[lo + q]->dev : nullptr;
+    hipLaunchKernelGGL(fv_post_kernel, dim3(b), dim3(kFvThreads), 0, as_stream(stream), L);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -39,12 +39,9 @@
 #include <vector>
 
 #include "ldc_hip.h"
+#include "ldc_fv_common.inc"      // v4d, MFMA_F64 and the finite-volume types shared with ldc_fv_post.hip
 
 namespace {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-#define MFMA_F64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
 // Timing switches and cycle stamps (ldc_debug_ablate / ldc_debug_stamps) exist only in the INSTRUMENTED build of this
 // file (-DLDC_TIMING -> lib/libldc_hip_timing.so, what tools/kbench.py, kstamps.py, pstamps.py and ab_masks.py load).  In the

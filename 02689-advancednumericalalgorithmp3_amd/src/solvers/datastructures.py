@@ -9,6 +9,7 @@ dataclass defaults (e.g. ``CFL: 1.5`` in conf/solver/spectral/sg.yaml).
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass, field, fields
 from typing import List, Optional
 
@@ -92,9 +93,12 @@ class FVParameters(Parameters):
     # --- additions of the MI355X build (optional, defaults keep reference behaviour) ---
     device: str = "cuda:0"
     check_every: int = 2048        # iterations enqueued between host polls of the latch
+    # streamfunction and vortex metrics after a solve: "host" (SciPy sparse solve, one trial after another) or "device"
+    # (ldc_fv_post_enqueue, all trials of a batch in one launch); not given: LDC_FV_VORTEX_METRICS may choose
+    vortex_metrics: str = field(default_factory=lambda: os.environ.get("LDC_FV_VORTEX_METRICS", "host"))
 
     def to_mlflow(self) -> dict:
-        skip = {"device", "check_every"}
+        skip = {"device", "check_every", "vortex_metrics"}
         return {k: _mlflow_scalar(v) for k, v in self.as_dict().items() if k not in skip}
 
 

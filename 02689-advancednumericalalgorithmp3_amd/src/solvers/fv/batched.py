@@ -23,7 +23,7 @@ import numpy as np
 
 from ..base import WARMUP_ITERATIONS
 from . import ldc_fv_lib as F
-from .solver import FVSolver, advance
+from .solver import FVSolver, advance, postprocess
 
 log = logging.getLogger(__name__)
 
@@ -124,6 +124,10 @@ class BatchedFVSolver:
         work = [0 if q in self.errors else total * s.nx * s.ny
                 for q, (s, (_, _, total, _)) in enumerate(zip(self.solvers, out))]
         work_all = max(1, sum(work))
+        # the device path of the vortex metrics: every finished trial that asks for it in one go (_store_results below
+        # finds its result block); a trial in `errors` is left alone
+        postprocess([s for q, s in enumerate(self.solvers)
+                     if q not in self.errors and s.params.vortex_metrics == "device"])
         for q, (s, (done, _, total, hist)) in enumerate(zip(self.solvers, out)):
             if q in self.errors:
                 continue

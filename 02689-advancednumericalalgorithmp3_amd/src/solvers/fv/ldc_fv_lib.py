@@ -9,13 +9,17 @@ import ctypes as C
 
 from solvers.spectral import ldc_lib as _L
 
-VERSION = 1
+VERSION = 2
 MIN_N, MAX_N = 8, 256
 REC_LEN, CTRL_LEN = 8, 8
 NWORK, DESC_DOUBLES = 32, 64
 LAUNCH_MAX = 256
 E_NAN = -5
 CTRL_DONE, CTRL_ITER, CTRL_NAN, CTRL_GIVEUP, CTRL_LIN_ITERS, CTRL_SOLVES = range(6)
+# slots of a result block of ldc_fv_post_enqueue (LDC_FV_POST_*)
+(POST_PSI_MIN, POST_OMEGA_CENTER, POST_OMEGA_MAX, POST_PSI_BR, POST_PSI_BL, POST_PSI_TL, POST_PSI_MIN_CELL,
+ POST_OMEGA_MAX_CELL, POST_PSI_BR_CELL, POST_PSI_BL_CELL, POST_PSI_TL_CELL, POST_NONFINITE) = range(12)
+POST_RESULT_LEN = 16
 DBG = ("grad_p", "diag", "b", "u_star", "v_star", "mdot_star", "rhs_p", "p_prime", "u_prime", "v_prime", "mdot")
 
 _dp = C.c_void_p
@@ -30,9 +34,18 @@ class Problem(C.Structure):
     )
 
 
+class Post(C.Structure):
+    """Mirror of ``struct ldc_fv_post`` -- keep field order in sync with the header."""
+    _fields_ = (
+        [(n, _dp) for n in ("Sx", "lamx", "Sy", "lamy")]
+        + [(n, C.c_int32) for n in ("ix_lt", "ix_gt", "jy_lt", "jy_gt")]
+        + [(n, _dp) for n in ("psi", "omega", "result")]
+    )
+
+
 # every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
-           "ldc_fv_status", "ldc_fv_step_debug")
+           "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_post_enqueue")
 
 _bound = None
 
@@ -57,6 +70,7 @@ def lib() -> C.CDLL:
         L.ldc_fv_batch_enqueue.argtypes = [C.POINTER(_dp), C.c_int, C.c_int, _dp]
         L.ldc_fv_status.argtypes = [_dp]
         L.ldc_fv_step_debug.argtypes = [_dp, C.c_int, C.POINTER(_dp), _dp]
+        L.ldc_fv_post_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(Post), C.c_int, _dp]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -73,3 +87,10 @@ def batch_enqueue(handles, n_iters: int, stream) -> None:
     """One launch (per LAUNCH_MAX trials) advancing every handle by up to n_iters iterations."""
     arr = (_dp * len(handles))(*[h.value if isinstance(h, _dp) else h for h in handles])
     check(lib().ldc_fv_batch_enqueue(arr, len(handles), int(n_iters), _dp(stream)), "ldc_fv_batch_enqueue")
+
+
+def post_enqueue(handles, posts, stream) -> None:
+    """omega, psi and the result block of every handle (``posts``: one ``Post`` each), one launch per LAUNCH_MAX."""
+    arr = (_dp * len(handles))(*[h.value if isinstance(h, _dp) else h for h in handles])
+    blocks = (Post * len(posts))(*posts)
+    check(lib().ldc_fv_post_enqueue(arr, blocks, len(handles), _dp(stream)), "ldc_fv_post_enqueue")

@@ -4,7 +4,9 @@ Contract: reference src/solvers/fv/solver.py (the iteration, :170-257), base.py:
 :359-450 (E, Z, P), :569-760 (streamfunction and vortex extrema).  Every SIMPLE iteration runs in the HIP kernel of
 include/ldc_fv.h -- one work-group per trial, ``check_every`` iterations per launch -- and the host only reads the
 record rows and the latch.  The host computes, once per trial, the eigenvectors of the 1-D Neumann Laplacians that the
-kernel's exact pressure-correction solve uses, and, once per solve, the vortex metrics.
+kernel's exact pressure-correction solve uses, and, once per solve, the vortex metrics: on the host with SciPy's sparse
+solve (``vortex_metrics="host"``, the default) or on the device (``"device"``: ``ldc_fv_post_enqueue``, one work-group
+per trial, the same quantities by the same rules).
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ from . import ldc_fv_lib as F
 log = logging.getLogger(__name__)
 
 SCHEMES = {"Upwind": 0, "TVD": 1}
+VORTEX_METRICS = ("host", "device")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
 
 
@@ -49,6 +52,73 @@ def neumann_eig(n: int):
     lam, Q = np.linalg.eigh(T)
     assert abs(lam[0]) < 1e-10 and lam[1] > 1e-6, "Neumann Laplacian: one zero mode, first"
     return lam, Q
+
+
+_sine_cache = {}
+
+
+def sine_eig_host(m: int):
+    """(eigenvalues ascending, eigenvectors as columns) of the m x m Dirichlet second difference tridiag(-1, 2, -1),
+    analytic: S[k, j] = sqrt(2 / (m + 1)) sin(pi (k + 1)(j + 1) / (m + 1)), lam[k] = 2 - 2 cos(pi (k + 1) / (m + 1))."""
+    k = np.arange(1, m + 1, dtype=np.float64)
+    S = np.sqrt(2.0 / (m + 1)) * np.sin(np.pi * np.outer(k, k) / (m + 1))
+    return 2.0 - 2.0 * np.cos(np.pi * k / (m + 1)), S
+
+
+def sine_eig(m: int, device=None):
+    """``sine_eig_host(m)``; with a ``device`` as float64 tensors there, cached per (m, device): trials of equal size
+    share one upload."""
+    if device is None:
+        return sine_eig_host(m)
+    import torch
+    device = torch.device(device)
+    key = (int(m), device.type, torch.cuda.current_device() if device.index is None else device.index)
+    if key not in _sine_cache:
+        lam, S = sine_eig_host(m)
+        _sine_cache[key] = (torch.tensor(lam, dtype=torch.float64, device=device),
+                            torch.tensor(S, dtype=torch.float64, device=device).contiguous())
+    return _sine_cache[key]
+
+
+def mask_bounds(xs, ys):
+    """The corner regions of ``compute_vortex_metrics`` as index bounds on the sorted cell-centre coordinates:
+    xs < 0.5 is i < ix_lt, xs > 0.5 is i >= ix_gt, likewise ys (absolute coordinates, as the reference's masks)."""
+    return (int(np.count_nonzero(xs < 0.5)), int(xs.size - np.count_nonzero(xs > 0.5)),
+            int(np.count_nonzero(ys < 0.5)), int(ys.size - np.count_nonzero(ys > 0.5)))
+
+
+def postprocess(trials):
+    """omega, psi and the vortex extrema of ``trials`` (FVSolvers on one device, none in flight) on the device: one
+    launch per 256 trials, then ONE copy of all result blocks.  ``psi`` and ``omega`` stay on the device as
+    ``t["psi"]``, ``t["omega"]``; every trial keeps its row of the result blocks for ``compute_vortex_metrics``."""
+    import torch
+    from solvers.spectral import ldc_lib
+    if not trials:
+        return
+    dev = trials[0].device
+    index = torch.cuda.current_device() if dev.index is None else dev.index
+    with torch.cuda.device(dev):
+        results = torch.zeros((len(trials), F.POST_RESULT_LEN), dtype=torch.float64, device=dev)
+        posts = []
+        for q, s in enumerate(trials):
+            if (torch.cuda.current_device() if s.device.index is None else s.device.index) != index:
+                raise ValueError("postprocess: all trials must be on one device")
+            lamx, Sx = sine_eig(s.nx - 2, dev)
+            lamy, Sy = sine_eig(s.ny - 2, dev)
+            for name in ("psi", "omega"):
+                if name not in s.t:
+                    s.t[name] = torch.zeros(s.n_cells, dtype=torch.float64, device=dev)
+            ix_lt, ix_gt, jy_lt, jy_gt = s._mask_bounds
+            posts.append(F.Post(Sx=Sx.data_ptr(), lamx=lamx.data_ptr(), Sy=Sy.data_ptr(), lamy=lamy.data_ptr(),
+                                ix_lt=ix_lt, ix_gt=ix_gt, jy_lt=jy_lt, jy_gt=jy_gt, psi=s.t["psi"].data_ptr(),
+                                omega=s.t["omega"].data_ptr(), result=results[q].data_ptr()))
+        with ldc_lib.resident_lock(index):
+            for lo in range(0, len(trials), F.LAUNCH_MAX):
+                F.post_enqueue([s.handle for s in trials[lo: lo + F.LAUNCH_MAX]], posts[lo: lo + F.LAUNCH_MAX],
+                               torch.cuda.current_stream(dev).cuda_stream)
+            rows = results.cpu().numpy()          # (synchronises the stream)
+    for s, row in zip(trials, rows):
+        s._post = row.copy()
 
 
 def advance(trials, k):
@@ -88,6 +158,8 @@ class FVSolver(LidDrivenCavitySolver):
             raise ValueError(f"convection_scheme={p.convection_scheme!r}: 'Upwind' or 'TVD'")
         if p.convection_scheme == "TVD" and p.limiter != "MUSCL":
             raise ValueError(f"limiter={p.limiter!r}: the TVD scheme of the reference is MUSCL")
+        if p.vortex_metrics not in VORTEX_METRICS:
+            raise ValueError(f"vortex_metrics={p.vortex_metrics!r}: 'host' or 'device'")
         nx, ny = int(p.nx), int(p.ny)
         if not (F.MIN_N <= nx <= F.MAX_N and F.MIN_N <= ny <= F.MAX_N):
             raise ValueError(f"nx, ny = {nx}, {ny}: the FV kernel takes {F.MIN_N} ... {F.MAX_N} cells per axis")
@@ -98,6 +170,8 @@ class FVSolver(LidDrivenCavitySolver):
         xc, yc = (np.arange(nx) + 0.5) * self.dx_min, (np.arange(ny) + 0.5) * self.dy_min
         X, Y = np.meshgrid(xc, yc)
         self._init_fields(x=X.ravel(), y=Y.ravel())
+        self._mask_bounds = mask_bounds(np.sort(np.unique(self.fields.x)), np.sort(np.unique(self.fields.y)))
+        self._post = None                        # the trial's result block of the last postprocess()
 
         import torch
         from solvers.spectral import ldc_lib
@@ -175,6 +249,7 @@ class FVSolver(LidDrivenCavitySolver):
         for name, val in (("u", u), ("v", v), ("p", p), ("mdot", mdot)):
             self.t[name].copy_(torch.as_tensor(np.asarray(val, dtype=np.float64).ravel()))
         self.t["ctrl"].zero_()
+        self._post = None
 
     def state(self) -> dict:
         return {k: self.t[k].cpu().numpy().copy() for k in ("u", "v", "p", "mdot")}
@@ -205,6 +280,7 @@ class FVSolver(LidDrivenCavitySolver):
         ``solve()`` counts from 0 on the current state, with its own warm-up, history and iteration count."""
         self._make_handle(tolerance)
         self.t["ctrl"].zero_()
+        self._post = None
 
     def _advance(self, n_iters: int):
         n_iters = max(1, min(int(n_iters), self.rec_cap))
@@ -254,6 +330,8 @@ class FVSolver(LidDrivenCavitySolver):
         return psi
 
     def compute_vortex_metrics(self) -> dict:
+        if self.params.vortex_metrics == "device":
+            return self._device_vortex_metrics()
         omega = self._vorticity()
         psi = self._streamfunction(omega)
         xs, ys = np.sort(np.unique(self.fields.x)), np.sort(np.unique(self.fields.y))
@@ -272,6 +350,43 @@ class FVSolver(LidDrivenCavitySolver):
             else:
                 out.update({f"psi_{name}": 0.0, f"psi_{name}_x": 0.0, f"psi_{name}_y": 0.0})
         return out
+
+    # ---- the same on the device (ldc_fv_post_enqueue) ------------------------------------------------------
+    def _device_vortex_metrics(self) -> dict:
+        """The host branch's dict from the trial's result block: the block ``postprocess`` left (a batch post-processes
+        its trials together), or one of a launch of its own."""
+        if self._post is None:
+            postprocess([self])
+        r, self._post = self._post, None
+        if r[F.POST_NONFINITE] != 0:
+            raise FloatingPointError("vortex metrics: omega or psi is not finite")
+        xs, ys = np.sort(np.unique(self.fields.x)), np.sort(np.unique(self.fields.y))
+        xy = lambda c: (float(xs[int(c) % self.nx]), float(ys[int(c) // self.nx]))        # noqa: E731
+        (x0, y0), (x1, y1) = xy(r[F.POST_PSI_MIN_CELL]), xy(r[F.POST_OMEGA_MAX_CELL])
+        out = dict(psi_min=float(r[F.POST_PSI_MIN]), psi_min_x=x0, psi_min_y=y0,
+                   omega_center=float(r[F.POST_OMEGA_CENTER]), omega_max=float(r[F.POST_OMEGA_MAX]),
+                   omega_max_x=x1, omega_max_y=y1)
+        for q, name in enumerate(("BR", "BL", "TL")):
+            val, cell = float(r[F.POST_PSI_BR + q]), r[F.POST_PSI_BR_CELL + q]
+            if val > 0:
+                x, y = xy(cell)
+                out.update({f"psi_{name}": val, f"psi_{name}_x": x, f"psi_{name}_y": y})
+            else:
+                out.update({f"psi_{name}": 0.0, f"psi_{name}_x": 0.0, f"psi_{name}_y": 0.0})
+        return out
+
+    def _post_field(self, name) -> np.ndarray:
+        postprocess([self])
+        self._post = None
+        return self.t[name].cpu().numpy().reshape(self.shape_full).copy()
+
+    def streamfunction(self) -> np.ndarray:
+        """psi (ny, nx) of the current device state, computed on the device."""
+        return self._post_field("psi")
+
+    def vorticity(self) -> np.ndarray:
+        """omega (ny, nx) of the current device state, computed on the device."""
+        return self._post_field("omega")
 
     # ---- Ghia centrelines: linear interpolation, as the reference plots FV fields ----------------------------
     def ghia_error(self) -> dict:

@@ -1,4 +1,4 @@
-/* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc).
+/* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -21,6 +21,21 @@
  *    running totals.  The state (u, v, p, mdot) is not touched by that: a new solve continues from the fields.
  *    Between the enqueues of ONE solve leave ctrl alone.
  *  - functions return 0, a negative LDC_E_* code of ldc_hip.h, LDC_FV_E_NAN, or a positive hipError_t.
+ *
+ * Post-processing (version 2, csrc/ldc_fv_post.hip): the vorticity, the streamfunction and the vortex extrema of a
+ * trial that is NOT in flight, one work-group per trial, as the solver's host code computes them (base.py:569-760):
+ *  - omega (ny x nx) by ghost cells from u and v: -f at the walls, 2 lid_velocity - u at the lid;
+ *  - psi (ny x nx): the 5-point Dirichlet problem (cx Tx + cy Ty) psi = omega on the (nx-2) x (ny-2) interior cells,
+ *    T = tridiag(-1, 2, -1), cx = 1/dx^2, cy = 1/dy^2, solved exactly with the sine vectors
+ *    S_m[k][j] = sqrt(2/(m+1)) sin(pi (k+1)(j+1)/(m+1)), lam_m[k] = 2 - 2 cos(pi (k+1)/(m+1)), m = nx-2 and ny-2
+ *    (S row-major m x m; symmetric); the boundary ring of psi is exactly 0.0;
+ *  - the extrema are (value, cell) pairs, ties to the LOWEST cell c = j*nx + i (numpy.argmin / argmax); the three
+ *    corner regions are BR: i >= ix_gt and j < jy_lt, BL: i < ix_lt and j < jy_lt, TL: i < ix_lt and j >= jy_gt.
+ *    The caller derives the four bounds from its own cell-centre coordinates (x < 0.5: i < ix_lt; x > 0.5:
+ *    i >= ix_gt; likewise y), so the kernel compares no coordinates;
+ *  - result: LDC_FV_POST_RESULT_LEN doubles, the LDC_FV_POST_* slots below; cells are stored as doubles, -1 = none;
+ *  - scratch: two of the trial's work vectors and 72 bytes of the descriptor slot behind the descriptor.  The state,
+ *    rec and ctrl are only read, so a solve goes on afterwards as if nothing had happened.
  */
 #ifndef LDC_FV_H
 #define LDC_FV_H
@@ -31,7 +46,7 @@
 extern "C" {
 #endif
 
-#define LDC_FV_VERSION 1
+#define LDC_FV_VERSION 2
 #define LDC_FV_MIN_N 8
 #define LDC_FV_MAX_N 256
 #define LDC_FV_REC_LEN 8
@@ -77,6 +92,30 @@ struct ldc_fv_problem {
   int64_t *ctrl;                  /* LDC_FV_CTRL_LEN */
 };
 
+/* slots of a result block of ldc_fv_post_enqueue */
+#define LDC_FV_POST_PSI_MIN 0          /* min psi */
+#define LDC_FV_POST_OMEGA_CENTER 1     /* omega at the cell of min psi */
+#define LDC_FV_POST_OMEGA_MAX 2        /* the signed omega at the cell of max |omega| */
+#define LDC_FV_POST_PSI_BR 3           /* max psi inside BR, BL, TL (-inf for a region without cells); the caller */
+#define LDC_FV_POST_PSI_BL 4           /* keeps one that is > 0 */
+#define LDC_FV_POST_PSI_TL 5
+#define LDC_FV_POST_PSI_MIN_CELL 6     /* their cells c = j*nx + i, in the same order */
+#define LDC_FV_POST_OMEGA_MAX_CELL 7
+#define LDC_FV_POST_PSI_BR_CELL 8
+#define LDC_FV_POST_PSI_BL_CELL 9
+#define LDC_FV_POST_PSI_TL_CELL 10
+#define LDC_FV_POST_NONFINITE 11       /* non-zero: some omega or psi is not finite, the other slots mean nothing */
+#define LDC_FV_POST_RESULT_LEN 16      /* (the rest is written as 0) */
+
+struct ldc_fv_post {
+  const double *Sx, *lamx;        /* sine eigenvectors (nx-2)^2 and eigenvalues (nx-2) */
+  const double *Sy, *lamy;        /* the same for ny-2 */
+  int32_t ix_lt, ix_gt;           /* cells with x < 0.5: i < ix_lt; with x > 0.5: i >= ix_gt */
+  int32_t jy_lt, jy_gt;           /* cells with y < 0.5: j < jy_lt; with y > 0.5: j >= jy_gt */
+  double *psi, *omega;            /* out: n each */
+  double *result;                 /* out: LDC_FV_POST_RESULT_LEN */
+};
+
 typedef struct ldc_fv ldc_fv;
 
 int ldc_fv_version(void);
@@ -93,6 +132,9 @@ int ldc_fv_batch_enqueue(ldc_fv *const *hs, int n, int n_iters, void *stream);
 int ldc_fv_status(ldc_fv *h);
 /* One iteration, copying the intermediates selected by `which` into out[k] (device pointers). */
 int ldc_fv_step_debug(ldc_fv *h, int which, double *const *out, void *stream);
+/* omega, psi and the result block of n trials (any sizes, one device), one work-group each; trial q takes posts[q]. */
+/* Validation comes first and needs no device.  The trials must not be in flight on another stream.                  */
+int ldc_fv_post_enqueue(ldc_fv *const *hs, const struct ldc_fv_post *posts, int n, void *stream);
 
 #ifdef __cplusplus
 }

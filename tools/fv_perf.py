@@ -11,6 +11,12 @@ with the wall time of the process, the launcher's own time inside the solves and
 ``--main`` points at the main.py of another checkout (a worktree of the parent commit, built there) for an A/B on one
 card; ``--max-batch 1`` runs this checkout's trials one by one.
 
+``--post`` times the post-processing of a finished batch (streamfunction and vortex metrics, copies included): 256 trials
+at N = 64 and 64 at N = 128, each after ``--iters`` iterations from rest, on the host path (SciPy's sparse solve, one
+trial after another) and on the device path (ldc_fv_post_enqueue), in one process, alternated twice.
+
+    python tools/fv_perf.py --post [--iters 200] [--post-cases 256x64,64x128]
+
     python tools/fv_perf.py --sweep [--label head] [--main /path/to/other/checkout/02689-.../main.py] [--max-batch 1]
 """
 import argparse
@@ -54,8 +60,54 @@ def sweep(a):
                           per_trial=trials)), flush=True)
 
 
+def post(a):
+    import numpy as np
+    import torch
+    import __graft_entry__ as g
+    g.build()
+    from solvers.fv.batched import BatchedFVSolver
+    from solvers.fv.solver import postprocess
+    kw = dict(name="fv", convection_scheme="TVD", alpha_uv=0.4, alpha_p=0.2, linear_solver_tol=1e-9, tolerance=1e-30,
+              check_every=a.iters, max_iterations=a.iters)
+    for case in a.post_cases.split(","):
+        b, n = (int(x) for x in case.split("x"))
+        batch = BatchedFVSolver([dict(kw, nx=n, ny=n, Re=100.0 + 900.0 * q / max(1, b - 1)) for q in range(b)])
+        for s in batch.solvers:
+            s._begin(1e-30)
+        batch._step(list(range(b)), a.iters)
+        for s in batch.solvers:
+            s._finalize_fields()
+
+        def run(mode):
+            for s in batch.solvers:
+                s.params.vortex_metrics = mode
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if mode == "device":
+                postprocess(batch.solvers)
+            out = [s.compute_vortex_metrics() for s in batch.solvers]
+            return time.perf_counter() - t0, out
+        run("device")                                         # (first launch, sine tables, output tensors)
+        times = {"host": [], "device": []}
+        for _ in range(2):
+            for mode in ("host", "device"):
+                dt, out = run(mode)
+                times[mode].append(dt)
+                times[mode + "_psi_min"] = float(np.mean([m["psi_min"] for m in out]))
+        host, dev = min(times["host"]), min(times["device"])
+        print(json.dumps(dict(what="post", N=n, trials=b, iterations=a.iters,
+                              host_seconds=[round(t, 4) for t in times["host"]],
+                              device_seconds=[round(t, 5) for t in times["device"]],
+                              host_ms_per_trial=round(host / b * 1e3, 3), device_ms_per_trial=round(dev / b * 1e3, 4),
+                              host_over_device=round(host / dev, 1),
+                              mean_psi_min=dict(host=times["host_psi_min"], device=times["device_psi_min"]))), flush=True)
+        batch.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--post", action="store_true", help="time host and device post-processing of finished batches")
+    ap.add_argument("--post-cases", default="256x64,64x128", help="trials x N, comma-separated")
     ap.add_argument("--sweep", action="store_true", help="time the N = 64, 128 x Re = 100, 400, 1000 sweep through main.py")
     ap.add_argument("--label", default="head")
     ap.add_argument("--main", default=None, help="main.py of another (built) checkout")
@@ -69,6 +121,8 @@ def main():
     a = ap.parse_args()
     if a.sweep:
         return sweep(a)
+    if a.post:
+        return post(a)
     import torch
     import __graft_entry__ as g
     g.build()
