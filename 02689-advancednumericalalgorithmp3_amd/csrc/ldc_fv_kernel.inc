@@ -634,6 +634,7 @@ int ldc_fv_create(const struct ldc_fv_problem* pr, ldc_fv** out) {
   ldc_fv* s = new (std::nothrow) ldc_fv;
   if (!s) return LDC_E_STATE;
   s->dev = slot; s->ctrl = h.ctrl; s->rec_cap = pr->rec_cap; s->device = dev;
+  s->nx = pr->nx; s->ny = pr->ny; s->dx = pr->dx; s->dy = pr->dy;
   *out = s;
   return 0;
 }

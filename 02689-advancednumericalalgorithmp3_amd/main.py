@@ -65,6 +65,8 @@ def make_record(cfg: dict, solver, out_dir: Path, t0: float) -> dict:
                validation_table=solver.validation_table(), total_seconds=time.perf_counter() - t0)
     if hasattr(solver, "kernel_mode"):          # which of the library's kernels advanced this trial (include/ldc_hip.h: 0, 3, 4, 5)
         rec["kernel_mode"] = int(solver.kernel_mode)
+    if hasattr(solver, "level_iterations"):     # a sequenced finite-volume solve: the iterations of every level, coarse -> fine
+        rec["level_iterations"] = [int(k) for k in solver.level_iterations]
     if int(cfg["Re"]) in V.GHIA_RE:
         rec["ghia"] = solver.ghia_error()
     m = solver.metrics
@@ -137,16 +139,19 @@ def one_wide_batch(cfgs: list, n_cus: int, knob: str = None) -> bool:
 
 
 SG, FSG, FV = "solvers.spectral.sg.SGSolver", "solvers.spectral.fsg.FSGSolver", "solvers.fv.solver.FVSolver"
+FV_FSG = "solvers.fv.fsg.FVFSGSolver"        # coarse-to-fine sequences of finite-volume trials (solver=fv/fsg)
+FV_TARGETS = (FV, FV_FSG)
 FV_LAUNCH_MAX = 256        # LDC_FV_LAUNCH_MAX (include/ldc_fv.h): one finite-volume work-group per CU of an MI355X
 
 
 def batch_key(cfg: dict) -> tuple:
     """What the trials of one batch must share.  Spectral trials: solver class, N, level hierarchy, diagnostics flag and
     nx / ny (solver.ny=... overrides).  Finite-volume trials: the solver class alone -- the FV kernel advances any mix
-    of sizes, schemes and parameters in one launch (solvers.fv.batched)."""
+    of sizes, schemes and parameters in one launch (solvers.fv.batched); sequenced trials (solver=fv/fsg) of any
+    sizes and depths form a batch of their own (BatchedFVFSGSolver)."""
     sv = cfg["solver"]
-    if sv["_target_"] == FV:
-        return (FV,)
+    if sv["_target_"] in FV_TARGETS:
+        return (sv["_target_"],)
     return (sv["_target_"], int(cfg["N"]), int(sv.get("n_levels", 0)), bool(sv.get("diagnostics", True)),
             int(sv.get("nx", cfg["N"])), int(sv.get("ny", cfg["N"])))
 
@@ -167,9 +172,9 @@ def batch_sizes(key: tuple, count: int, max_batch: int, given: bool) -> list:
     Without a cap from the user a batch is as large as the kernel takes at once where one work-group advances a trial:
     256 for finite-volume trials and for the spectral sizes the trial-per-CU kernel holds (M = N + 1 <= 44)."""
     target = key[0]
-    if target not in (SG, FSG, FV) or count < 2 or max_batch <= 1:
+    if target not in (SG, FSG) + FV_TARGETS or count < 2 or max_batch <= 1:
         return []
-    if given or (target != FV and int(key[1]) + 1 > 44):
+    if given or (target not in FV_TARGETS and int(key[1]) + 1 > 44):
         cap = max_batch
     else:
         cap = max(max_batch, FV_LAUNCH_MAX)
@@ -195,7 +200,7 @@ def run_batches(groups: list, device: str = None) -> list:
     n_cus = _device_cus(device)      # decides whether a size fills the chip on its own (N >= 241 on 256 CUs)
     tasks = []
     for gi, (cfgs, _) in enumerate(groups):
-        if cfgs[0]["solver"]["_target_"] == FV:
+        if cfgs[0]["solver"]["_target_"] in FV_TARGETS:
             # a finite-volume group is ONE batch: its work-groups are independent (one CU each, no waits), so halves on
             # two streams gain nothing; it lasts as long as its longest trial, whatever the sizes in it
             weight = max(trial_cost(dict(N=c["N"], Re=c["Re"]), solver=FV) for c in cfgs)
@@ -250,9 +255,9 @@ def run_batches(groups: list, device: str = None) -> list:
                 target = part[0]["solver"]["_target_"]
                 if len(nodes) == 1:                 # alone on its stream: the single-trial kernels (no argument blocks in memory)
                     batch = _OneTrial(C.instantiate(dict(nodes[0], _target_=target)))
-                elif target == FV:
-                    from solvers.fv.batched import BatchedFVSolver
-                    batch = BatchedFVSolver(nodes)
+                elif target in FV_TARGETS:
+                    from solvers.fv.batched import BatchedFVFSGSolver, BatchedFVSolver
+                    batch = (BatchedFVFSGSolver if target == FV_FSG else BatchedFVSolver)(nodes)
                 else:
                     batch = (BatchedFSGSolver if target.endswith("FSGSolver") else BatchedSGSolver)(nodes)     # built on this worker's stream
                 batch.solve()

@@ -102,6 +102,15 @@ class FVParameters(Parameters):
         return {k: _mlflow_scalar(v) for k, v in self.as_dict().items() if k not in skip}
 
 
+@dataclass
+class FVFSGParameters(FVParameters):
+    """Coarse-to-fine grid sequencing of the finite-volume solver (solvers.fv.fsg.FVFSGSolver): converge on n // 2 (and
+    coarser), prolong, converge on n.  All three are real parameters of a run and go to MLflow."""
+    n_levels: int = 2                        # at most this many levels, the fine one included
+    coarsest_n: int = 16                     # no level has fewer cells per axis
+    coarse_tolerance_factor: float = 1.0     # a level k levels below the fine one runs to tolerance * factor^k
+
+
 _VORTEX_KEYS = (
     "psi_min", "psi_min_x", "psi_min_y", "omega_center",
     "omega_max", "omega_max_x", "omega_max_y",

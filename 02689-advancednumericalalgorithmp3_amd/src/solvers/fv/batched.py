@@ -13,6 +13,9 @@ kernels' co-resident work-groups fits beside it), and the spectral kernels of mo
 work-groups resident at once and give up after a bounded spin.  So every FV chunk runs under the device's
 ``ldc_lib.resident_lock``, like those launches do: in a mixed sweep an FV chunk and a co-resident spectral chunk take
 turns, while launch-path spectral batches of other streams still run beside either.
+
+``BatchedFVFSGSolver`` is the same for coarse-to-fine sequences (solvers.fv.fsg): stage by stage, every stage a batch of
+ordinary trials, one ``prolong`` launch between stages.
 """
 from __future__ import annotations
 
@@ -23,7 +26,8 @@ import numpy as np
 
 from ..base import WARMUP_ITERATIONS
 from . import ldc_fv_lib as F
-from .solver import FVSolver, advance, postprocess
+from .fsg import FVFSGSolver, level_tolerance
+from .solver import FVSolver, advance, postprocess, prolong
 
 log = logging.getLogger(__name__)
 
@@ -68,13 +72,15 @@ class BatchedFVSolver:
     kernel reports a NaN ends as a lone run ends -- with the ``LdcError`` of ``ldc_fv_status`` -- but here the exception
     is kept in ``errors[index]`` instead of raised, and the other trials are not disturbed."""
 
+    Solver = FVSolver
+
     def __init__(self, trials: list):
         if not trials:
-            raise ValueError("BatchedFVSolver needs at least one trial")
+            raise ValueError(f"{type(self).__name__} needs at least one trial")
         self.solvers = []
         try:
             for t in trials:
-                self.solvers.append(FVSolver(**t))
+                self.solvers.append(self.Solver(**t))
         except BaseException:                 # the handles of the trials already built
             self.close()
             raise
@@ -114,14 +120,28 @@ class BatchedFVSolver:
         out = run_chunks([s.rec_cap for s in self.solvers], caps, self._step)
         wall = time.perf_counter() - t0
         self.batch_seconds, self.batch_size = wall, len(self.solvers)
+        self._store(out, wall)
+        log.info("batched solve of %d FV trials finished in %.2f s (%d stopped on a NaN)", len(self.solvers), wall,
+                 len(self.errors))
+        return [None if q in self.errors else s.metrics for q, s in enumerate(self.solvers)]
+
+    @staticmethod
+    def _nan_error(s, total):
+        """What a lone _advance raises for a trial whose kernel reports a NaN (ldc_fv_status -> LDC_FV_E_NAN)."""
+        try:
+            F.check(F.lib().ldc_fv_status(s.handle), f"FV trial at iteration {total}")
+            raise RuntimeError(f"FV trial at iteration {total}: ctrl reports a NaN, ldc_fv_status does not")
+        except Exception as exc:
+            return exc
+
+    def _store(self, out, wall, extra_work=None):
+        """History, metrics and fields of every trial from ``out`` (run_chunks' rows of ``self.solvers``, in order); a
+        trial that stopped on a NaN, and one already in ``errors``, gets an error instead.  ``extra_work``: per trial,
+        iterations x cells spent before (coarser levels), which count in its share of the wall time."""
         for q, (s, (_, nan, total, _)) in enumerate(zip(self.solvers, out)):
-            if nan:                           # what a lone _advance raises (ldc_fv_status -> LDC_FV_E_NAN)
-                try:
-                    F.check(F.lib().ldc_fv_status(s.handle), f"FV trial at iteration {total}")
-                    raise RuntimeError(f"FV trial at iteration {total}: ctrl reports a NaN, ldc_fv_status does not")
-                except Exception as exc:
-                    self.errors[q] = exc
-        work = [0 if q in self.errors else total * s.nx * s.ny
+            if nan and q not in self.errors:
+                self.errors[q] = self._nan_error(s, total)
+        work = [0 if q in self.errors else total * s.nx * s.ny + (extra_work[q] if extra_work else 0)
                 for q, (s, (_, _, total, _)) in enumerate(zip(self.solvers, out))]
         work_all = max(1, sum(work))
         # the device path of the vortex metrics: every finished trial that asks for it in one go (_store_results below
@@ -133,6 +153,69 @@ class BatchedFVSolver:
                 continue
             s.history = hist
             s._store_results(hist[WARMUP_ITERATIONS:], total, done == 1, wall * work[q] / work_all)
-        log.info("batched solve of %d FV trials finished in %.2f s (%d stopped on a NaN)", len(self.solvers), wall,
-                 len(self.errors))
+
+
+class BatchedFVFSGSolver(BatchedFVSolver):
+    """``trials``: list of FVFSGSolver keyword dicts, all on one device; sizes, depths and parameters may differ.
+
+    The levels are counted from the fine one DOWN, and a stage advances every trial that has a level at that depth: with
+    hierarchies [16, 32, 64] and [20, 40] the stages are {16}, then {32, 20}, then {64, 40}.  So a trial joins at its own
+    coarsest level, all fine levels run together in the last stage, and a stage lasts as long as its longest trial.
+    Every stage is one ``run_chunks`` of ordinary FVSolvers; between stages ONE ``prolong`` call takes every state one
+    level up.  A level is the same launches' work whether its trial runs alone or here, so every trial's fields, history,
+    ``metrics.iterations`` and ``level_iterations`` are those of its lone ``FVFSGSolver.solve()``.  A trial that stops
+    on a NaN on any level gets that level's ``LdcError`` in ``errors[index]`` and goes no further."""
+
+    Solver = FVFSGSolver
+
+    def solve(self, max_iter: int = None):
+        ps = [s.params for s in self.solvers]
+        caps = [int(p.max_iterations if max_iter is None else max_iter) for p in ps]
+        sizes = [s.level_sizes() for s in self.solvers]
+        depth = max(len(z) for z in sizes)
+        self.errors = {}
+        below = {}                                # trial -> its level under the one about to run
+        extra = [0] * len(self.solvers)
+        for s in self.solvers:
+            s.level_iterations = []
+        t0 = time.perf_counter()
+        out = [None] * len(self.solvers)
+        try:
+            for above in range(depth - 1, -1, -1):        # levels above: depth - 1 ... 0 (the fine levels)
+                group = [q for q in range(len(self.solvers)) if len(sizes[q]) > above and q not in self.errors]
+                if not group:
+                    continue
+                lvls = {}
+                for q in group:
+                    nx, ny = sizes[q][len(sizes[q]) - 1 - above]
+                    lvls[q] = self.solvers[q] if above == 0 else self.solvers[q].make_level(nx, ny)
+                prolong([(below[q], lvls[q]) for q in group if q in below])
+                for q in group:
+                    if q in below:
+                        below.pop(q).close()
+                    lvls[q]._begin(level_tolerance(ps[q].tolerance, ps[q].coarse_tolerance_factor, above))
+                    self.solvers[q]._started = False
+                rows = run_chunks([lvls[q].rec_cap for q in group], [caps[q] for q in group],
+                                  lambda live, k: advance([lvls[group[i]] for i in live], k))
+                for q, row in zip(group, rows):
+                    _, nan, total, _ = row
+                    self.solvers[q].level_iterations.append(int(total))
+                    if nan:
+                        self.errors[q] = self._nan_error(lvls[q], total)
+                    if above == 0:
+                        out[q] = row
+                    else:
+                        extra[q] += total * lvls[q].nx * lvls[q].ny
+                        below[q] = lvls[q]
+                log.info("FV sequence, %d level(s) above the fine one: %d trials, iterations %s", above, len(group),
+                         [r[2] for r in rows])
+        finally:
+            for lvl in below.values():
+                lvl.close()
+        wall = time.perf_counter() - t0
+        self.batch_seconds, self.batch_size = wall, len(self.solvers)
+        empty = (0, 0, 0, np.zeros((0, F.REC_LEN)))
+        self._store([o if o is not None else empty for o in out], wall, extra)
+        log.info("batched sequenced solve of %d FV trials finished in %.2f s (%d stopped on a NaN)", len(self.solvers),
+                 wall, len(self.errors))
         return [None if q in self.errors else s.metrics for q, s in enumerate(self.solvers)]

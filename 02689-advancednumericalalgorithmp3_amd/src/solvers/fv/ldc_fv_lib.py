@@ -14,6 +14,7 @@ MIN_N, MAX_N = 8, 256
 REC_LEN, CTRL_LEN = 8, 8
 NWORK, DESC_DOUBLES = 32, 64
 LAUNCH_MAX = 256
+PROLONG_LAUNCH_MAX = 128
 E_NAN = -5
 CTRL_DONE, CTRL_ITER, CTRL_NAN, CTRL_GIVEUP, CTRL_LIN_ITERS, CTRL_SOLVES = range(6)
 # slots of a result block of ldc_fv_post_enqueue (LDC_FV_POST_*)
@@ -45,7 +46,7 @@ class Post(C.Structure):
 
 # every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
-           "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_post_enqueue")
+           "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue")
 
 _bound = None
 
@@ -63,6 +64,9 @@ def lib() -> C.CDLL:
     global _bound
     L = _L.lib()
     if _bound is None:
+        missing = [name for name in EXPORTS if not hasattr(L, name)]
+        if missing:               # (ldc_fv_prolong_enqueue came without a new version number: a library from before it)
+            raise _L.LdcError(f"libldc_hip.so is out of date: it does not export {', '.join(missing)}; rebuild it")
         L.ldc_fv_version.restype = C.c_int
         L.ldc_fv_create.argtypes = [C.POINTER(Problem), C.POINTER(_dp)]
         L.ldc_fv_destroy.argtypes = [_dp]
@@ -71,6 +75,7 @@ def lib() -> C.CDLL:
         L.ldc_fv_status.argtypes = [_dp]
         L.ldc_fv_step_debug.argtypes = [_dp, C.c_int, C.POINTER(_dp), _dp]
         L.ldc_fv_post_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(Post), C.c_int, _dp]
+        L.ldc_fv_prolong_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(_dp), C.c_int, _dp]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -94,3 +99,13 @@ def post_enqueue(handles, posts, stream) -> None:
     arr = (_dp * len(handles))(*[h.value if isinstance(h, _dp) else h for h in handles])
     blocks = (Post * len(posts))(*posts)
     check(lib().ldc_fv_post_enqueue(arr, blocks, len(handles), _dp(stream)), "ldc_fv_post_enqueue")
+
+
+def prolong_enqueue(coarse_handles, fine_handles, stream) -> None:
+    """fine_handles[q] <- the prolongation of coarse_handles[q] (u, v, p, mdot; include/ldc_fv.h), one work-group per
+    pair, any number of pairs: the library launches PROLONG_LAUNCH_MAX at a time and checks all of them first."""
+    if len(coarse_handles) != len(fine_handles):
+        raise ValueError(f"{len(coarse_handles)} coarse handles for {len(fine_handles)} fine ones")
+    raw = lambda hs: (_dp * len(hs))(*[h.value if isinstance(h, _dp) else h for h in hs])        # noqa: E731
+    check(lib().ldc_fv_prolong_enqueue(raw(coarse_handles), raw(fine_handles), len(fine_handles), _dp(stream)),
+          "ldc_fv_prolong_enqueue")

@@ -121,6 +121,33 @@ def postprocess(trials):
         s._post = row.copy()
 
 
+def prolong(pairs):
+    """Start every fine trial from the state of its coarse one: ``pairs`` of (coarse, fine) FVSolvers on one device, of
+    any sizes and parameters but one domain (Lx, Ly), none in flight (``ldc_fv_prolong_enqueue``: bilinear in u, v, p from the coarse cell
+    centres and the boundary values, p pinned at cell 0, mdot from the new u and v).  One call of the library for all pairs, which it checks together and
+    launches ``PROLONG_LAUNCH_MAX`` (128) at a time, one work-group each; the fine trials' control words, records and work vectors are left alone (a ``solve()`` zeroes the
+    control words itself), and so are the coarse trials.  A fine trial must not be the coarse or the fine trial of
+    another pair of the same call: chain levels with one call per level."""
+    import torch
+    from solvers.spectral import ldc_lib
+    pairs = list(pairs)
+    if not pairs:
+        return
+    dev = pairs[0][1].device
+    index = torch.cuda.current_device() if dev.index is None else dev.index
+    for c, f in pairs:
+        for s in (c, f):
+            if (torch.cuda.current_device() if s.device.index is None else s.device.index) != index:
+                raise ValueError("prolong: all trials must be on one device")
+    with torch.cuda.device(dev):
+        with ldc_lib.resident_lock(index):
+            F.prolong_enqueue([c.handle for c, _ in pairs], [f.handle for _, f in pairs],
+                              torch.cuda.current_stream(dev).cuda_stream)
+            torch.cuda.current_stream(dev).synchronize()      # (the lock goes back with the CUs free)
+    for _, f in pairs:
+        f._post = None
+
+
 def advance(trials, k):
     """One chunk for lone trials and batches alike: ``k`` iterations (at most every trial's record ring) for each of
     ``trials`` (FVSolvers on one device) in ONE launch, one work-group each, then ONE copy of their ctrl words and ONE of

@@ -1,4 +1,5 @@
-/* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip).
+/* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
+ * csrc/ldc_fv_prolong.hip).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -36,6 +37,21 @@
  *  - result: LDC_FV_POST_RESULT_LEN doubles, the LDC_FV_POST_* slots below; cells are stored as doubles, -1 = none;
  *  - scratch: two of the trial's work vectors and 72 bytes of the descriptor slot behind the descriptor.  The state,
  *    rec and ctrl are only read, so a solve goes on afterwards as if nothing had happened.
+ *
+ * Prolongation (csrc/ldc_fv_prolong.hip): the state of a FINE trial from the state of a COARSE one on the same domain,
+ * of any two sizes (coarse-to-fine sequencing, continuation in Re at equal size), one work-group per pair, neither
+ * trial in flight.  Read: the coarse trial's u, v, p, ulid and sizes.  Written: the fine trial's u, v, p, mdot and
+ * nothing else (no ctrl, no rec, no work vector), so the caller zeroes ctrl as before any new solve.
+ *  - per axis the coarse field is extended by a ring on the domain boundary: nodes e_0 = 0, e_k = (k - 1/2) h_c
+ *    (k = 1..n_c, the cell centres), e_{n_c+1} = n_c h_c.  u and v on the ring are 0.0, except u above cell i on the
+ *    lid (the y ring, j = ny_c + 1), which is the coarse ulid[i]; the four corners are 0.0.  The ring of p repeats
+ *    the nearest cell (zero normal gradient);
+ *  - a fine centre x = (i + 1/2) h_f takes the left node k = the largest node with e_k <= x, at most n_c, and the
+ *    weight t = (x - e_k) / (e_{k+1} - e_k); the value is bilinear, x first: lo = a + tx (b - a) on row ky,
+ *    hi likewise on row ky + 1, then lo + ty (hi - lo).  No multiply-add is contracted;
+ *  - p: the interpolated value at fine cell 0 is subtracted from every cell, so p[0] is exactly 0.0 (the pinned cell);
+ *  - mdot from the new u, v as the solver's face rule: interior faces rho (1/2 f_N + 1/2 f_P) |S|, the faces on the
+ *    four walls exactly 0.0.
  */
 #ifndef LDC_FV_H
 #define LDC_FV_H
@@ -56,6 +72,7 @@ extern "C" {
 #define LDC_FV_WORK_LEN(nx, ny) (LDC_FV_NWORK * (int64_t)(nx) * (ny) + LDC_FV_DESC_DOUBLES)
 #define LDC_FV_FACES(nx, ny) ((int64_t)(ny) * ((nx) + 1) + (int64_t)((ny) + 1) * (nx))
 #define LDC_FV_LAUNCH_MAX 256      /* trials per launch of ldc_fv_batch_enqueue (more: several launches) */
+#define LDC_FV_PROLONG_LAUNCH_MAX 128 /* pairs per launch of ldc_fv_prolong_enqueue: two descriptors per pair in the arguments */
 #define LDC_FV_E_NAN (-5)          /* ldc_fv_status: the trial produced a NaN and stopped */
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
@@ -135,6 +152,14 @@ int ldc_fv_step_debug(ldc_fv *h, int which, double *const *out, void *stream);
 /* omega, psi and the result block of n trials (any sizes, one device), one work-group each; trial q takes posts[q]. */
 /* Validation comes first and needs no device.  The trials must not be in flight on another stream.                  */
 int ldc_fv_post_enqueue(ldc_fv *const *hs, const struct ldc_fv_post *posts, int n, void *stream);
+/* fine[q] <- the prolongation of coarse[q] for n pairs (any sizes, one device), one work-group of 512 threads each and */
+/* no waits between them; more than LDC_FV_PROLONG_LAUNCH_MAX pairs: several launches.  Validation comes first, and its  */
+/* first part needs no device: LDC_E_ARG for a null list or n < 1, LDC_E_STATE for a null handle; then LDC_E_STATE for  */
+/* a handle of another device, LDC_E_ARG for a size outside LDC_FV_MIN_N .. LDC_FV_MAX_N, for a pair whose domains      */
+/* differ (nx dx or ny dy, beyond 1e-12 relative), for coarse[q] == fine[q] and for a fine trial that is also the       */
+/* coarse or the fine trial of another pair of the call, however many launches it takes (its pairs are unordered).      */
+/* The library keeps no record of launches: that no trial is in flight on another stream is the caller's to see to.     */
+int ldc_fv_prolong_enqueue(ldc_fv *const *coarse, ldc_fv *const *fine, int n, void *stream);
 
 #ifdef __cplusplus
 }
