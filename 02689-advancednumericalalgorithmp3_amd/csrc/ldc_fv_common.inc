@@ -1,6 +1,6 @@
 // ldc_fv_common.inc -- what the translation units of the finite-volume solver share (include/ldc_fv.h):
 // ldc_kernels.hip (through ldc_fv_kernel.inc, the SIMPLE iteration), ldc_fv_post.hip (streamfunction and vortex
-// metrics) and ldc_fv_prolong.hip (coarse-to-fine transfer of the state).  Types and constants only: each unit keeps its own device functions, so neither unit's code object
+// metrics), ldc_fv_prolong.hip (coarse-to-fine transfer of the state) and ldc_fv_anderson.hip (Anderson mixing).  Types and constants only: each unit keeps its own device functions, so neither unit's code object
 // depends on the other's.
 #ifndef LDC_FV_COMMON_INC
 #define LDC_FV_COMMON_INC

@@ -96,6 +96,12 @@ class FVParameters(Parameters):
     # streamfunction and vortex metrics after a solve: "host" (SciPy sparse solve, one trial after another) or "device"
     # (ldc_fv_post_enqueue, all trials of a batch in one launch); not given: LDC_FV_VORTEX_METRICS may choose
     vortex_metrics: str = field(default_factory=lambda: os.environ.get("LDC_FV_VORTEX_METRICS", "host"))
+    # Anderson acceleration of the outer iteration (ldc_fv_anderson_enqueue): "none" or "anderson", the number of
+    # difference columns kept (1 ... 16) and the iteration count from which the iterates are mixed.  Real parameters of
+    # a run: they go to MLflow
+    acceleration: str = "none"
+    anderson_depth: int = 5
+    anderson_start: int = 10
 
     def to_mlflow(self) -> dict:
         skip = {"device", "check_every", "vortex_metrics"}

@@ -15,6 +15,8 @@ REC_LEN, CTRL_LEN = 8, 8
 NWORK, DESC_DOUBLES = 32, 64
 LAUNCH_MAX = 256
 PROLONG_LAUNCH_MAX = 128
+ANDERSON_LAUNCH_MAX, ANDERSON_MAX_DEPTH, ANDERSON_STATE_LEN = 96, 16, 4
+ASTATE_COLUMNS, ASTATE_POSITION, ASTATE_SEEN, ASTATE_FALLBACKS = range(4)
 E_NAN = -5
 CTRL_DONE, CTRL_ITER, CTRL_NAN, CTRL_GIVEUP, CTRL_LIN_ITERS, CTRL_SOLVES = range(6)
 # slots of a result block of ldc_fv_post_enqueue (LDC_FV_POST_*)
@@ -44,9 +46,15 @@ class Post(C.Structure):
     )
 
 
+class Anderson(C.Structure):
+    """Mirror of ``struct ldc_fv_anderson`` -- keep field order in sync with the header."""
+    _fields_ = [("depth", C.c_int32), ("start", C.c_int32), ("hist", _dp), ("hist_len", C.c_int64), ("astate", _dp)]
+
+
 # every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
-           "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue")
+           "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
+           "ldc_fv_anderson_enqueue")
 
 _bound = None
 
@@ -59,13 +67,18 @@ def faces(nx: int, ny: int) -> int:
     return ny * (nx + 1) + (ny + 1) * nx
 
 
+def anderson_hist_len(nx: int, ny: int, depth: int) -> int:
+    """x, g_prev, f_prev and ``depth`` columns each of dG and dF, every one [u | v | p | mdot]."""
+    return (2 * depth + 3) * (3 * nx * ny + faces(nx, ny))
+
+
 def lib() -> C.CDLL:
     """The shared library with the FV entry points' signatures set (raises if it has not been built)."""
     global _bound
     L = _L.lib()
     if _bound is None:
         missing = [name for name in EXPORTS if not hasattr(L, name)]
-        if missing:               # (ldc_fv_prolong_enqueue came without a new version number: a library from before it)
+        if missing:               # (ldc_fv_prolong_enqueue and ldc_fv_anderson_enqueue came without a new version number)
             raise _L.LdcError(f"libldc_hip.so is out of date: it does not export {', '.join(missing)}; rebuild it")
         L.ldc_fv_version.restype = C.c_int
         L.ldc_fv_create.argtypes = [C.POINTER(Problem), C.POINTER(_dp)]
@@ -76,6 +89,7 @@ def lib() -> C.CDLL:
         L.ldc_fv_step_debug.argtypes = [_dp, C.c_int, C.POINTER(_dp), _dp]
         L.ldc_fv_post_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(Post), C.c_int, _dp]
         L.ldc_fv_prolong_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(_dp), C.c_int, _dp]
+        L.ldc_fv_anderson_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(Anderson), C.c_int, C.c_int, _dp]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -109,3 +123,13 @@ def prolong_enqueue(coarse_handles, fine_handles, stream) -> None:
     raw = lambda hs: (_dp * len(hs))(*[h.value if isinstance(h, _dp) else h for h in hs])        # noqa: E731
     check(lib().ldc_fv_prolong_enqueue(raw(coarse_handles), raw(fine_handles), len(fine_handles), _dp(stream)),
           "ldc_fv_prolong_enqueue")
+
+
+def anderson_enqueue(handles, blocks, n_iters: int, stream) -> None:
+    """``n_iters`` times: one SIMPLE iteration of every handle, then the mixing kernel (``blocks``: one ``Anderson``
+    each, depth 0 for a plain trial); all enqueued, nothing synchronises."""
+    if len(handles) != len(blocks):
+        raise ValueError(f"{len(blocks)} Anderson blocks for {len(handles)} handles")
+    arr = (_dp * len(handles))(*[h.value if isinstance(h, _dp) else h for h in handles])
+    acc = (Anderson * len(blocks))(*blocks)
+    check(lib().ldc_fv_anderson_enqueue(arr, acc, len(handles), int(n_iters), _dp(stream)), "ldc_fv_anderson_enqueue")

@@ -3,7 +3,8 @@
 Contract: reference src/solvers/fv/solver.py (the iteration, :170-257), base.py:202-330 (the loop and its record),
 :359-450 (E, Z, P), :569-760 (streamfunction and vortex extrema).  Every SIMPLE iteration runs in the HIP kernel of
 include/ldc_fv.h -- one work-group per trial, ``check_every`` iterations per launch -- and the host only reads the
-record rows and the latch.  The host computes, once per trial, the eigenvectors of the 1-D Neumann Laplacians that the
+record rows and the latch.  ``acceleration="anderson"`` mixes the iterates on the device after every iteration
+(``ldc_fv_anderson_enqueue``: one launch per iteration and a mixing launch after it, still one wait per chunk).  The host computes, once per trial, the eigenvectors of the 1-D Neumann Laplacians that the
 kernel's exact pressure-correction solve uses, and, once per solve, the vortex metrics: on the host with SciPy's sparse
 solve (``vortex_metrics="host"``, the default) or on the device (``"device"``: ``ldc_fv_post_enqueue``, one work-group
 per trial, the same quantities by the same rules).
@@ -24,6 +25,7 @@ log = logging.getLogger(__name__)
 
 SCHEMES = {"Upwind": 0, "TVD": 1}
 VORTEX_METRICS = ("host", "device")
+ACCELERATIONS = ("none", "anderson")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
 
 
@@ -154,6 +156,9 @@ def advance(trials, k):
     the first ``k`` rows of their record rings (the slices stack whatever the rings' own lengths); per trial (rows of the
     new iterations, latch, nan, iteration count).
 
+    With ``acceleration="anderson"`` on any of the trials the chunk is ``k`` launches of ONE iteration with the mixing
+    kernel after each (``ldc_fv_anderson_enqueue``), all enqueued before the one wait; without, the launch of before.
+
     A work-group holds its CU for the whole chunk, so launch and wait hold the device's resident lock: not beside a
     launch whose work-groups must all be resident (a lone trial in the launcher's pool of streams, next to spectral
     batches; solvers.fv.batched)."""
@@ -162,10 +167,15 @@ def advance(trials, k):
     from solvers.spectral.chunks import _words
     dev = trials[0].device
     index = torch.cuda.current_device() if dev.index is None else dev.index
+    accelerated = any(s.accelerated for s in trials)
     with torch.cuda.device(dev):
         starts = _words([s.t["ctrl"] for s in trials])[:, F.CTRL_ITER]
         with ldc_lib.resident_lock(index):
-            F.batch_enqueue([s.handle for s in trials], k, torch.cuda.current_stream(dev).cuda_stream)
+            if accelerated:     # k launches of one iteration, a mixing launch after each; plain trials ride at depth 0
+                F.anderson_enqueue([s.handle for s in trials], [s._anderson_block() for s in trials], k,
+                                   torch.cuda.current_stream(dev).cuda_stream)
+            else:
+                F.batch_enqueue([s.handle for s in trials], k, torch.cuda.current_stream(dev).cuda_stream)
             ctrl = _words([s.t["ctrl"] for s in trials])        # (synchronises the stream)
         rings = _words([s.t["rec"][:k] for s in trials])
     return [(ring[: int(c[F.CTRL_ITER] - start)].copy(), int(c[F.CTRL_DONE]), int(c[F.CTRL_NAN]), int(c[F.CTRL_ITER]))
@@ -187,6 +197,13 @@ class FVSolver(LidDrivenCavitySolver):
             raise ValueError(f"limiter={p.limiter!r}: the TVD scheme of the reference is MUSCL")
         if p.vortex_metrics not in VORTEX_METRICS:
             raise ValueError(f"vortex_metrics={p.vortex_metrics!r}: 'host' or 'device'")
+        if p.acceleration not in ACCELERATIONS:
+            raise ValueError(f"acceleration={p.acceleration!r}: 'none' or 'anderson'")
+        if not 1 <= int(p.anderson_depth) <= F.ANDERSON_MAX_DEPTH:
+            raise ValueError(f"anderson_depth={p.anderson_depth}: 1 ... {F.ANDERSON_MAX_DEPTH} columns")
+        if int(p.anderson_start) < 1:
+            raise ValueError(f"anderson_start={p.anderson_start}: an iteration count, at least 1")
+        self.accelerated = p.acceleration == "anderson"
         nx, ny = int(p.nx), int(p.ny)
         if not (F.MIN_N <= nx <= F.MAX_N and F.MIN_N <= ny <= F.MAX_N):
             raise ValueError(f"nx, ny = {nx}, {ny}: the FV kernel takes {F.MIN_N} ... {F.MAX_N} cells per axis")
@@ -218,7 +235,11 @@ class FVSolver(LidDrivenCavitySolver):
             u=torch.zeros(nx * ny, **f64), v=torch.zeros(nx * ny, **f64), p=torch.zeros(nx * ny, **f64),
             mdot=torch.zeros(F.faces(nx, ny), **f64), work=torch.zeros(F.work_len(nx, ny), **f64),
             rec=torch.zeros((self.rec_cap, F.REC_LEN), **f64),
-            ctrl=torch.zeros(F.CTRL_LEN, dtype=torch.int64, device=self.device))
+            ctrl=torch.zeros(F.CTRL_LEN, dtype=torch.int64, device=self.device),
+            # the mixing kernel's words: every trial has them (a plain trial rides in an accelerated call at depth 0)
+            astate=torch.zeros(F.ANDERSON_STATE_LEN, dtype=torch.int64, device=self.device))
+        if self.accelerated:
+            self.t["hist"] = torch.zeros(F.anderson_hist_len(nx, ny, int(p.anderson_depth)), **f64)
         self._handle = None
         self._handle_tol = None
         self._make_handle(p.tolerance)
@@ -251,6 +272,14 @@ class FVSolver(LidDrivenCavitySolver):
             F.lib().ldc_fv_destroy(self._handle)
             self._handle = None
 
+    def _anderson_block(self) -> F.Anderson:
+        """This trial's block of an ``anderson_enqueue`` call: its depth and history, depth 0 for a plain trial."""
+        p = self.params
+        if not self.accelerated:
+            return F.Anderson(depth=0, start=1, hist=None, hist_len=0, astate=self.t["astate"].data_ptr())
+        return F.Anderson(depth=int(p.anderson_depth), start=int(p.anderson_start), hist=self.t["hist"].data_ptr(),
+                          hist_len=self.t["hist"].numel(), astate=self.t["astate"].data_ptr())
+
     def close(self):
         """Release the device handle (the torch tensors go with the object)."""
         self._destroy_handle()
@@ -276,6 +305,7 @@ class FVSolver(LidDrivenCavitySolver):
         for name, val in (("u", u), ("v", v), ("p", p), ("mdot", mdot)):
             self.t[name].copy_(torch.as_tensor(np.asarray(val, dtype=np.float64).ravel()))
         self.t["ctrl"].zero_()
+        self.t["astate"].zero_()
         self._post = None
 
     def state(self) -> dict:
@@ -283,9 +313,10 @@ class FVSolver(LidDrivenCavitySolver):
 
     def counters(self) -> dict:
         c = self.t["ctrl"].cpu().numpy()
+        a = self.t["astate"].cpu().numpy()
         return dict(done=int(c[F.CTRL_DONE]), iterations=int(c[F.CTRL_ITER]), nan=int(c[F.CTRL_NAN]),
                     linear_giveups=int(c[F.CTRL_GIVEUP]), linear_iterations=int(c[F.CTRL_LIN_ITERS]),
-                    momentum_solves=int(c[F.CTRL_SOLVES]))
+                    momentum_solves=int(c[F.CTRL_SOLVES]), anderson_fallbacks=int(a[F.ASTATE_FALLBACKS]))
 
     def step_debug(self, which=F.DBG) -> dict:
         """One iteration through ldc_fv_step_debug; returns the named intermediates (include/ldc_fv.h)."""
@@ -307,6 +338,7 @@ class FVSolver(LidDrivenCavitySolver):
         ``solve()`` counts from 0 on the current state, with its own warm-up, history and iteration count."""
         self._make_handle(tolerance)
         self.t["ctrl"].zero_()
+        self.t["astate"].zero_()                 # (the mixing history starts over with the count: include/ldc_fv.h)
         self._post = None
 
     def _advance(self, n_iters: int):

@@ -1,5 +1,5 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
- * csrc/ldc_fv_prolong.hip).
+ * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -52,6 +52,30 @@
  *  - p: the interpolated value at fine cell 0 is subtracted from every cell, so p[0] is exactly 0.0 (the pinned cell);
  *  - mdot from the new u, v as the solver's face rule: interior faces rho (1/2 f_N + 1/2 f_P) |S|, the faces on the
  *    four walls exactly 0.0.
+ *
+ * Anderson acceleration (csrc/ldc_fv_anderson.hip, ldc_fv_anderson_enqueue): the outer iteration as the fixed-point map
+ * x -> g = SIMPLE(x) on the concatenation [u | v | p | mdot] (L = 3n + faces entries), mixed after every iteration by a
+ * kernel of its own, one work-group of 512 threads per trial; the solve kernel is not touched.  Per trial and iteration,
+ * with it = ctrl[1] after the SIMPLE launch:
+ *  - it equals astate[2] (the trial was latched, NaN or capped: the launch did nothing): nothing happens;
+ *  - otherwise rec row 0 (where a launch of one iteration writes) is copied to rec row j, the iteration's place in the
+ *    enqueue; the row of iteration 0 waits in the last LDC_FV_REC_LEN doubles of the descriptor slot in the tail of
+ *    `work` and goes back to row 0 with the trial's last iteration of the enqueue (the last one, or the one that set
+ *    ctrl[0] or ctrl[2]), so rec reads as after ldc_fv_batch_enqueue.  With ctrl[0] or ctrl[2] set, or depth 0, that
+ *    is all;
+ *  - x is the state the SIMPLE launch started from, which the kernel keeps in hist.  After a zeroed astate it has none:
+ *    the first iteration of a solve only keeps g as the next x.  From the second on f = g - x, and from the third on
+ *    the differences dG = g - g_prev, dF = f - f_prev replace the oldest of `depth` columns (a ring; slot astate[1]);
+ *  - it < start, or no column yet: the next state is g.  Otherwise, over the m valid columns in SLOT order, A = dF^T dF
+ *    and b = dF^T f over the u, v, p entries (the first 3n), A += 1e-12 trace(A) / m on the diagonal, A gamma = b by
+ *    Cholesky (one thread), and the next state is g - sum_i gamma_i dG_i over all L entries.  The weights of the g's sum
+ *    to 1, so the mixed mdot is a combination of mass-conserving fluxes and p[0] stays 0; it is WRITTEN as 0.0;
+ *  - a pivot <= 0 (or NaN) or a gamma that is not finite: the fallback.  The next state is g, the ring is emptied
+ *    (g_prev and f_prev stay) and astate[3] counts it;
+ *  - hist: x, g_prev, f_prev, dG[depth], dF[depth], L doubles each: (2 depth + 3) L.  The Gram matrix is recomputed in
+ *    full every iteration, sums in a fixed order (per thread in increasing index, wave shuffles, LDS), so lone runs,
+ *    batches and repeats agree bit for bit.
+ *  Between the enqueues of ONE solve an accelerated trial is advanced by ldc_fv_anderson_enqueue only.
  */
 #ifndef LDC_FV_H
 #define LDC_FV_H
@@ -73,6 +97,10 @@ extern "C" {
 #define LDC_FV_FACES(nx, ny) ((int64_t)(ny) * ((nx) + 1) + (int64_t)((ny) + 1) * (nx))
 #define LDC_FV_LAUNCH_MAX 256      /* trials per launch of ldc_fv_batch_enqueue (more: several launches) */
 #define LDC_FV_PROLONG_LAUNCH_MAX 128 /* pairs per launch of ldc_fv_prolong_enqueue: two descriptors per pair in the arguments */
+#define LDC_FV_ANDERSON_LAUNCH_MAX 96 /* trials per launch of the mixing kernel: 32 bytes per trial in the arguments */
+#define LDC_FV_ANDERSON_MAX_DEPTH 16
+#define LDC_FV_ANDERSON_STATE_LEN 4
+#define LDC_FV_ANDERSON_HIST_LEN(nx, ny, depth) ((2 * (int64_t)(depth) + 3) * (3 * (int64_t)(nx) * (ny) + LDC_FV_FACES(nx, ny)))
 #define LDC_FV_E_NAN (-5)          /* ldc_fv_status: the trial produced a NaN and stopped */
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
@@ -133,6 +161,15 @@ struct ldc_fv_post {
   double *result;                 /* out: LDC_FV_POST_RESULT_LEN */
 };
 
+struct ldc_fv_anderson {
+  int32_t depth;                  /* 0 .. LDC_FV_ANDERSON_MAX_DEPTH columns; 0: no mixing (a plain trial in the same call) */
+  int32_t start;                  /* mixing from this iteration count on (>= 1) */
+  double *hist;                   /* LDC_FV_ANDERSON_HIST_LEN(nx, ny, depth) device doubles (depth 0: may be NULL) */
+  int64_t hist_len;               /* the length of hist */
+  int64_t *astate;                /* device int64[LDC_FV_ANDERSON_STATE_LEN]: valid columns, ring position, the iteration */
+                                  /* count seen last, fallbacks taken.  Zero it exactly when ctrl is zeroed. */
+};
+
 typedef struct ldc_fv ldc_fv;
 
 int ldc_fv_version(void);
@@ -160,6 +197,15 @@ int ldc_fv_post_enqueue(ldc_fv *const *hs, const struct ldc_fv_post *posts, int 
 /* coarse or the fine trial of another pair of the call, however many launches it takes (its pairs are unordered).      */
 /* The library keeps no record of launches: that no trial is in flight on another stream is the caller's to see to.     */
 int ldc_fv_prolong_enqueue(ldc_fv *const *coarse, ldc_fv *const *fine, int n, void *stream);
+/* n_iters accelerated iterations of n trials (any sizes and parameters, one device): for every iteration             */
+/* ldc_fv_batch_enqueue(hs, n, 1, stream), then the mixing kernel, one work-group of 512 threads per trial and no waits */
+/* between them, LDC_FV_ANDERSON_LAUNCH_MAX trials per launch; trial q takes acc[q].  All of it is enqueued; nothing    */
+/* synchronises.  Validation runs as a whole before any launch, and its first part needs no device: LDC_E_ARG for a    */
+/* null list, n < 1 or n_iters < 1; then per trial, in list order, LDC_E_STATE for a null handle and LDC_E_ARG for      */
+/* depth outside 0 .. 16, start < 1, a null astate, n_iters > rec_cap, and with depth > 0 a null hist or a hist_len     */
+/* below LDC_FV_ANDERSON_HIST_LEN.  Then LDC_E_NODEVICE, and LDC_E_STATE for a handle of another device.  A trial may    */
+/* appear once in a call, and no two trials may share hist or astate: that is the caller's to see to.                   */
+int ldc_fv_anderson_enqueue(ldc_fv *const *hs, const struct ldc_fv_anderson *acc, int n, int n_iters, void *stream);
 
 #ifdef __cplusplus
 }
