@@ -1,0 +1,895 @@
+// ldc_fv_wide.hip -- ONE finite-volume trial advanced by the whole chip (include/ldc_fv.h, ldc_fv_wide_*).  A translation
+// unit of its own, linked into libldc_hip.so beside ldc_kernels.hip and the other FV units: the code object of the solve
+// kernels is the same with and without this file.
+//
+// Mapping: one kernel launch per phase of the SIMPLE iteration, up to 256 work-groups of 256 threads each, every cell
+// sweep a grid-stride loop.  The launch boundary is the only barrier between work-groups: nobody waits for anybody, so
+// there are no flags, no spin limits and no co-residency.  The arithmetic is that of ldc_fv_kernel.inc, phase by phase,
+// on the same work vectors (FvVec), so after one iteration `work` holds the intermediates ldc_fv_step_debug copies out.
+// One iteration is the chain
+//   assemble | min(lin_budget, max_lin_iters) x (p, v, s, t, x) | linfinish | faces | gemm x 4 | correct | fluxvort |
+//   sums | record
+// Rules every kernel keeps:
+//  - the grid is a function of (nx, ny) alone;
+//  - a work-group writes its partial sums to its own slot; the NEXT launch lets every work-group add all slots in one
+//    fixed order, so all work-groups hold the same scalars and runs repeat bit for bit;
+//  - no work-group reads a word another work-group of the same launch writes: the slots and the BiCGSTAB scalars exist
+//    twice and alternate by launch (`par`), and the latch, the NaN word, the overflow word and the record row are
+//    written by launches of ONE work-group only (begin, linfinish, record);
+//  - every kernel but `begin` starts at the gate: latch, NaN word or overflow word set -> return at once.
+// The data-dependent BiCGSTAB loop is a fixed number of launches; once both components have finished their launches
+// only carry the scalars on.  A component still active after lin_budget < max_lin_iters iterations sets the overflow
+// word in `linfinish`, BEFORE u, v, p or mdot have been touched (assemble and BiCGSTAB write work vectors only), and
+// the host repeats the rest of the chunk with twice the budget: the result does not depend on the budget.
+//
+// scratch (LDC_FV_WIDE_SCRATCH_LEN doubles): 16 int64 words (overflow, record row, pending give-ups, pending BiCGSTAB
+// iterations), 2 x 32 doubles of BiCGSTAB scalars, 2 x G x 10 slot sums, G x 10 sums of the record row.
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <mutex>
+#include <new>
+#include <utility>
+#include <vector>
+
+#include "ldc_hip.h"
+#include "ldc_fv_common.inc"
+
+namespace {
+
+constexpr int kWT = 256;                    // threads of a work-group
+constexpr int kWW = kWT / 64;
+constexpr int kWS = 10;                     // doubles of a slot
+constexpr int kWMaxG = 256;                 // most work-groups of a sweep: one per CU, and one slot per thread to add
+constexpr int kWWords = 16;
+constexpr int kWKry = 32;                   // doubles of one copy of the BiCGSTAB scalars: 16 per component
+enum { WW_OVF, WW_ROW, WW_GIVEUPS, WW_LIN_ITERS };
+static_assert(LDC_FV_WIDE_SCRATCH_LEN(8, 8) == kWWords + 2 * kWKry + 3 * kWS * 1, "scratch layout");
+static_assert(LDC_FV_WIDE_SCRATCH_LEN(1024, 1024) == kWWords + 2 * kWKry + 3 * kWS * kWMaxG, "scratch layout");
+
+struct FvWideArgs {
+  FvDesc d;
+  double* scr;
+  int G;                                    // work-groups of a sweep
+};
+
+struct FvKrylov {
+  double atol, nr2, rh, rh_prev, alpha, omega, beta;
+  bool act, brk, fin;
+  int its;
+};
+
+__device__ __forceinline__ long long* wide_words(const FvWideArgs& a) { return reinterpret_cast<long long*>(a.scr); }
+__device__ __forceinline__ double* wide_kry(const FvWideArgs& a, int par) { return a.scr + kWWords + kWKry * par; }
+__device__ __forceinline__ double* wide_slots(const FvWideArgs& a, int par) {
+  return a.scr + kWWords + 2 * kWKry + par * a.G * kWS;
+}
+__device__ __forceinline__ double* wide_rec_slots(const FvWideArgs& a) { return a.scr + kWWords + 2 * kWKry + 2 * a.G * kWS; }
+
+// the gate: true when the launch has nothing to do
+__device__ __forceinline__ bool wide_gate(const FvWideArgs& a) {
+  return a.d.ctrl[0] != 0 || a.d.ctrl[2] != 0 || wide_words(a)[WW_OVF] != 0;
+}
+
+// sums of K values over the work-group in a fixed order; every thread gets the totals.  Ends on a barrier, so `lds`
+// can be used again at once.
+template <int K>
+__device__ __forceinline__ void wide_block_sum(double (&a)[K], double* lds) {
+  static_assert(K <= kWS, "slot");
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a[k] += __shfl_xor(a[k], off);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) lds[w * kWS + k] = a[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < kWW; ++q) s += lds[q * kWS + k];
+    a[k] = s;
+  }
+  __syncthreads();
+}
+
+// the totals of entries first .. first + K - 1 over all G slots the launch before wrote: thread t takes slot t
+template <int K>
+__device__ __forceinline__ void wide_slot_sum(const double* slots, int G, int first, double (&a)[K], double* lds) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) a[k] = (int)threadIdx.x < G ? slots[threadIdx.x * kWS + first + k] : 0.0;
+  wide_block_sum(a, lds);
+}
+
+// this work-group's partial sums into entries first .. of its own slot
+template <int K>
+__device__ __forceinline__ void wide_slot_put(double* slots, int first, double (&a)[K], double* lds) {
+  wide_block_sum(a, lds);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) slots[blockIdx.x * kWS + first + k] = a[k];
+  }
+}
+
+__device__ __forceinline__ void wide_kry_load(const double* K, FvKrylov (&s)[2]) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const double* k = K + 16 * q;
+    s[q].atol = k[0]; s[q].nr2 = k[1]; s[q].rh = k[2]; s[q].rh_prev = k[3]; s[q].alpha = k[4]; s[q].omega = k[5];
+    s[q].beta = k[6]; s[q].act = k[7] != 0.0; s[q].brk = k[8] != 0.0; s[q].fin = k[9] != 0.0; s[q].its = (int)k[10];
+  }
+}
+
+// (work-group 0 alone writes the copy the NEXT launch reads)
+__device__ __forceinline__ void wide_kry_store(double* K, const FvKrylov (&s)[2]) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    double* k = K + 16 * q;
+    k[0] = s[q].atol; k[1] = s[q].nr2; k[2] = s[q].rh; k[3] = s[q].rh_prev; k[4] = s[q].alpha; k[5] = s[q].omega;
+    k[6] = s[q].beta; k[7] = s[q].act ? 1.0 : 0.0; k[8] = s[q].brk ? 1.0 : 0.0; k[9] = s[q].fin ? 1.0 : 0.0;
+    k[10] = (double)s[q].its;
+  }
+}
+
+// what fv_bicgstab does with the sums of its last sweep, at the top of iteration `it` (or after the last one)
+__device__ __forceinline__ void wide_kry_after_x(FvKrylov (&s)[2], const double (&s4)[4], int it) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    if (!s[q].act) continue;
+    if (s[q].fin) { s[q].act = false; s[q].its = it; continue; }
+    s[q].nr2 = s4[2 * q]; s[q].rh_prev = s[q].rh; s[q].rh = s4[2 * q + 1];
+    s[q].its = it;
+  }
+}
+
+// the test at the head of iteration `it`: converged or broken down -> finished with `it` iterations
+__device__ __forceinline__ void wide_kry_head(FvKrylov (&s)[2], int it) {
+  const double rhotol = 2.220446049250313e-16 * 2.220446049250313e-16;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    s[q].beta = 0;
+    if (!s[q].act) continue;
+    if (sqrt(s[q].nr2) < s[q].atol || fabs(s[q].rh) < rhotol || (it > 0 && fabs(s[q].omega) < rhotol)) {
+      s[q].act = false; s[q].its = it; continue;
+    }
+    if (it > 0) s[q].beta = (s[q].rh / s[q].rh_prev) * (s[q].alpha / s[q].omega);
+  }
+}
+
+__device__ __forceinline__ double fv_muscl(double r) {
+  return r > 0 ? fmax(0.0, fmin(fmin(2.0, 2.0 * r), 0.5 * (1 + r))) : 0.0;
+}
+
+// TVD deferred correction of a face (ldc_fv_kernel.inc: fv_dc; DESIGN.md FV-Q1)
+__device__ __forceinline__ double fv_dc(double m, double fP, double fN) {
+  double up, down, r;
+  const double F_low = m * (m >= 0 ? fP : fN);
+  if (m >= 0) {
+    up = fP; down = fN;
+    const double fW = 2 * fP - fN;
+    r = (fN - fP) / (fP - fW + 1e-12);
+  } else {
+    up = fN; down = fP;
+    const double fW = 2 * fN - fP;
+    r = (fP - fN) / (fN - fW + 1e-12);
+  }
+  const double psi = fv_muscl(r);
+  return m * (up + 0.5 * psi * (down - up)) - F_low;
+}
+
+// central-difference gradient with the reference's rules (ldc_fv_kernel.inc: fv_grad)
+__device__ __forceinline__ void fv_grad(const double* f, int c, int i, int j, int nx, int ny, double dx, double dy,
+                                        double& gx, double& gy) {
+  gx = 0.0; gy = 0.0;
+  if (c == 0) return;
+  const double fc = f[c];
+  double sx = 0.0, sy = 0.0;
+  int nxc = 0, nyc = 0;
+  if (i > 0 && c - 1 != 0) { sx += (f[c - 1] - fc) / (-dx); ++nxc; }
+  if (i < nx - 1) { sx += (f[c + 1] - fc) / dx; ++nxc; }
+  if (j > 0 && c - nx != 0) { sy += (f[c - nx] - fc) / (-dy); ++nyc; }
+  if (j < ny - 1) { sy += (f[c + nx] - fc) / dy; ++nyc; }
+  gx = nxc > 0 ? sx / nxc : 0.0;
+  gy = nyc > 0 ? sy / nyc : 0.0;
+}
+
+// y = (relaxed A) x at cell c: diag = aP / alpha_uv
+__device__ __forceinline__ double fv_matvec(const double* w, int n, const double* x, int c, int i, int j, int nx,
+                                            int ny, double inv_a) {
+  double y = (w[FV_AP * n + c] * inv_a) * x[c];
+  if (i > 0) y += w[FV_AW * n + c] * x[c - 1];
+  if (i < nx - 1) y += w[FV_AE * n + c] * x[c + 1];
+  if (j > 0) y += w[FV_AS * n + c] * x[c - nx];
+  if (j < ny - 1) y += w[FV_AN * n + c] * x[c + nx];
+  return y;
+}
+
+// geometry, coefficients and arrays of the trial, and this thread's cells: c = first, first + stride, ...
+struct WCtx {
+  const FvDesc& d;
+  int nx, ny, n, ldx, first, stride;
+  double dx, dy, V, rho, inv_a;
+  double *w, *fx, *fy;
+  __device__ __forceinline__ explicit WCtx(const FvWideArgs& a)
+      : d(a.d), nx(a.d.nx), ny(a.d.ny), n(nx * ny), ldx(nx + 1), first(blockIdx.x * kWT + threadIdx.x),
+        stride(a.G * kWT), dx(a.d.dx), dy(a.d.dy), V(dx * dy), rho(a.d.rho), inv_a(1.0 / a.d.alpha_uv), w(a.d.work),
+        fx(a.d.mdot), fy(a.d.mdot + ny * ldx) {}
+  __device__ __forceinline__ double* vec(FvVec k, int q = 0) const { return w + (k + q) * n; }
+};
+
+// ---- begin: the first launch of an enqueue (one work-group): the overflow word and the record row start at 0
+__global__ __launch_bounds__(64) void fv_wide_begin(FvWideArgs a) {
+  if (threadIdx.x == 0) {
+    wide_words(a)[WW_OVF] = 0;
+    wide_words(a)[WW_ROW] = 0;
+  }
+}
+
+// ---- 1. grad p, the five diagonals, the relaxed right-hand sides, the BiCGSTAB start; slot: |b_u|^2, |b_v|^2
+__global__ __launch_bounds__(kWT) void fv_wide_assemble(FvWideArgs a, int par) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  const WCtx x(a);
+  const FvDesc& d = x.d;
+  const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
+  double* const w = x.w;
+  const double *fx = x.fx, *fy = x.fy;
+  const double Dx = d.mu * x.dy / x.dx, Dy = d.mu * x.dx / x.dy, Dbx = d.mu * x.dy / (0.5 * x.dx),
+               Dby = d.mu * x.dx / (0.5 * x.dy), scale = (1.0 - d.alpha_uv) / d.alpha_uv;
+  const bool tvd = d.scheme == 1;
+  double b2[2] = {0.0, 0.0};
+  for (int c = x.first; c < n; c += x.stride) {
+    const int i = c % nx, j = c / nx;
+    double gx, gy;
+    fv_grad(d.p, c, i, j, nx, ny, x.dx, x.dy, gx, gy);
+    x.vec(FV_GPX)[c] = gx; x.vec(FV_GPY)[c] = gy;
+    double aP = 0.0, aW = 0.0, aE = 0.0, aS = 0.0, aN = 0.0, bu = 0.0, bv = 0.0;
+    const double uc = d.u[c], vc = d.v[c];
+    if (i > 0) {                 // west face: owner c-1, neighbour c
+      const double m = fx[j * ldx + i];
+      aP += Dx - fmin(m, 0.0); aW = -(fmax(m, 0.0) + Dx);
+      if (tvd) { bu += fv_dc(m, d.u[c - 1], uc); bv += fv_dc(m, d.v[c - 1], vc); }
+    } else {
+      aP += Dbx + (-fx[j * ldx]);
+    }
+    if (i < nx - 1) {            // east face: owner c
+      const double m = fx[j * ldx + i + 1];
+      aP += fmax(m, 0.0) + Dx; aE = fmin(m, 0.0) - Dx;
+      if (tvd) { bu -= fv_dc(m, uc, d.u[c + 1]); bv -= fv_dc(m, vc, d.v[c + 1]); }
+    } else {
+      aP += Dbx + fx[j * ldx + nx];
+    }
+    if (j > 0) {
+      const double m = fy[j * nx + i];
+      aP += Dy - fmin(m, 0.0); aS = -(fmax(m, 0.0) + Dy);
+      if (tvd) { bu += fv_dc(m, d.u[c - nx], uc); bv += fv_dc(m, d.v[c - nx], vc); }
+    } else {
+      aP += Dby + (-fy[i]);
+    }
+    if (j < ny - 1) {
+      const double m = fy[(j + 1) * nx + i];
+      aP += fmax(m, 0.0) + Dy; aN = fmin(m, 0.0) - Dy;
+      if (tvd) { bu -= fv_dc(m, uc, d.u[c + nx]); bv -= fv_dc(m, vc, d.v[c + nx]); }
+    } else {
+      const double mo = fy[ny * nx + i];
+      aP += Dby + mo;
+      bu += (Dby + mo) * d.ulid[i];
+    }
+    w[FV_AP * n + c] = aP; w[FV_AW * n + c] = aW; w[FV_AE * n + c] = aE;
+    w[FV_AS * n + c] = aS; w[FV_AN * n + c] = aN;
+    w[FV_BU * n + c] = bu; w[FV_BV * n + c] = bv;
+    const double hu = (bu - gx * x.V) + scale * aP * uc;      // Patankar relaxation (helpers.py:6-25)
+    const double hv = (bv - gy * x.V) + scale * aP * vc;
+    x.vec(FV_XU)[c] = 0.0; x.vec(FV_XV)[c] = 0.0;
+    x.vec(FV_RU)[c] = hu; x.vec(FV_RTU)[c] = hu; x.vec(FV_RV)[c] = hv; x.vec(FV_RTV)[c] = hv;
+    b2[0] += hu * hu; b2[1] += hv * hv;
+  }
+  wide_slot_put(wide_slots(a, par ^ 1), 0, b2, lds);
+}
+
+// ---- 2. the joint u / v BiCGSTAB, iteration `it`, one launch per sweep of fv_bicgstab.  Each reads the scalars of
+//         copy `par` and the slots `par`, and writes the copies par ^ 1.
+// p: the scalars from the sums of the launch before (it = 0: |b|^2 of assemble), the head test; p and phat
+__global__ __launch_bounds__(kWT) void fv_wide_bicg_p(FvWideArgs a, int it, int par) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  const WCtx x(a);
+  const int n = x.n;
+  FvKrylov s[2];
+  if (it == 0) {
+    double b2[2];
+    wide_slot_sum(wide_slots(a, par), a.G, 0, b2, lds);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const double bn = sqrt(b2[q]);
+      s[q].nr2 = b2[q]; s[q].rh = b2[q]; s[q].rh_prev = 0; s[q].alpha = 0; s[q].omega = 0; s[q].beta = 0; s[q].its = 0;
+      s[q].atol = x.d.lin_tol * bn;
+      s[q].act = bn != 0.0; s[q].brk = false; s[q].fin = false;
+    }
+  } else {
+    wide_kry_load(wide_kry(a, par), s);
+    double s4[4];
+    wide_slot_sum(wide_slots(a, par), a.G, 0, s4, lds);
+    wide_kry_after_x(s, s4, it);
+  }
+  wide_kry_head(s, it);
+  wide_kry_store(wide_kry(a, par ^ 1), s);
+  if (!s[0].act && !s[1].act) return;
+  for (int c = x.first; c < n; c += x.stride) {
+    const double dg = x.w[FV_AP * n + c] * x.inv_a;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (!s[q].act) continue;
+      double *p = x.vec(FV_PU, q), *r = x.vec(FV_RU, q);
+      const double pp = it > 0 ? (p[c] - s[q].omega * x.vec(FV_VU, q)[c]) * s[q].beta + r[c] : r[c];
+      p[c] = pp; x.vec(FV_PHU, q)[c] = pp / dg;
+    }
+  }
+}
+
+// v = A phat; slot: rtilde . v
+__global__ __launch_bounds__(kWT) void fv_wide_bicg_v(FvWideArgs a, int par) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  const WCtx x(a);
+  const int nx = x.nx, ny = x.ny, n = x.n;
+  FvKrylov s[2];
+  wide_kry_load(wide_kry(a, par), s);
+  wide_kry_store(wide_kry(a, par ^ 1), s);
+  if (!s[0].act && !s[1].act) return;
+  double s2[2] = {0, 0};
+  for (int c = x.first; c < n; c += x.stride) {
+    const int i = c % nx, j = c / nx;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (!s[q].act) continue;
+      const double y = fv_matvec(x.w, n, x.vec(FV_PHU, q), c, i, j, nx, ny, x.inv_a);
+      x.vec(FV_VU, q)[c] = y; s2[q] += x.vec(FV_RTU, q)[c] * y;
+    }
+  }
+  wide_slot_put(wide_slots(a, par ^ 1), 0, s2, lds);
+}
+
+// alpha; s = r - alpha v (into r) and shat
+__global__ __launch_bounds__(kWT) void fv_wide_bicg_s(FvWideArgs a, int par) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  const WCtx x(a);
+  const int n = x.n;
+  FvKrylov s[2];
+  wide_kry_load(wide_kry(a, par), s);
+  if (s[0].act || s[1].act) {
+    double s2[2];
+    wide_slot_sum(wide_slots(a, par), a.G, 0, s2, lds);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      s[q].brk = false;
+      if (!s[q].act) continue;
+      if (s2[q] == 0.0) { s[q].brk = true; continue; }
+      s[q].alpha = s[q].rh / s2[q];
+    }
+  }
+  wide_kry_store(wide_kry(a, par ^ 1), s);
+  if (!s[0].act && !s[1].act) return;
+  for (int c = x.first; c < n; c += x.stride) {
+    const double dg = x.w[FV_AP * n + c] * x.inv_a;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (!s[q].act || s[q].brk) continue;
+      double* r = x.vec(FV_RU, q);
+      const double sv = r[c] - s[q].alpha * x.vec(FV_VU, q)[c];
+      r[c] = sv; x.vec(FV_SHU, q)[c] = sv / dg;
+    }
+  }
+}
+
+// t = A shat; slot: s.s, t.s, t.t per component
+__global__ __launch_bounds__(kWT) void fv_wide_bicg_t(FvWideArgs a, int par) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  const WCtx x(a);
+  const int nx = x.nx, ny = x.ny, n = x.n;
+  FvKrylov s[2];
+  wide_kry_load(wide_kry(a, par), s);
+  wide_kry_store(wide_kry(a, par ^ 1), s);
+  if (!s[0].act && !s[1].act) return;
+  double s3[6] = {0, 0, 0, 0, 0, 0};
+  for (int c = x.first; c < n; c += x.stride) {
+    const int i = c % nx, j = c / nx;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (!s[q].act || s[q].brk) continue;
+      const double t = fv_matvec(x.w, n, x.vec(FV_SHU, q), c, i, j, nx, ny, x.inv_a), sv = x.vec(FV_RU, q)[c];
+      x.vec(FV_TU, q)[c] = t; s3[3 * q] += sv * sv; s3[3 * q + 1] += t * sv; s3[3 * q + 2] += t * t;
+    }
+  }
+  wide_slot_put(wide_slots(a, par ^ 1), 0, s3, lds);
+}
+
+// omega (or the early finish on |s|); x and r; slot: r.r, rtilde.r per component
+__global__ __launch_bounds__(kWT) void fv_wide_bicg_x(FvWideArgs a, int it, int par) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  const WCtx x(a);
+  const int n = x.n;
+  FvKrylov s[2];
+  wide_kry_load(wide_kry(a, par), s);
+  if (s[0].act || s[1].act) {
+    double s3[6];
+    wide_slot_sum(wide_slots(a, par), a.G, 0, s3, lds);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      s[q].fin = false;                      // fin: converged on |s|: x += alpha phat and stop
+      if (!s[q].act) continue;
+      if (s[q].brk) { s[q].act = false; s[q].its = it + 1; continue; }
+      if (sqrt(s3[3 * q]) < s[q].atol) { s[q].fin = true; continue; }
+      s[q].omega = s3[3 * q + 1] / s3[3 * q + 2];
+    }
+  }
+  wide_kry_store(wide_kry(a, par ^ 1), s);
+  if (!s[0].act && !s[1].act) return;
+  double s4[4] = {0, 0, 0, 0};
+  for (int c = x.first; c < n; c += x.stride) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (!s[q].act) continue;
+      double *xs = x.vec(FV_XU, q), *ph = x.vec(FV_PHU, q);
+      if (s[q].fin) xs[c] += s[q].alpha * ph[c];
+      else {
+        double* rs = x.vec(FV_RU, q);
+        double xn = xs[c]; xn += s[q].alpha * ph[c]; xn += s[q].omega * x.vec(FV_SHU, q)[c]; xs[c] = xn;
+        const double r = rs[c] - s[q].omega * x.vec(FV_TU, q)[c];
+        rs[c] = r; s4[2 * q] += r * r; s4[2 * q + 1] += x.vec(FV_RTU, q)[c] * r;
+      }
+    }
+  }
+  wide_slot_put(wide_slots(a, par ^ 1), 0, s4, lds);
+}
+
+// linfinish (one work-group), after `nb` = min(lin_budget, max_lin_iters) iterations: the last sums; a component still
+// active at nb = max_lin_iters is the accepted give-up, at nb < max_lin_iters the overflow (nothing but work vectors
+// has been written so far).  The counters wait in the scratch words for the record launch.
+__global__ __launch_bounds__(kWT) void fv_wide_linfinish(FvWideArgs a, int nb, int par) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  FvKrylov s[2];
+  wide_kry_load(wide_kry(a, par), s);
+  double s4[4];
+  wide_slot_sum(wide_slots(a, par), a.G, 0, s4, lds);
+  wide_kry_after_x(s, s4, nb);
+  long long giveups = 0, lin_iters = 0;
+  bool overflow = false;
+  if (nb < a.d.maxit) {
+    wide_kry_head(s, nb);                   // (what iteration nb would find first)
+    overflow = s[0].act || s[1].act;
+  } else {
+    giveups = (s[0].act ? 1 : 0) + (s[1].act ? 1 : 0);
+  }
+  lin_iters = s[0].its + s[1].its;
+  if (threadIdx.x == 0) {
+    long long* w = wide_words(a);
+    if (overflow) w[WW_OVF] = 1;
+    else { w[WW_GIVEUPS] = giveups; w[WW_LIN_ITERS] = lin_iters; }
+  }
+}
+
+// ---- 3. Rhie-Chow face velocities, mdot*, rhs_p = -div mdot* (entry 0 = 0); slot: the sum of rhs_p, whose negative
+//         is the cell-0 entry of the pinned solve (the first GEMM puts it in as it reads C)
+__global__ __launch_bounds__(kWT) void fv_wide_faces(FvWideArgs a, int par) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  const WCtx x(a);
+  const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
+  double* const w = x.w;
+  double *fx = x.fx, *fy = x.fy;
+  const double V = x.V;
+  double csum[1] = {0.0};
+  for (int c = x.first; c < n; c += x.stride) {
+    const int i = c % nx, j = c / nx;
+    const double DP = V / (w[FV_AP * n + c] + 1e-14);
+    double flux[4];                      // W, E, S, N in +x / +y
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      const bool xdir = f < 2;
+      const int o = f == 0 ? c - 1 : f == 1 ? c + 1 : f == 2 ? c - nx : c + nx;
+      const bool wall = f == 0 ? i == 0 : f == 1 ? i == nx - 1 : f == 2 ? j == 0 : j == ny - 1;
+      if (wall) { flux[f] = 0.0; continue; }     // boundary velocity has no normal component
+      const int P = (f == 0 || f == 2) ? o : c, N = (f == 0 || f == 2) ? c : o;
+      const double g = 0.5;
+      const double* st = xdir ? x.vec(FV_XU) : x.vec(FV_XV);
+      const double* gp = xdir ? x.vec(FV_GPX) : x.vec(FV_GPY);
+      const double DPc = P == c ? DP : V / (w[FV_AP * n + P] + 1e-14);
+      const double DNc = N == c ? DP : V / (w[FV_AP * n + N] + 1e-14);
+      const double Uf = (1.0 - g) * st[P] + g * st[N];
+      const double gbar = g * gp[N] + (1.0 - g) * gp[P];          // interpolate_to_face(grad_p)
+      const double gin = (1.0 - g) * gp[P] + g * gp[N];           // rhie_chow.py's inline interpolation (FV-Q2)
+      const double Df = g * DNc + (1.0 - g) * DPc;
+      flux[f] = x.rho * ((Uf - Df * (gbar - gin)) * (xdir ? x.dy : x.dx));
+    }
+    if (i == 0) fx[j * ldx] = flux[0];
+    fx[j * ldx + i + 1] = flux[1];
+    if (j == 0) fy[i] = flux[2];
+    fy[(j + 1) * nx + i] = flux[3];
+    const double rhs = c == 0 ? 0.0 : -((flux[1] - flux[0]) + (flux[3] - flux[2]));
+    x.vec(FV_C)[c] = rhs;
+    csum[0] += rhs;
+  }
+  wide_slot_put(wide_slots(a, par ^ 1), 0, csum, lds);
+}
+
+// ---- 4. one GEMM of the fast diagonalisation: C[r][c] = sum_k A(r, k) B(k, c) as fv_gemm, one wave per 16 x 16 tile,
+//         four tiles per work-group, operands from L2 with zero fill at the edges.  FIRST: B is rhs_p, whose entry 0 is
+//         minus the sum the launch before left in the slots.  SCALE: the epilogue / (ax lamx + ay lamy), zero mode dropped.
+struct FvWideGemm {
+  const double *A, *B;
+  double* C;
+  int sar, sak, sbk, sbc, M, N, K;
+};
+
+template <bool FIRST, bool SCALE>
+__global__ __launch_bounds__(kWT) void fv_wide_gemm(FvWideArgs a, FvWideGemm g, int par) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  double b00 = 0.0;
+  if (FIRST) {
+    double csum[1];
+    wide_slot_sum(wide_slots(a, par), a.G, 0, csum, lds);
+    b00 = -csum[0];
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int M = g.M, N = g.N, K = g.K;
+  const int tn = (N + 15) >> 4, tiles = ((M + 15) >> 4) * tn;
+  const int t = blockIdx.x * kWW + w;
+  if (t >= tiles) return;
+  const int r0 = (t / tn) * 16, c0 = (t % tn) * 16;
+  const int ar = r0 + (lane & 15), bc = c0 + (lane & 15), kq = lane >> 4;
+  v4d acc = {0.0, 0.0, 0.0, 0.0};
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    const int k = k0 + kq;
+    const double av = (ar < M && k < K) ? g.A[ar * g.sar + k * g.sak] : 0.0;
+    double bv = (bc < N && k < K) ? g.B[k * g.sbk + bc * g.sbc] : 0.0;
+    if (FIRST && k == 0 && bc == 0) bv = b00;
+    acc = MFMA_F64(av, bv, acc);
+  }
+  const double ax = a.d.dy / a.d.dx, ay = a.d.dx / a.d.dy;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int row = r0 + (lane >> 4) + 4 * q, col = c0 + (lane & 15);
+    if (row < M && col < N) {
+      double val = acc[q];
+      if (SCALE) val = (row == 0 && col == 0) ? 0.0 : val * (1.0 / (ax * a.d.lamx[col] + ay * a.d.lamy[row]));
+      g.C[row * N + col] = val;
+    }
+  }
+}
+
+// ---- 5. u' = -D grad p', u = u* + u', p += alpha_p p'; record sums 0 .. 6 of this work-group
+__global__ __launch_bounds__(kWT) void fv_wide_correct(FvWideArgs a) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  const WCtx x(a);
+  const FvDesc& d = x.d;
+  const int nx = x.nx, ny = x.ny, n = x.n;
+  const double y0 = x.vec(FV_Y)[0];
+  double part[7] = {0, 0, 0, 0, 0, 0, 0};
+  for (int c = x.first; c < n; c += x.stride) {
+    const int i = c % nx, j = c / nx;
+    double gx, gy;
+    fv_grad(x.vec(FV_Y), c, i, j, nx, ny, x.dx, x.dy, gx, gy);
+    const double D = x.V / (x.w[FV_AP * n + c] + 1e-14);
+    const double upc = -D * gx, vpc = -D * gy;
+    const double un = x.vec(FV_XU)[c] + upc, vn = x.vec(FV_XV)[c] + vpc, uo = d.u[c], vo = d.v[c];
+    const double pp = x.vec(FV_Y)[c] - y0;
+    d.p[c] += d.alpha_p * pp;
+    d.u[c] = un; d.v[c] = vn; x.vec(FV_UP)[c] = upc; x.vec(FV_VP)[c] = vpc;
+    part[0] += (un - uo) * (un - uo); part[1] += uo * uo;
+    part[2] += (vn - vo) * (vn - vo); part[3] += vo * vo;
+    part[4] += upc * upc; part[5] += vpc * vpc; part[6] += un * un + vn * vn;
+  }
+  wide_slot_put(wide_rec_slots(a), 0, part, lds);
+}
+
+// ---- 6. mdot += rho interp(u', v') . S (walls: rho u'_P |S|, FV-Q4); vorticity with ghost cells; record sum 8
+__global__ __launch_bounds__(kWT) void fv_wide_fluxvort(FvWideArgs a) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  const WCtx x(a);
+  const FvDesc& d = x.d;
+  const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
+  double *fx = x.fx, *fy = x.fy;
+  const double dx = x.dx, dy = x.dy, rho = x.rho;
+  double part[1] = {0.0};
+  for (int c = x.first; c < n; c += x.stride) {
+    const int i = c % nx, j = c / nx;
+    const double *up = x.vec(FV_UP), *vp = x.vec(FV_VP);
+    const double ue = i < nx - 1 ? 0.5 * up[c + 1] + (1.0 - 0.5) * up[c] : up[c];
+    const double vn = j < ny - 1 ? 0.5 * vp[c + nx] + (1.0 - 0.5) * vp[c] : vp[c];
+    if (i == 0) fx[j * ldx] += rho * (up[c] * dy);
+    fx[j * ldx + i + 1] += rho * (ue * dy);
+    if (j == 0) fy[i] += rho * (vp[c] * dx);
+    fy[(j + 1) * nx + i] += rho * (vn * dx);
+    const double vE = i < nx - 1 ? d.v[c + 1] : -d.v[c], vW = i > 0 ? d.v[c - 1] : -d.v[c];
+    const double uN = j < ny - 1 ? d.u[c + nx] : 2 * d.lid - d.u[c], uS = j > 0 ? d.u[c - nx] : -d.u[c];
+    const double wc = (vE - vW) / (2 * dx) - (uN - uS) / (2 * dy);
+    x.vec(FV_OMEGA)[c] = wc;
+    part[0] += wc * wc;
+  }
+  wide_slot_put(wide_rec_slots(a), 8, part, lds);
+}
+
+// ---- 7a. |div mdot|^2 and |grad omega|^2: record sums 7 and 9
+__global__ __launch_bounds__(kWT) void fv_wide_sums(FvWideArgs a) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  const WCtx x(a);
+  const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
+  const double *fx = x.fx, *fy = x.fy;
+  double p7[1] = {0.0}, p9[1] = {0.0};
+  for (int c = x.first; c < n; c += x.stride) {
+    const int i = c % nx, j = c / nx;
+    const double* om = x.vec(FV_OMEGA);
+    const double dv = (fx[j * ldx + i + 1] - fx[j * ldx + i]) + (fy[(j + 1) * nx + i] - fy[j * nx + i]);
+    p7[0] += dv * dv;
+    const double wc = om[c];
+    const double wE = i < nx - 1 ? om[c + 1] : -wc, wW = i > 0 ? om[c - 1] : -wc;
+    const double wN = j < ny - 1 ? om[c + nx] : -wc, wS = j > 0 ? om[c - nx] : -wc;
+    const double gx = (wE - wW) / (2 * x.dx), gy = (wN - wS) / (2 * x.dy);
+    p9[0] += gx * gx + gy * gy;
+  }
+  wide_slot_put(wide_rec_slots(a), 7, p7, lds);
+  wide_slot_put(wide_rec_slots(a), 9, p9, lds);
+}
+
+// ---- 7b. record (one work-group): the record row, the latch and ctrl[0 .. 5], once per iteration
+__global__ __launch_bounds__(kWT) void fv_wide_record(FvWideArgs a) {
+  __shared__ double lds[kWW * kWS];
+  if (wide_gate(a)) return;
+  const FvDesc& d = a.d;
+  double part[kWS];
+  wide_slot_sum(wide_rec_slots(a), a.G, 0, part, lds);
+  const double V = d.dx * d.dy;
+  const double chu = sqrt(part[0]) / (sqrt(part[1]) + 1e-12), chv = sqrt(part[2]) / (sqrt(part[3]) + 1e-12);
+  const double rel = chu > chv ? chu : chv;
+  if (threadIdx.x == 0) {
+    long long* w = wide_words(a);
+    const long long k = w[WW_ROW], iter = d.ctrl[1];
+    if (k >= 0 && k < d.rec_cap) {
+      double* row = d.rec + k * LDC_FV_REC_LEN;
+      row[0] = rel; row[1] = sqrt(part[4]); row[2] = sqrt(part[5]); row[3] = sqrt(part[7]);
+      row[4] = 0.5 * (part[6] * V); row[5] = 0.5 * (part[8] * V); row[6] = 0.5 * (part[9] * V); row[7] = 0.0;
+    }
+    w[WW_ROW] = k + 1;
+    if (rel != rel) d.ctrl[2] = 1;
+    else if (iter >= d.warmup && rel < d.tol) d.ctrl[0] = 1;
+    d.ctrl[1] = iter + 1;
+    d.ctrl[3] += w[WW_GIVEUPS]; d.ctrl[4] += w[WW_LIN_ITERS]; d.ctrl[5] += 2;
+  }
+}
+
+inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+std::mutex g_wide_mutex;
+hipStream_t g_wide_stream[64] = {};
+
+// this unit's private non-blocking stream of the current device (call with g_wide_mutex held)
+hipError_t wide_stream(hipStream_t* out) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+  if (g_wide_stream[dev] == nullptr) {
+    e = hipStreamCreateWithFlags(&g_wide_stream[dev], hipStreamNonBlocking);
+    if (e != hipSuccess) return e;
+  }
+  *out = g_wide_stream[dev];
+  return hipSuccess;
+}
+
+// a small synchronous copy on that stream (off the legacy stream, as the library's other status reads)
+hipError_t wide_copy_now(void* dst, const void* src, size_t bytes) {
+  std::lock_guard<std::mutex> lock(g_wide_mutex);
+  hipStream_t st = nullptr;
+  hipError_t e = wide_stream(&st);
+  if (e != hipSuccess) return e;
+  e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+  const hipError_t w = hipStreamSynchronize(st);
+  return e != hipSuccess ? e : w;
+}
+
+}  // namespace
+
+struct ldc_fv_wide {
+  FvWideArgs a;
+  int device;
+  int graph;                                 // replay ONE captured iteration per budget (ldc_fv_wide_set_graph)
+  std::vector<std::pair<int, hipGraphExec_t>> graphs;        // (BiCGSTAB iterations, the iteration's graph), kept until destroy
+  hipEvent_t done;                           // behind the last graph launch: no graph is destroyed in flight
+};
+
+namespace {
+
+#define WIDE_LAUNCH(kernel, grid, block, ...)                                        \
+  do {                                                                               \
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);         \
+    const hipError_t e_ = hipGetLastError();                                         \
+    if (e_ != hipSuccess) return (int)e_;                                            \
+  } while (0)
+
+// the launches of ONE iteration with `nb` BiCGSTAB iterations; `par` alternates launch by launch
+int wide_iteration(const ldc_fv_wide* h, int nb, hipStream_t st) {
+  const FvWideArgs& a = h->a;
+  const FvDesc& d = a.d;
+  const int nx = d.nx, ny = d.ny, n = nx * ny, G = a.G;
+  int par = 0;
+  WIDE_LAUNCH(fv_wide_assemble, G, kWT, a, par); par ^= 1;
+  for (int it = 0; it < nb; ++it) {
+    WIDE_LAUNCH(fv_wide_bicg_p, G, kWT, a, it, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_bicg_v, G, kWT, a, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_bicg_s, G, kWT, a, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_bicg_t, G, kWT, a, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_bicg_x, G, kWT, a, it, par); par ^= 1;
+  }
+  WIDE_LAUNCH(fv_wide_linfinish, 1, kWT, a, nb, par); par ^= 1;
+  WIDE_LAUNCH(fv_wide_faces, G, kWT, a, par); par ^= 1;
+  double* w = d.work;
+  double *Cv = w + (int64_t)FV_C * n, *W1 = w + (int64_t)FV_W1 * n, *W2 = w + (int64_t)FV_W2 * n,
+         *Y = w + (int64_t)FV_Y * n;
+  const int tiles = ((ny + 15) / 16) * ((nx + 15) / 16), gg = (tiles + kWW - 1) / kWW;
+  const FvWideGemm g1 = {d.Qy, Cv, W1, 1, ny, nx, 1, ny, nx, ny};     // W1 = Qy^T C
+  const FvWideGemm g2 = {W1, d.Qx, W2, nx, 1, nx, 1, ny, nx, nx};     // W2 = W1 Qx / Lambda
+  const FvWideGemm g3 = {d.Qy, W2, W1, ny, 1, nx, 1, ny, nx, ny};     // W1 = Qy W2
+  const FvWideGemm g4 = {W1, d.Qx, Y, nx, 1, 1, nx, ny, nx, nx};      // Y = W1 Qx^T
+  WIDE_LAUNCH((fv_wide_gemm<true, false>), gg, kWT, a, g1, par);
+  WIDE_LAUNCH((fv_wide_gemm<false, true>), gg, kWT, a, g2, par);
+  WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, g3, par);
+  WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, g4, par);
+  WIDE_LAUNCH(fv_wide_correct, G, kWT, a);
+  WIDE_LAUNCH(fv_wide_fluxvort, G, kWT, a);
+  WIDE_LAUNCH(fv_wide_sums, G, kWT, a);
+  WIDE_LAUNCH(fv_wide_record, 1, kWT, a);
+  return 0;
+}
+
+// Budgets above this are launched one by one: the graph of an iteration has 11 + 5 nb nodes
+constexpr int kWideGraphMaxNb = 64;
+
+// The graph of ONE iteration with nb BiCGSTAB iterations: a linear chain captured on this unit's private stream (relaxed
+// mode: kernel launches only, no call elsewhere needs to be prohibited meanwhile), instantiated once and kept.
+int wide_graph(ldc_fv_wide* h, int nb, hipGraphExec_t* out) {
+  for (const auto& g : h->graphs)
+    if (g.first == nb) { *out = g.second; return 0; }
+  std::lock_guard<std::mutex> lock(g_wide_mutex);
+  hipStream_t cs = nullptr;
+  hipError_t e = wide_stream(&cs);
+  if (e != hipSuccess) return (int)e;
+  e = hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed);
+  if (e != hipSuccess) return (int)e;
+  const int rc = wide_iteration(h, nb, cs);
+  hipGraph_t g = nullptr;
+  const hipError_t ce = hipStreamEndCapture(cs, &g);
+  if (rc != 0 || ce != hipSuccess) {
+    if (g) (void)hipGraphDestroy(g);
+    return rc != 0 ? rc : (int)ce;
+  }
+  hipGraphExec_t exec = nullptr;
+  const hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  if (ie != hipSuccess) return (int)ie;
+  h->graphs.emplace_back(nb, exec);
+  *out = exec;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ldc_fv_wide_create(const struct ldc_fv_problem* pr, double* scratch, int64_t scratch_len, ldc_fv_wide** out) {
+  if (!pr || !out) return LDC_E_ARG;
+  *out = nullptr;
+  if (pr->nx < LDC_FV_MIN_N || pr->nx > LDC_FV_WIDE_MAX_N || pr->ny < LDC_FV_MIN_N || pr->ny > LDC_FV_WIDE_MAX_N) return LDC_E_ARG;
+  if (pr->scheme != 0 && pr->scheme != 1) return LDC_E_ARG;
+  if (pr->rec_cap < 1 || pr->warmup < 0 || pr->max_lin_iters < 1) return LDC_E_ARG;
+  if (!(pr->dx > 0) || !(pr->dy > 0) || !(pr->rho > 0) || !(pr->mu > 0)) return LDC_E_ARG;
+  if (!(pr->alpha_uv > 0 && pr->alpha_uv <= 1) || !(pr->alpha_p > 0 && pr->alpha_p <= 1)) return LDC_E_ARG;
+  if (!(pr->lin_tol > 0) || !(pr->tol >= 0)) return LDC_E_ARG;
+  const void* req[] = {pr->ulid, pr->Qx, pr->lamx, pr->Qy, pr->lamy, pr->u, pr->v, pr->p, pr->mdot, pr->work,
+                       pr->rec, pr->ctrl, scratch};
+  for (const void* q : req) if (!q) return LDC_E_ARG;
+  if (scratch_len < LDC_FV_WIDE_SCRATCH_LEN(pr->nx, pr->ny)) return LDC_E_ARG;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
+  ldc_fv_wide* s = new (std::nothrow) ldc_fv_wide;
+  if (!s) return LDC_E_STATE;
+  FvDesc& h = s->a.d;
+  h.nx = pr->nx; h.ny = pr->ny; h.scheme = pr->scheme; h.rec_cap = pr->rec_cap; h.warmup = pr->warmup;
+  h.maxit = pr->max_lin_iters;
+  h.dx = pr->dx; h.dy = pr->dy; h.rho = pr->rho; h.mu = pr->mu; h.alpha_uv = pr->alpha_uv; h.alpha_p = pr->alpha_p;
+  h.lin_tol = pr->lin_tol; h.tol = pr->tol; h.lid = pr->lid_velocity;
+  h.ulid = pr->ulid; h.Qx = pr->Qx; h.lamx = pr->lamx; h.Qy = pr->Qy; h.lamy = pr->lamy;
+  h.u = pr->u; h.v = pr->v; h.p = pr->p; h.mdot = pr->mdot; h.work = pr->work; h.rec = pr->rec;
+  h.ctrl = reinterpret_cast<long long*>(pr->ctrl);
+  s->a.scr = scratch;
+  s->a.G = (int)LDC_FV_WIDE_GROUPS(pr->nx, pr->ny);
+  s->device = dev;
+  s->graph = LDC_FV_WIDE_GRAPH_DEFAULT;
+  s->done = nullptr;
+  *out = s;
+  return 0;
+}
+
+int ldc_fv_wide_destroy(ldc_fv_wide* h) {
+  if (!h) return LDC_E_STATE;
+  if (h->done) {
+    (void)hipEventSynchronize(h->done);
+    (void)hipEventDestroy(h->done);
+  }
+  for (const auto& g : h->graphs) (void)hipGraphExecDestroy(g.second);
+  delete h;
+  return 0;
+}
+
+int ldc_fv_wide_set_graph(ldc_fv_wide* h, int on) {
+  if (!h) return LDC_E_STATE;
+  if (on != 0 && on != 1) return LDC_E_ARG;
+  h->graph = on;
+  return 0;
+}
+
+int ldc_fv_wide_enqueue(ldc_fv_wide* h, int n_iters, int lin_budget, void* stream) {
+  if (!h) return LDC_E_STATE;
+  if (n_iters < 1 || n_iters > h->a.d.rec_cap || lin_budget < 1) return LDC_E_ARG;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
+  if (dev != h->device) return LDC_E_STATE;
+  hipStream_t st = as_stream(stream);
+  const int nb = lin_budget < h->a.d.maxit ? lin_budget : h->a.d.maxit;
+  hipGraphExec_t exec = nullptr;
+  if (h->graph && nb <= kWideGraphMaxNb) {
+    const int rc = wide_graph(h, nb, &exec);
+    if (rc != 0) return rc;
+    if (!h->done) {
+      const hipError_t e = hipEventCreateWithFlags(&h->done, hipEventDisableTiming);
+      if (e != hipSuccess) return (int)e;
+    }
+  }
+  WIDE_LAUNCH(fv_wide_begin, 1, 64, h->a);
+  for (int k = 0; k < n_iters; ++k) {
+    if (exec) {
+      const hipError_t e = hipGraphLaunch(exec, st);
+      if (e != hipSuccess) return (int)e;
+    } else {
+      const int rc = wide_iteration(h, nb, st);
+      if (rc != 0) return rc;
+    }
+  }
+  if (exec) {
+    const hipError_t e = hipEventRecord(h->done, st);
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
+}
+
+int ldc_fv_wide_launches(const ldc_fv_wide* h, int lin_budget) {
+  if (!h || lin_budget < 1) return LDC_E_ARG;
+  return 11 + 5 * (lin_budget < h->a.d.maxit ? lin_budget : h->a.d.maxit);
+}
+
+int ldc_fv_wide_status(ldc_fv_wide* h) {
+  if (!h) return LDC_E_STATE;
+  long long nan_flag = 0, ovf = 0;
+  hipError_t e = wide_copy_now(&nan_flag, h->a.d.ctrl + 2, sizeof(nan_flag));
+  if (e != hipSuccess) return (int)e;
+  e = wide_copy_now(&ovf, reinterpret_cast<long long*>(h->a.scr) + WW_OVF, sizeof(ovf));
+  if (e != hipSuccess) return (int)e;
+  return nan_flag ? LDC_FV_E_NAN : (ovf ? LDC_FV_WIDE_E_BUDGET : 0);
+}
+
+}  // extern "C"

@@ -151,6 +151,8 @@ def batch_key(cfg: dict) -> tuple:
     sizes and depths form a batch of their own (BatchedFVFSGSolver)."""
     sv = cfg["solver"]
     if sv["_target_"] in FV_TARGETS:
+        if sv.get("mapping", "cu") == "chip":     # a chip trial takes every CU: it never shares a launch (batch_sizes)
+            return (sv["_target_"], "chip")
         return (sv["_target_"],)
     return (sv["_target_"], int(cfg["N"]), int(sv.get("n_levels", 0)), bool(sv.get("diagnostics", True)),
             int(sv.get("nx", cfg["N"])), int(sv.get("ny", cfg["N"])))
@@ -173,6 +175,8 @@ def batch_sizes(key: tuple, count: int, max_batch: int, given: bool) -> list:
     256 for finite-volume trials and for the spectral sizes the trial-per-CU kernel holds (M = N + 1 <= 44)."""
     target = key[0]
     if target not in (SG, FSG) + FV_TARGETS or count < 2 or max_batch <= 1:
+        return []
+    if target in FV_TARGETS and key[1:] == ("chip",):
         return []
     if given or (target not in FV_TARGETS and int(key[1]) + 1 > 44):
         cap = max_batch

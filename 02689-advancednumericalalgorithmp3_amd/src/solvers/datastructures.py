@@ -102,9 +102,15 @@ class FVParameters(Parameters):
     acceleration: str = "none"
     anderson_depth: int = 5
     anderson_start: int = 10
+    # how a trial is laid on the device: "cu" (one work-group on one CU for its whole life; batches of them fill the
+    # chip) or "chip" (one kernel launch per phase over all CUs, 8 ... 1024 cells per axis, lone trials only), and the
+    # BiCGSTAB iterations the first chunk of a "chip" solve carries per SIMPLE iteration (doubled when a solve needs
+    # more).  Neither changes what is computed beyond rounding: they stay out of MLflow, like device
+    mapping: str = "cu"
+    linear_budget: int = 12
 
     def to_mlflow(self) -> dict:
-        skip = {"device", "check_every", "vortex_metrics"}
+        skip = {"device", "check_every", "vortex_metrics", "mapping", "linear_budget"}
         return {k: _mlflow_scalar(v) for k, v in self.as_dict().items() if k not in skip}
 
 

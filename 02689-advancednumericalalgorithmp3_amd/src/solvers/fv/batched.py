@@ -77,6 +77,9 @@ class BatchedFVSolver:
     def __init__(self, trials: list):
         if not trials:
             raise ValueError(f"{type(self).__name__} needs at least one trial")
+        for t in trials:
+            if t.get("mapping", "cu") == "chip":
+                raise ValueError("mapping='chip' inside a batch: a chip trial takes every CU, run it on its own")
         self.solvers = []
         try:
             for t in trials:

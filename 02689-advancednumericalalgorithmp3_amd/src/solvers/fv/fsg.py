@@ -65,6 +65,7 @@ class FVFSGSolver(FVSolver):
     fine.  ``metrics.wall_time_seconds`` is the time of the whole sequence."""
 
     Parameters = FVFSGParameters
+    _needs_cu_handle = "an FSG level"         # every level is prolonged through its one-CU handle
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)

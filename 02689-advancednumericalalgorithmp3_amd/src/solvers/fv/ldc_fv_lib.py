@@ -18,6 +18,8 @@ PROLONG_LAUNCH_MAX = 128
 ANDERSON_LAUNCH_MAX, ANDERSON_MAX_DEPTH, ANDERSON_STATE_LEN = 96, 16, 4
 ASTATE_COLUMNS, ASTATE_POSITION, ASTATE_SEEN, ASTATE_FALLBACKS = range(4)
 E_NAN = -5
+WIDE_MAX_N = 1024
+E_BUDGET = -6                  # ldc_fv_wide_status: the last enqueue ran out of BiCGSTAB launches (LDC_FV_WIDE_E_BUDGET)
 CTRL_DONE, CTRL_ITER, CTRL_NAN, CTRL_GIVEUP, CTRL_LIN_ITERS, CTRL_SOLVES = range(6)
 # slots of a result block of ldc_fv_post_enqueue (LDC_FV_POST_*)
 (POST_PSI_MIN, POST_OMEGA_CENTER, POST_OMEGA_MAX, POST_PSI_BR, POST_PSI_BL, POST_PSI_TL, POST_PSI_MIN_CELL,
@@ -54,7 +56,8 @@ class Anderson(C.Structure):
 # every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
            "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
-           "ldc_fv_anderson_enqueue")
+           "ldc_fv_anderson_enqueue", "ldc_fv_wide_create", "ldc_fv_wide_destroy", "ldc_fv_wide_enqueue",
+           "ldc_fv_wide_launches", "ldc_fv_wide_status", "ldc_fv_wide_set_graph")
 
 _bound = None
 
@@ -72,13 +75,23 @@ def anderson_hist_len(nx: int, ny: int, depth: int) -> int:
     return (2 * depth + 3) * (3 * nx * ny + faces(nx, ny))
 
 
+def wide_groups(nx: int, ny: int) -> int:
+    """Work-groups of a cell sweep of the chip mapping (LDC_FV_WIDE_GROUPS)."""
+    return min(256, (nx * ny + 255) // 256)
+
+
+def wide_scratch_len(nx: int, ny: int) -> int:
+    """LDC_FV_WIDE_SCRATCH_LEN: control words, two copies of the BiCGSTAB scalars, three sets of slot sums."""
+    return 80 + 30 * wide_groups(nx, ny)
+
+
 def lib() -> C.CDLL:
     """The shared library with the FV entry points' signatures set (raises if it has not been built)."""
     global _bound
     L = _L.lib()
     if _bound is None:
         missing = [name for name in EXPORTS if not hasattr(L, name)]
-        if missing:               # (ldc_fv_prolong_enqueue and ldc_fv_anderson_enqueue came without a new version number)
+        if missing:               # (the entry points after ldc_fv_post_enqueue came without a new version number)
             raise _L.LdcError(f"libldc_hip.so is out of date: it does not export {', '.join(missing)}; rebuild it")
         L.ldc_fv_version.restype = C.c_int
         L.ldc_fv_create.argtypes = [C.POINTER(Problem), C.POINTER(_dp)]
@@ -90,6 +103,12 @@ def lib() -> C.CDLL:
         L.ldc_fv_post_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(Post), C.c_int, _dp]
         L.ldc_fv_prolong_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(_dp), C.c_int, _dp]
         L.ldc_fv_anderson_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(Anderson), C.c_int, C.c_int, _dp]
+        L.ldc_fv_wide_create.argtypes = [C.POINTER(Problem), _dp, C.c_int64, C.POINTER(_dp)]
+        L.ldc_fv_wide_destroy.argtypes = [_dp]
+        L.ldc_fv_wide_enqueue.argtypes = [_dp, C.c_int, C.c_int, _dp]
+        L.ldc_fv_wide_launches.argtypes = [_dp, C.c_int]
+        L.ldc_fv_wide_status.argtypes = [_dp]
+        L.ldc_fv_wide_set_graph.argtypes = [_dp, C.c_int]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L

@@ -26,6 +26,7 @@ log = logging.getLogger(__name__)
 SCHEMES = {"Upwind": 0, "TVD": 1}
 VORTEX_METRICS = ("host", "device")
 ACCELERATIONS = ("none", "anderson")
+MAPPINGS = ("cu", "chip")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
 
 
@@ -97,6 +98,8 @@ def postprocess(trials):
     from solvers.spectral import ldc_lib
     if not trials:
         return
+    for s in trials:
+        s._require_cu_handle("postprocess")
     dev = trials[0].device
     index = torch.cuda.current_device() if dev.index is None else dev.index
     with torch.cuda.device(dev):
@@ -139,6 +142,7 @@ def prolong(pairs):
     index = torch.cuda.current_device() if dev.index is None else dev.index
     for c, f in pairs:
         for s in (c, f):
+            s._require_cu_handle("prolong")
             if (torch.cuda.current_device() if s.device.index is None else s.device.index) != index:
                 raise ValueError("prolong: all trials must be on one device")
     with torch.cuda.device(dev):
@@ -182,11 +186,43 @@ def advance(trials, k):
             for start, c, ring in zip(starts, ctrl, rings)]
 
 
+def advance_with_budget(step, start, k, budget, max_lin_iters):
+    """``k`` iterations of a ``"chip"`` trial that stands at iteration ``start``, whatever BiCGSTAB budget they need.
+
+    ``step(m, budget)`` enqueues up to ``m`` iterations with ``budget`` BiCGSTAB iterations each, waits, and returns
+    (rows of the iterations it completed, latch, nan, iteration count, overflow).  An overflow means: the iteration after
+    the last completed one needs more than ``budget`` and has changed nothing; the rest is enqueued again with twice the
+    budget, at most ``max_lin_iters`` (where the kernel accepts a solve that has not converged, so it cannot overflow).
+    Returns (rows, latch, nan, iteration count, budget now, retries): no iteration is lost or counted twice."""
+    import numpy as np
+    blocks, total, retries = [], int(start), 0
+    latch = nan = 0
+    while total - start < k:
+        rows, latch, nan, new_total, overflow = step(k - (total - start), budget)
+        if len(rows) != new_total - total:
+            raise RuntimeError(f"{len(rows)} record rows for iterations {total} ... {new_total}")
+        blocks.append(rows)
+        total = int(new_total)
+        if latch or nan:
+            break
+        if overflow:
+            if budget >= max_lin_iters:
+                raise RuntimeError(f"linear budget {budget} >= max_lin_iters {max_lin_iters} reported an overflow")
+            budget = min(2 * budget, int(max_lin_iters))
+            retries += 1
+        elif total - start < k:
+            raise RuntimeError("device loop made no progress")
+    rows = np.concatenate(blocks, axis=0) if blocks else np.zeros((0, F.REC_LEN))
+    return rows, int(latch), int(nan), total, budget, retries
+
+
 class FVSolver(LidDrivenCavitySolver):
-    """Collocated finite-volume SIMPLE solver; ``nx`` x ``ny`` cells (8 ... 256 each)."""
+    """Collocated finite-volume SIMPLE solver; ``nx`` x ``ny`` cells (8 ... 256 each with ``mapping="cu"``, one
+    work-group per trial; 8 ... 1024 with ``mapping="chip"``, one launch per phase over the whole chip)."""
 
     Parameters = FVParameters
     rho = 1.0
+    _needs_cu_handle = None                   # (a subclass that cannot do without the one-CU handle names itself here)
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
@@ -204,9 +240,27 @@ class FVSolver(LidDrivenCavitySolver):
         if int(p.anderson_start) < 1:
             raise ValueError(f"anderson_start={p.anderson_start}: an iteration count, at least 1")
         self.accelerated = p.acceleration == "anderson"
+        if p.mapping not in MAPPINGS:
+            raise ValueError(f"mapping={p.mapping!r}: 'cu' or 'chip'")
+        if int(p.linear_budget) < 1:
+            raise ValueError(f"linear_budget={p.linear_budget}: BiCGSTAB iterations per SIMPLE iteration, at least 1")
+        self.chip = p.mapping == "chip"
         nx, ny = int(p.nx), int(p.ny)
-        if not (F.MIN_N <= nx <= F.MAX_N and F.MIN_N <= ny <= F.MAX_N):
-            raise ValueError(f"nx, ny = {nx}, {ny}: the FV kernel takes {F.MIN_N} ... {F.MAX_N} cells per axis")
+        max_n = F.WIDE_MAX_N if self.chip else F.MAX_N
+        if not (F.MIN_N <= nx <= max_n and F.MIN_N <= ny <= max_n):
+            raise ValueError(f"nx, ny = {nx}, {ny}: the FV kernel takes {F.MIN_N} ... {max_n} cells per axis "
+                             f"with mapping={p.mapping!r}")
+        if self.chip and self.accelerated:
+            raise ValueError("acceleration='anderson' with mapping='chip': the mixing kernel follows the one-CU kernel's "
+                             "launches only")
+        # the one-CU handle beside the wide one wherever it exists: postprocess, prolong and start_from use it
+        self._has_cu_handle = not self.chip or max(nx, ny) <= F.MAX_N
+        if self._needs_cu_handle and not self._has_cu_handle:
+            raise ValueError(f"{self._needs_cu_handle} of {nx} x {ny} cells: the prolongation takes at most {F.MAX_N} "
+                             f"cells per axis")
+        if p.vortex_metrics == "device" and not self._has_cu_handle:
+            raise ValueError(f"vortex_metrics='device' at {nx} x {ny}: device post-processing takes at most {F.MAX_N} "
+                             f"cells per axis")
         self.nx, self.ny, self.n_cells = nx, ny, nx * ny
         self.dx_min, self.dy_min = p.Lx / nx, p.Ly / ny
         self.shape_full = (ny, nx)               # as the reference's FV solver: cells c = j*nx + i
@@ -240,7 +294,13 @@ class FVSolver(LidDrivenCavitySolver):
             astate=torch.zeros(F.ANDERSON_STATE_LEN, dtype=torch.int64, device=self.device))
         if self.accelerated:
             self.t["hist"] = torch.zeros(F.anderson_hist_len(nx, ny, int(p.anderson_depth)), **f64)
+        if self.chip:
+            self.t["scratch"] = torch.zeros(F.wide_scratch_len(nx, ny), **f64)
+        self.linear_budget = int(p.linear_budget)        # grows when a solve overflows it (advance_with_budget)
+        self.linear_budget_retries = 0
         self._handle = None
+        self._wide = None
+        self.wide_graph = None                   # None: the library's default; set_wide_graph() chooses
         self._handle_tol = None
         self._make_handle(p.tolerance)
 
@@ -257,20 +317,46 @@ class FVSolver(LidDrivenCavitySolver):
 
     def _make_handle(self, tolerance: float):
         import torch
-        if self._handle is not None and self._handle_tol == tolerance:
+        if (self._handle is not None or self._wide is not None) and self._handle_tol == tolerance:
             return
         self._destroy_handle()
-        h = C.c_void_p()
         pr = self._problem(tolerance)
         with torch.cuda.device(self.device):
             torch.cuda.current_stream(self.device).synchronize()
-            F.check(F.lib().ldc_fv_create(C.byref(pr), C.byref(h)), "ldc_fv_create")
-        self._handle, self._handle_tol = h, tolerance
+            if self._has_cu_handle:
+                h = C.c_void_p()
+                F.check(F.lib().ldc_fv_create(C.byref(pr), C.byref(h)), "ldc_fv_create")
+                self._handle = h
+            if self.chip:
+                h = C.c_void_p()
+                F.check(F.lib().ldc_fv_wide_create(C.byref(pr), self.t["scratch"].data_ptr(),
+                                                   self.t["scratch"].numel(), C.byref(h)), "ldc_fv_wide_create")
+                self._wide = h
+                if self.wide_graph is not None:
+                    F.check(F.lib().ldc_fv_wide_set_graph(h, int(self.wide_graph)), "ldc_fv_wide_set_graph")
+        self._handle_tol = tolerance
 
     def _destroy_handle(self):
         if self._handle is not None:
             F.lib().ldc_fv_destroy(self._handle)
             self._handle = None
+        if getattr(self, "_wide", None) is not None:
+            F.lib().ldc_fv_wide_destroy(self._wide)
+            self._wide = None
+        self._handle_tol = None
+
+    def set_wide_graph(self, on: bool):
+        """A ``"chip"`` trial's launches: one replayed hipGraph per iteration (True) or every kernel on its own (False).
+        The same kernels in the same order either way (tools/fv_wide_perf.py measures both)."""
+        if not self.chip:
+            raise ValueError("set_wide_graph: only a mapping='chip' trial has launches to capture")
+        self.wide_graph = bool(on)
+        F.check(F.lib().ldc_fv_wide_set_graph(self._wide, int(self.wide_graph)), "ldc_fv_wide_set_graph")
+
+    def _require_cu_handle(self, what: str):
+        if self._handle is None:
+            raise ValueError(f"{what}: a trial of {self.nx} x {self.ny} cells has no one-CU handle "
+                             f"(at most {F.MAX_N} cells per axis)")
 
     def _anderson_block(self) -> F.Anderson:
         """This trial's block of an ``anderson_enqueue`` call: its depth and history, depth 0 for a plain trial."""
@@ -306,6 +392,7 @@ class FVSolver(LidDrivenCavitySolver):
             self.t[name].copy_(torch.as_tensor(np.asarray(val, dtype=np.float64).ravel()))
         self.t["ctrl"].zero_()
         self.t["astate"].zero_()
+        self.linear_budget, self.linear_budget_retries = int(self.params.linear_budget), 0
         self._post = None
 
     def state(self) -> dict:
@@ -316,7 +403,8 @@ class FVSolver(LidDrivenCavitySolver):
         a = self.t["astate"].cpu().numpy()
         return dict(done=int(c[F.CTRL_DONE]), iterations=int(c[F.CTRL_ITER]), nan=int(c[F.CTRL_NAN]),
                     linear_giveups=int(c[F.CTRL_GIVEUP]), linear_iterations=int(c[F.CTRL_LIN_ITERS]),
-                    momentum_solves=int(c[F.CTRL_SOLVES]), anderson_fallbacks=int(a[F.ASTATE_FALLBACKS]))
+                    momentum_solves=int(c[F.CTRL_SOLVES]), anderson_fallbacks=int(a[F.ASTATE_FALLBACKS]),
+                    linear_budget_retries=int(self.linear_budget_retries))
 
     def step_debug(self, which=F.DBG) -> dict:
         """One iteration through ldc_fv_step_debug; returns the named intermediates (include/ldc_fv.h)."""
@@ -339,10 +427,35 @@ class FVSolver(LidDrivenCavitySolver):
         self._make_handle(tolerance)
         self.t["ctrl"].zero_()
         self.t["astate"].zero_()                 # (the mixing history starts over with the count: include/ldc_fv.h)
+        self.linear_budget, self.linear_budget_retries = int(self.params.linear_budget), 0
         self._post = None
+
+    def _wide_step(self, m: int, budget: int):
+        """One wide enqueue of up to ``m`` iterations at ``budget`` and ONE wait (``advance_with_budget``'s step)."""
+        import torch
+        from solvers.spectral import ldc_lib
+        index = torch.cuda.current_device() if self.device.index is None else self.device.index
+        with torch.cuda.device(self.device):
+            start = int(self.t["ctrl"][F.CTRL_ITER].item())
+            with ldc_lib.resident_lock(index):
+                F.check(F.lib().ldc_fv_wide_enqueue(self._wide, int(m), int(budget), C.c_void_p(self._stream())),
+                        "ldc_fv_wide_enqueue")
+                c = self.t["ctrl"].cpu().numpy()          # (synchronises the stream)
+            total = int(c[F.CTRL_ITER])
+            rows = self.t["rec"][: total - start].cpu().numpy().copy()
+            overflow = int(self.t["scratch"][:1].view(torch.int64).item())
+        return rows, int(c[F.CTRL_DONE]), int(c[F.CTRL_NAN]), total, overflow
 
     def _advance(self, n_iters: int):
         n_iters = max(1, min(int(n_iters), self.rec_cap))
+        if self.chip:
+            start = int(self.t["ctrl"][F.CTRL_ITER].item())
+            rows, done, nan, total, self.linear_budget, retries = advance_with_budget(
+                self._wide_step, start, n_iters, self.linear_budget, LINEAR_MAX_ITERATIONS)
+            self.linear_budget_retries += retries
+            if nan:
+                F.check(F.lib().ldc_fv_wide_status(self._wide), f"FV trial at iteration {total}")
+            return rows, done, total
         rows, done, nan, total = advance([self], n_iters)[0]
         if nan:
             F.check(F.lib().ldc_fv_status(self._handle), f"FV trial at iteration {total}")

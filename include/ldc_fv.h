@@ -1,5 +1,5 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
- * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip).
+ * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -76,6 +76,22 @@
  *    full every iteration, sums in a fixed order (per thread in increasing index, wave shuffles, LDS), so lone runs,
  *    batches and repeats agree bit for bit.
  *  Between the enqueues of ONE solve an accelerated trial is advanced by ldc_fv_anderson_enqueue only.
+ *
+ * A lone trial on the whole chip (csrc/ldc_fv_wide.hip, ldc_fv_wide_*): the same iteration on the same arrays, with the
+ * same meaning of u, v, p, mdot, work, rec and ctrl, for LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N cells per axis.  One kernel
+ * launch per phase of the iteration, up to 256 work-groups each; the launch boundary is the only barrier, so no
+ * work-group waits for another.  The work vectors keep the layout of the one-CU kernel: after one iteration `work`
+ * holds the intermediates of ldc_fv_step_debug (vector k at work + k n, in the order grad p x / y, aP aW aE aS aN, u*,
+ * v*, ..., rhs_p at 23 with entry 0 = 0, p' + const at 26, u' and v' at 27 and 28, b_u and b_v at 30 and 31).
+ *  - sums: every work-group leaves its partial in a slot of `scratch`, the next launch adds the slots in a fixed
+ *    order, so runs repeat bit for bit (the order differs from the one-CU kernel's: the two agree to rounding);
+ *  - an enqueue carries lin_budget BiCGSTAB iterations per SIMPLE iteration (min(lin_budget, max_lin_iters) times five
+ *    launches).  A momentum solve still active after lin_budget < max_lin_iters iterations sets the overflow word
+ *    before u, v, p or mdot are touched: ctrl stays as it was, the rest of the enqueue does nothing, ldc_fv_wide_status
+ *    returns LDC_FV_WIDE_E_BUDGET and the caller enqueues the remaining iterations again with a larger budget (every
+ *    enqueue clears the word).  With lin_budget >= max_lin_iters a solve still active is the accepted give-up of
+ *    ctrl[3].  So the result does not depend on the budget;
+ *  - scratch: LDC_FV_WIDE_SCRATCH_LEN doubles owned by the caller, the library's between two enqueues of one solve too.
  */
 #ifndef LDC_FV_H
 #define LDC_FV_H
@@ -102,6 +118,12 @@ extern "C" {
 #define LDC_FV_ANDERSON_STATE_LEN 4
 #define LDC_FV_ANDERSON_HIST_LEN(nx, ny, depth) ((2 * (int64_t)(depth) + 3) * (3 * (int64_t)(nx) * (ny) + LDC_FV_FACES(nx, ny)))
 #define LDC_FV_E_NAN (-5)          /* ldc_fv_status: the trial produced a NaN and stopped */
+#define LDC_FV_WIDE_MAX_N 1024     /* cells per axis of a trial on the whole chip */
+#define LDC_FV_WIDE_GRAPH_DEFAULT 0 /* ldc_fv_wide_set_graph of a new handle (profiles/fv_wide.md) */
+#define LDC_FV_WIDE_E_BUDGET (-6)  /* ldc_fv_wide_status: the last enqueue stopped for want of BiCGSTAB launches */
+/* work-groups of a sweep over the cells (one slot of partial sums each) and the caller's scratch, in doubles */
+#define LDC_FV_WIDE_GROUPS(nx, ny) ((((int64_t)(nx) * (ny) + 255) / 256) < 256 ? (((int64_t)(nx) * (ny) + 255) / 256) : 256)
+#define LDC_FV_WIDE_SCRATCH_LEN(nx, ny) (80 + 30 * LDC_FV_WIDE_GROUPS(nx, ny))
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
 #define LDC_FV_DBG_GRAD_P 0        /* 2n: d/dx p, then d/dy p                                    */
@@ -171,6 +193,7 @@ struct ldc_fv_anderson {
 };
 
 typedef struct ldc_fv ldc_fv;
+typedef struct ldc_fv_wide ldc_fv_wide;
 
 int ldc_fv_version(void);
 /* Validate (no device needed), then write the trial's descriptor into the tail of `work` (synchronous copy on the */
@@ -206,6 +229,24 @@ int ldc_fv_prolong_enqueue(ldc_fv *const *coarse, ldc_fv *const *fine, int n, vo
 /* below LDC_FV_ANDERSON_HIST_LEN.  Then LDC_E_NODEVICE, and LDC_E_STATE for a handle of another device.  A trial may    */
 /* appear once in a call, and no two trials may share hist or astate: that is the caller's to see to.                   */
 int ldc_fv_anderson_enqueue(ldc_fv *const *hs, const struct ldc_fv_anderson *acc, int n, int n_iters, void *stream);
+/* A trial advanced by the whole chip.  Validation is ldc_fv_create's with nx, ny up to LDC_FV_WIDE_MAX_N, a non-null   */
+/* scratch and scratch_len >= LDC_FV_WIDE_SCRATCH_LEN(nx, ny); it comes first and needs no device.  Nothing is copied   */
+/* or launched: the arrays may be shared with an ldc_fv handle of the same problem (one of the two in flight at a time). */
+int ldc_fv_wide_create(const struct ldc_fv_problem *prob, double *scratch, int64_t scratch_len, ldc_fv_wide **out);
+int ldc_fv_wide_destroy(ldc_fv_wide *h);
+/* Up to n_iters SIMPLE iterations (1 .. rec_cap) with lin_budget (>= 1) BiCGSTAB iterations each, all launches enqueued */
+/* on `stream`; stops early at the latch, a NaN or the overflow.  LDC_E_STATE for a null handle, then LDC_E_ARG, then     */
+/* the device.                                                                                                          */
+int ldc_fv_wide_enqueue(ldc_fv_wide *h, int n_iters, int lin_budget, void *stream);
+/* on = 1: an enqueue replays ONE captured iteration per budget value (a linear hipGraph of that iteration's launches,   */
+/* captured at the first enqueue with that budget and kept until destroy; budgets above 64 are launched one by one);   */
+/* on = 0: every kernel is launched on its own.  Same kernels, same order, same results.  A new handle starts with      */
+/* LDC_FV_WIDE_GRAPH_DEFAULT.  destroy waits for the last replay before it frees the graphs.                            */
+int ldc_fv_wide_set_graph(ldc_fv_wide *h, int on);
+/* Kernel launches of ONE iteration at that budget (an enqueue adds one).  Needs no device. */
+int ldc_fv_wide_launches(const ldc_fv_wide *h, int lin_budget);
+/* 0, LDC_FV_E_NAN, or LDC_FV_WIDE_E_BUDGET when the last enqueue overflowed (wait for its stream first). */
+int ldc_fv_wide_status(ldc_fv_wide *h);
 
 #ifdef __cplusplus
 }
