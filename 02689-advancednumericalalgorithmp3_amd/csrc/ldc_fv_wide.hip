@@ -23,7 +23,20 @@
 // the host repeats the rest of the chunk with twice the budget: the result does not depend on the budget.
 //
 // scratch (LDC_FV_WIDE_SCRATCH_LEN doubles): 16 int64 words (overflow, record row, pending give-ups, pending BiCGSTAB
-// iterations), 2 x 32 doubles of BiCGSTAB scalars, 2 x G x 10 slot sums, G x 10 sums of the record row.
+// iterations, the enqueue's quota of iterations), 2 x 32 doubles of BiCGSTAB scalars, 2 x G x 10 slot sums, G x 10 sums
+// of the record row.
+//
+// Several trials in the same launches (ldc_fv_wide_batch_*, mapping="shared"): none of the rules needs a trial to be
+// alone on the card, so every phase is a device function of (the trial's arguments, the work-group's index g WITHIN its
+// trial) and exists as two kernels.  The lone one passes (its argument block, blockIdx.x).  The batch one looks its
+// work-group up in a table in device memory that ldc_fv_wide_batch_create wrote once: a block map `blockIdx.x -> (trial
+// q, g)` for the cell sweeps and one for the GEMMs (one scalar load, the same for every lane; a prefix array would cost a
+// chain of eight dependent loads at 256 trials), q = blockIdx.x for the launches of one work-group per trial, then a copy
+// of entry q of the argument table.  No kernel ever writes the table, so these are scalar loads.  The arithmetic, the
+// sweep order, the slots, `par` and the trial's own G are the lone kernels': a trial in a batch is bit-identical to its
+// lone run.  An enqueue gives every trial a quota of iterations (the word WW_QUOTA, written by `begin`) and runs
+// max(quota) chains; the gate also returns once the trial's record row has reached its quota, so a trial that is
+// finished, capped, NaN, overflowed or not meant at all (quota 0) costs empty work-groups and the table is never rebuilt.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -45,7 +58,7 @@ constexpr int kWS = 10;                     // doubles of a slot
 constexpr int kWMaxG = 256;                 // most work-groups of a sweep: one per CU, and one slot per thread to add
 constexpr int kWWords = 16;
 constexpr int kWKry = 32;                   // doubles of one copy of the BiCGSTAB scalars: 16 per component
-enum { WW_OVF, WW_ROW, WW_GIVEUPS, WW_LIN_ITERS };
+enum { WW_OVF, WW_ROW, WW_GIVEUPS, WW_LIN_ITERS, WW_QUOTA };
 static_assert(LDC_FV_WIDE_SCRATCH_LEN(8, 8) == kWWords + 2 * kWKry + 3 * kWS * 1, "scratch layout");
 static_assert(LDC_FV_WIDE_SCRATCH_LEN(1024, 1024) == kWWords + 2 * kWKry + 3 * kWS * kWMaxG, "scratch layout");
 
@@ -53,6 +66,27 @@ struct FvWideArgs {
   FvDesc d;
   double* scr;
   int G;                                    // work-groups of a sweep
+};
+
+// The table of a batch in the caller's device buffer (LDC_FV_WIDE_BATCH_TABLE_LEN bytes): n entries, then the block map
+// of the cell sweeps (sum of G_q words) and that of the GEMMs (sum of LDC_FV_WIDE_GEMM_GROUPS words), one word
+// q << 16 | g per work-group, trial after trial.
+struct FvWideEntry {
+  FvWideArgs a;
+  char pad[LDC_FV_WIDE_BATCH_ENTRY_BYTES - sizeof(FvWideArgs)];
+};
+static_assert(sizeof(FvWideEntry) == LDC_FV_WIDE_BATCH_ENTRY_BYTES, "table entry");
+static_assert(LDC_FV_WIDE_BATCH_MAX <= 1 << 15 && LDC_FV_WIDE_GEMM_GROUPS(LDC_FV_WIDE_MAX_N, LDC_FV_WIDE_MAX_N) <= 1 << 16,
+              "a block-map word");
+
+struct FvWideTable {
+  const FvWideEntry* __restrict__ entries;
+  const uint32_t* __restrict__ sweep;
+  const uint32_t* __restrict__ gemm;
+};
+
+struct FvWideQuotas {
+  int32_t q[LDC_FV_WIDE_BATCH_MAX];
 };
 
 struct FvKrylov {
@@ -70,7 +104,8 @@ __device__ __forceinline__ double* wide_rec_slots(const FvWideArgs& a) { return 
 
 // the gate: true when the launch has nothing to do
 __device__ __forceinline__ bool wide_gate(const FvWideArgs& a) {
-  return a.d.ctrl[0] != 0 || a.d.ctrl[2] != 0 || wide_words(a)[WW_OVF] != 0;
+  const long long* w = wide_words(a);
+  return a.d.ctrl[0] != 0 || a.d.ctrl[2] != 0 || w[WW_OVF] != 0 || w[WW_ROW] >= w[WW_QUOTA];
 }
 
 // sums of K values over the work-group in a fixed order; every thread gets the totals.  Ends on a barrier, so `lds`
@@ -107,13 +142,13 @@ __device__ __forceinline__ void wide_slot_sum(const double* slots, int G, int fi
   wide_block_sum(a, lds);
 }
 
-// this work-group's partial sums into entries first .. of its own slot
+// the partial sums of work-group g (of its trial) into entries first .. of its own slot
 template <int K>
-__device__ __forceinline__ void wide_slot_put(double* slots, int first, double (&a)[K], double* lds) {
+__device__ __forceinline__ void wide_slot_put(double* slots, int g, int first, double (&a)[K], double* lds) {
   wide_block_sum(a, lds);
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int k = 0; k < K; ++k) slots[blockIdx.x * kWS + first + k] = a[k];
+    for (int k = 0; k < K; ++k) slots[g * kWS + first + k] = a[k];
   }
 }
 
@@ -127,8 +162,8 @@ __device__ __forceinline__ void wide_kry_load(const double* K, FvKrylov (&s)[2])
 }
 
 // (work-group 0 alone writes the copy the NEXT launch reads)
-__device__ __forceinline__ void wide_kry_store(double* K, const FvKrylov (&s)[2]) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+__device__ __forceinline__ void wide_kry_store(double* K, int g, const FvKrylov (&s)[2]) {
+  if (g != 0 || threadIdx.x != 0) return;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     double* k = K + 16 * q;
@@ -217,26 +252,27 @@ struct WCtx {
   int nx, ny, n, ldx, first, stride;
   double dx, dy, V, rho, inv_a;
   double *w, *fx, *fy;
-  __device__ __forceinline__ explicit WCtx(const FvWideArgs& a)
-      : d(a.d), nx(a.d.nx), ny(a.d.ny), n(nx * ny), ldx(nx + 1), first(blockIdx.x * kWT + threadIdx.x),
+  __device__ __forceinline__ WCtx(const FvWideArgs& a, int g)
+      : d(a.d), nx(a.d.nx), ny(a.d.ny), n(nx * ny), ldx(nx + 1), first(g * kWT + threadIdx.x),
         stride(a.G * kWT), dx(a.d.dx), dy(a.d.dy), V(dx * dy), rho(a.d.rho), inv_a(1.0 / a.d.alpha_uv), w(a.d.work),
         fx(a.d.mdot), fy(a.d.mdot + ny * ldx) {}
   __device__ __forceinline__ double* vec(FvVec k, int q = 0) const { return w + (k + q) * n; }
 };
 
-// ---- begin: the first launch of an enqueue (one work-group): the overflow word and the record row start at 0
-__global__ __launch_bounds__(64) void fv_wide_begin(FvWideArgs a) {
+// ---- begin: the first launch of an enqueue (one work-group): the overflow word and the record row start at 0, the
+//      quota is the number of iterations the enqueue means for this trial
+__device__ __forceinline__ void wide_begin(const FvWideArgs& a, int quota) {
   if (threadIdx.x == 0) {
     wide_words(a)[WW_OVF] = 0;
     wide_words(a)[WW_ROW] = 0;
+    wide_words(a)[WW_QUOTA] = quota;
   }
 }
 
 // ---- 1. grad p, the five diagonals, the relaxed right-hand sides, the BiCGSTAB start; slot: |b_u|^2, |b_v|^2
-__global__ __launch_bounds__(kWT) void fv_wide_assemble(FvWideArgs a, int par) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_assemble(const FvWideArgs& a, int g, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a);
+  const WCtx x(a, g);
   const FvDesc& d = x.d;
   const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
   double* const w = x.w;
@@ -291,16 +327,15 @@ __global__ __launch_bounds__(kWT) void fv_wide_assemble(FvWideArgs a, int par) {
     x.vec(FV_RU)[c] = hu; x.vec(FV_RTU)[c] = hu; x.vec(FV_RV)[c] = hv; x.vec(FV_RTV)[c] = hv;
     b2[0] += hu * hu; b2[1] += hv * hv;
   }
-  wide_slot_put(wide_slots(a, par ^ 1), 0, b2, lds);
+  wide_slot_put(wide_slots(a, par ^ 1), g, 0, b2, lds);
 }
 
 // ---- 2. the joint u / v BiCGSTAB, iteration `it`, one launch per sweep of fv_bicgstab.  Each reads the scalars of
 //         copy `par` and the slots `par`, and writes the copies par ^ 1.
 // p: the scalars from the sums of the launch before (it = 0: |b|^2 of assemble), the head test; p and phat
-__global__ __launch_bounds__(kWT) void fv_wide_bicg_p(FvWideArgs a, int it, int par) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_bicg_p(const FvWideArgs& a, int g, int it, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a);
+  const WCtx x(a, g);
   const int n = x.n;
   FvKrylov s[2];
   if (it == 0) {
@@ -320,7 +355,7 @@ __global__ __launch_bounds__(kWT) void fv_wide_bicg_p(FvWideArgs a, int it, int 
     wide_kry_after_x(s, s4, it);
   }
   wide_kry_head(s, it);
-  wide_kry_store(wide_kry(a, par ^ 1), s);
+  wide_kry_store(wide_kry(a, par ^ 1), g, s);
   if (!s[0].act && !s[1].act) return;
   for (int c = x.first; c < n; c += x.stride) {
     const double dg = x.w[FV_AP * n + c] * x.inv_a;
@@ -335,14 +370,13 @@ __global__ __launch_bounds__(kWT) void fv_wide_bicg_p(FvWideArgs a, int it, int 
 }
 
 // v = A phat; slot: rtilde . v
-__global__ __launch_bounds__(kWT) void fv_wide_bicg_v(FvWideArgs a, int par) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_bicg_v(const FvWideArgs& a, int g, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a);
+  const WCtx x(a, g);
   const int nx = x.nx, ny = x.ny, n = x.n;
   FvKrylov s[2];
   wide_kry_load(wide_kry(a, par), s);
-  wide_kry_store(wide_kry(a, par ^ 1), s);
+  wide_kry_store(wide_kry(a, par ^ 1), g, s);
   if (!s[0].act && !s[1].act) return;
   double s2[2] = {0, 0};
   for (int c = x.first; c < n; c += x.stride) {
@@ -354,14 +388,13 @@ __global__ __launch_bounds__(kWT) void fv_wide_bicg_v(FvWideArgs a, int par) {
       x.vec(FV_VU, q)[c] = y; s2[q] += x.vec(FV_RTU, q)[c] * y;
     }
   }
-  wide_slot_put(wide_slots(a, par ^ 1), 0, s2, lds);
+  wide_slot_put(wide_slots(a, par ^ 1), g, 0, s2, lds);
 }
 
 // alpha; s = r - alpha v (into r) and shat
-__global__ __launch_bounds__(kWT) void fv_wide_bicg_s(FvWideArgs a, int par) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_bicg_s(const FvWideArgs& a, int g, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a);
+  const WCtx x(a, g);
   const int n = x.n;
   FvKrylov s[2];
   wide_kry_load(wide_kry(a, par), s);
@@ -376,7 +409,7 @@ __global__ __launch_bounds__(kWT) void fv_wide_bicg_s(FvWideArgs a, int par) {
       s[q].alpha = s[q].rh / s2[q];
     }
   }
-  wide_kry_store(wide_kry(a, par ^ 1), s);
+  wide_kry_store(wide_kry(a, par ^ 1), g, s);
   if (!s[0].act && !s[1].act) return;
   for (int c = x.first; c < n; c += x.stride) {
     const double dg = x.w[FV_AP * n + c] * x.inv_a;
@@ -391,14 +424,13 @@ __global__ __launch_bounds__(kWT) void fv_wide_bicg_s(FvWideArgs a, int par) {
 }
 
 // t = A shat; slot: s.s, t.s, t.t per component
-__global__ __launch_bounds__(kWT) void fv_wide_bicg_t(FvWideArgs a, int par) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_bicg_t(const FvWideArgs& a, int g, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a);
+  const WCtx x(a, g);
   const int nx = x.nx, ny = x.ny, n = x.n;
   FvKrylov s[2];
   wide_kry_load(wide_kry(a, par), s);
-  wide_kry_store(wide_kry(a, par ^ 1), s);
+  wide_kry_store(wide_kry(a, par ^ 1), g, s);
   if (!s[0].act && !s[1].act) return;
   double s3[6] = {0, 0, 0, 0, 0, 0};
   for (int c = x.first; c < n; c += x.stride) {
@@ -410,14 +442,13 @@ __global__ __launch_bounds__(kWT) void fv_wide_bicg_t(FvWideArgs a, int par) {
       x.vec(FV_TU, q)[c] = t; s3[3 * q] += sv * sv; s3[3 * q + 1] += t * sv; s3[3 * q + 2] += t * t;
     }
   }
-  wide_slot_put(wide_slots(a, par ^ 1), 0, s3, lds);
+  wide_slot_put(wide_slots(a, par ^ 1), g, 0, s3, lds);
 }
 
 // omega (or the early finish on |s|); x and r; slot: r.r, rtilde.r per component
-__global__ __launch_bounds__(kWT) void fv_wide_bicg_x(FvWideArgs a, int it, int par) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_bicg_x(const FvWideArgs& a, int g, int it, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a);
+  const WCtx x(a, g);
   const int n = x.n;
   FvKrylov s[2];
   wide_kry_load(wide_kry(a, par), s);
@@ -433,7 +464,7 @@ __global__ __launch_bounds__(kWT) void fv_wide_bicg_x(FvWideArgs a, int it, int 
       s[q].omega = s3[3 * q + 1] / s3[3 * q + 2];
     }
   }
-  wide_kry_store(wide_kry(a, par ^ 1), s);
+  wide_kry_store(wide_kry(a, par ^ 1), g, s);
   if (!s[0].act && !s[1].act) return;
   double s4[4] = {0, 0, 0, 0};
   for (int c = x.first; c < n; c += x.stride) {
@@ -450,14 +481,13 @@ __global__ __launch_bounds__(kWT) void fv_wide_bicg_x(FvWideArgs a, int it, int 
       }
     }
   }
-  wide_slot_put(wide_slots(a, par ^ 1), 0, s4, lds);
+  wide_slot_put(wide_slots(a, par ^ 1), g, 0, s4, lds);
 }
 
 // linfinish (one work-group), after `nb` = min(lin_budget, max_lin_iters) iterations: the last sums; a component still
 // active at nb = max_lin_iters is the accepted give-up, at nb < max_lin_iters the overflow (nothing but work vectors
 // has been written so far).  The counters wait in the scratch words for the record launch.
-__global__ __launch_bounds__(kWT) void fv_wide_linfinish(FvWideArgs a, int nb, int par) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_linfinish(const FvWideArgs& a, int nb, int par, double* lds) {
   if (wide_gate(a)) return;
   FvKrylov s[2];
   wide_kry_load(wide_kry(a, par), s);
@@ -482,10 +512,9 @@ __global__ __launch_bounds__(kWT) void fv_wide_linfinish(FvWideArgs a, int nb, i
 
 // ---- 3. Rhie-Chow face velocities, mdot*, rhs_p = -div mdot* (entry 0 = 0); slot: the sum of rhs_p, whose negative
 //         is the cell-0 entry of the pinned solve (the first GEMM puts it in as it reads C)
-__global__ __launch_bounds__(kWT) void fv_wide_faces(FvWideArgs a, int par) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_faces(const FvWideArgs& a, int g, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a);
+  const WCtx x(a, g);
   const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
   double* const w = x.w;
   double *fx = x.fx, *fy = x.fy;
@@ -521,7 +550,7 @@ __global__ __launch_bounds__(kWT) void fv_wide_faces(FvWideArgs a, int par) {
     x.vec(FV_C)[c] = rhs;
     csum[0] += rhs;
   }
-  wide_slot_put(wide_slots(a, par ^ 1), 0, csum, lds);
+  wide_slot_put(wide_slots(a, par ^ 1), g, 0, csum, lds);
 }
 
 // ---- 4. one GEMM of the fast diagonalisation: C[r][c] = sum_k A(r, k) B(k, c) as fv_gemm, one wave per 16 x 16 tile,
@@ -533,9 +562,21 @@ struct FvWideGemm {
   int sar, sak, sbk, sbc, M, N, K;
 };
 
+// the four GEMMs of a trial: W1 = Qy^T C, W2 = W1 Qx / Lambda, W1 = Qy W2, Y = W1 Qx^T
+__host__ __device__ inline FvWideGemm wide_gemm_of(const FvDesc& d, int which) {
+  const int nx = d.nx, ny = d.ny;
+  const int64_t n = (int64_t)nx * ny;
+  double* w = d.work;
+  double *Cv = w + FV_C * n, *W1 = w + FV_W1 * n, *W2 = w + FV_W2 * n, *Y = w + FV_Y * n;
+  if (which == 0) return {d.Qy, Cv, W1, 1, ny, nx, 1, ny, nx, ny};
+  if (which == 1) return {W1, d.Qx, W2, nx, 1, nx, 1, ny, nx, nx};
+  if (which == 2) return {d.Qy, W2, W1, ny, 1, nx, 1, ny, nx, ny};
+  return {W1, d.Qx, Y, nx, 1, 1, nx, ny, nx, nx};
+}
+
+// (gb: the work-group's index among the trial's LDC_FV_WIDE_GEMM_GROUPS)
 template <bool FIRST, bool SCALE>
-__global__ __launch_bounds__(kWT) void fv_wide_gemm(FvWideArgs a, FvWideGemm g, int par) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_gemm(const FvWideArgs& a, int gb, const FvWideGemm& g, int par, double* lds) {
   if (wide_gate(a)) return;
   double b00 = 0.0;
   if (FIRST) {
@@ -546,7 +587,7 @@ __global__ __launch_bounds__(kWT) void fv_wide_gemm(FvWideArgs a, FvWideGemm g, 
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int M = g.M, N = g.N, K = g.K;
   const int tn = (N + 15) >> 4, tiles = ((M + 15) >> 4) * tn;
-  const int t = blockIdx.x * kWW + w;
+  const int t = gb * kWW + w;
   if (t >= tiles) return;
   const int r0 = (t / tn) * 16, c0 = (t % tn) * 16;
   const int ar = r0 + (lane & 15), bc = c0 + (lane & 15), kq = lane >> 4;
@@ -571,10 +612,9 @@ __global__ __launch_bounds__(kWT) void fv_wide_gemm(FvWideArgs a, FvWideGemm g, 
 }
 
 // ---- 5. u' = -D grad p', u = u* + u', p += alpha_p p'; record sums 0 .. 6 of this work-group
-__global__ __launch_bounds__(kWT) void fv_wide_correct(FvWideArgs a) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_correct(const FvWideArgs& a, int g, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a);
+  const WCtx x(a, g);
   const FvDesc& d = x.d;
   const int nx = x.nx, ny = x.ny, n = x.n;
   const double y0 = x.vec(FV_Y)[0];
@@ -593,14 +633,13 @@ __global__ __launch_bounds__(kWT) void fv_wide_correct(FvWideArgs a) {
     part[2] += (vn - vo) * (vn - vo); part[3] += vo * vo;
     part[4] += upc * upc; part[5] += vpc * vpc; part[6] += un * un + vn * vn;
   }
-  wide_slot_put(wide_rec_slots(a), 0, part, lds);
+  wide_slot_put(wide_rec_slots(a), g, 0, part, lds);
 }
 
 // ---- 6. mdot += rho interp(u', v') . S (walls: rho u'_P |S|, FV-Q4); vorticity with ghost cells; record sum 8
-__global__ __launch_bounds__(kWT) void fv_wide_fluxvort(FvWideArgs a) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_fluxvort(const FvWideArgs& a, int g, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a);
+  const WCtx x(a, g);
   const FvDesc& d = x.d;
   const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
   double *fx = x.fx, *fy = x.fy;
@@ -621,14 +660,13 @@ __global__ __launch_bounds__(kWT) void fv_wide_fluxvort(FvWideArgs a) {
     x.vec(FV_OMEGA)[c] = wc;
     part[0] += wc * wc;
   }
-  wide_slot_put(wide_rec_slots(a), 8, part, lds);
+  wide_slot_put(wide_rec_slots(a), g, 8, part, lds);
 }
 
 // ---- 7a. |div mdot|^2 and |grad omega|^2: record sums 7 and 9
-__global__ __launch_bounds__(kWT) void fv_wide_sums(FvWideArgs a) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_sums(const FvWideArgs& a, int g, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a);
+  const WCtx x(a, g);
   const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
   const double *fx = x.fx, *fy = x.fy;
   double p7[1] = {0.0}, p9[1] = {0.0};
@@ -643,13 +681,12 @@ __global__ __launch_bounds__(kWT) void fv_wide_sums(FvWideArgs a) {
     const double gx = (wE - wW) / (2 * x.dx), gy = (wN - wS) / (2 * x.dy);
     p9[0] += gx * gx + gy * gy;
   }
-  wide_slot_put(wide_rec_slots(a), 7, p7, lds);
-  wide_slot_put(wide_rec_slots(a), 9, p9, lds);
+  wide_slot_put(wide_rec_slots(a), g, 7, p7, lds);
+  wide_slot_put(wide_rec_slots(a), g, 9, p9, lds);
 }
 
 // ---- 7b. record (one work-group): the record row, the latch and ctrl[0 .. 5], once per iteration
-__global__ __launch_bounds__(kWT) void fv_wide_record(FvWideArgs a) {
-  __shared__ double lds[kWW * kWS];
+__device__ __forceinline__ void wide_record(const FvWideArgs& a, double* lds) {
   if (wide_gate(a)) return;
   const FvDesc& d = a.d;
   double part[kWS];
@@ -673,6 +710,57 @@ __global__ __launch_bounds__(kWT) void fv_wide_record(FvWideArgs a) {
   }
 }
 
+// ---- the kernels: every phase for a lone trial (arguments by value, g = blockIdx.x) and for a batch (the table)
+#define WIDE_LDS __shared__ double lds[kWW * kWS]
+// the trial and the work-group of this block of a batch launch, from a block map / for one work-group per trial
+#define WIDE_MAPPED(map)                                   \
+  const uint32_t m_ = t.map[blockIdx.x];                   \
+  const FvWideArgs a = t.entries[m_ >> 16].a;              \
+  const int g = (int)(m_ & 0xffffu)
+#define WIDE_SINGLE const FvWideArgs a = t.entries[blockIdx.x].a
+
+__global__ __launch_bounds__(64) void fv_wide_begin(FvWideArgs a, int quota) { wide_begin(a, quota); }
+__global__ __launch_bounds__(64) void fv_wide_b_begin(FvWideTable t, FvWideQuotas quotas) {
+  WIDE_SINGLE;
+  wide_begin(a, quotas.q[blockIdx.x]);
+}
+
+__global__ __launch_bounds__(kWT) void fv_wide_assemble(FvWideArgs a, int par) { WIDE_LDS; wide_assemble(a, blockIdx.x, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_assemble(FvWideTable t, int par) { WIDE_LDS; WIDE_MAPPED(sweep); wide_assemble(a, g, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_bicg_p(FvWideArgs a, int it, int par) { WIDE_LDS; wide_bicg_p(a, blockIdx.x, it, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_bicg_p(FvWideTable t, int it, int par) { WIDE_LDS; WIDE_MAPPED(sweep); wide_bicg_p(a, g, it, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_bicg_v(FvWideArgs a, int par) { WIDE_LDS; wide_bicg_v(a, blockIdx.x, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_bicg_v(FvWideTable t, int par) { WIDE_LDS; WIDE_MAPPED(sweep); wide_bicg_v(a, g, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_bicg_s(FvWideArgs a, int par) { WIDE_LDS; wide_bicg_s(a, blockIdx.x, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_bicg_s(FvWideTable t, int par) { WIDE_LDS; WIDE_MAPPED(sweep); wide_bicg_s(a, g, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_bicg_t(FvWideArgs a, int par) { WIDE_LDS; wide_bicg_t(a, blockIdx.x, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_bicg_t(FvWideTable t, int par) { WIDE_LDS; WIDE_MAPPED(sweep); wide_bicg_t(a, g, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_bicg_x(FvWideArgs a, int it, int par) { WIDE_LDS; wide_bicg_x(a, blockIdx.x, it, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_bicg_x(FvWideTable t, int it, int par) { WIDE_LDS; WIDE_MAPPED(sweep); wide_bicg_x(a, g, it, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_linfinish(FvWideArgs a, int nb, int par) { WIDE_LDS; wide_linfinish(a, nb, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_linfinish(FvWideTable t, int nb, int par) { WIDE_LDS; WIDE_SINGLE; wide_linfinish(a, nb, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_faces(FvWideArgs a, int par) { WIDE_LDS; wide_faces(a, blockIdx.x, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_faces(FvWideTable t, int par) { WIDE_LDS; WIDE_MAPPED(sweep); wide_faces(a, g, par, lds); }
+template <bool FIRST, bool SCALE>
+__global__ __launch_bounds__(kWT) void fv_wide_gemm(FvWideArgs a, FvWideGemm gd, int par) {
+  WIDE_LDS;
+  wide_gemm<FIRST, SCALE>(a, blockIdx.x, gd, par, lds);
+}
+template <bool FIRST, bool SCALE>
+__global__ __launch_bounds__(kWT) void fv_wide_b_gemm(FvWideTable t, int which, int par) {
+  WIDE_LDS;
+  WIDE_MAPPED(gemm);
+  wide_gemm<FIRST, SCALE>(a, g, wide_gemm_of(a.d, which), par, lds);
+}
+__global__ __launch_bounds__(kWT) void fv_wide_correct(FvWideArgs a) { WIDE_LDS; wide_correct(a, blockIdx.x, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_correct(FvWideTable t) { WIDE_LDS; WIDE_MAPPED(sweep); wide_correct(a, g, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_fluxvort(FvWideArgs a) { WIDE_LDS; wide_fluxvort(a, blockIdx.x, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_fluxvort(FvWideTable t) { WIDE_LDS; WIDE_MAPPED(sweep); wide_fluxvort(a, g, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_sums(FvWideArgs a) { WIDE_LDS; wide_sums(a, blockIdx.x, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_sums(FvWideTable t) { WIDE_LDS; WIDE_MAPPED(sweep); wide_sums(a, g, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_record(FvWideArgs a) { WIDE_LDS; wide_record(a, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_record(FvWideTable t) { WIDE_LDS; WIDE_SINGLE; wide_record(a, lds); }
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 std::mutex g_wide_mutex;
@@ -693,15 +781,21 @@ hipError_t wide_stream(hipStream_t* out) {
 }
 
 // a small synchronous copy on that stream (off the legacy stream, as the library's other status reads)
-hipError_t wide_copy_now(void* dst, const void* src, size_t bytes) {
+hipError_t wide_copy_now(void* dst, const void* src, size_t bytes, hipMemcpyKind kind = hipMemcpyDeviceToHost) {
   std::lock_guard<std::mutex> lock(g_wide_mutex);
   hipStream_t st = nullptr;
   hipError_t e = wide_stream(&st);
   if (e != hipSuccess) return e;
-  e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+  e = hipMemcpyAsync(dst, src, bytes, kind, st);
   const hipError_t w = hipStreamSynchronize(st);
   return e != hipSuccess ? e : w;
 }
+
+// the captured iterations of a handle, lone or batch: (BiCGSTAB iterations, the iteration's graph), kept until destroy
+struct WideGraphs {
+  std::vector<std::pair<int, hipGraphExec_t>> graphs;
+  hipEvent_t done = nullptr;                 // behind the last graph launch: no graph is destroyed in flight
+};
 
 }  // namespace
 
@@ -709,8 +803,15 @@ struct ldc_fv_wide {
   FvWideArgs a;
   int device;
   int graph;                                 // replay ONE captured iteration per budget (ldc_fv_wide_set_graph)
-  std::vector<std::pair<int, hipGraphExec_t>> graphs;        // (BiCGSTAB iterations, the iteration's graph), kept until destroy
-  hipEvent_t done;                           // behind the last graph launch: no graph is destroyed in flight
+  WideGraphs gs;
+};
+
+struct ldc_fv_wide_batch {
+  int n, maxit, device, graph;               // (the head, with rec_cap, is all that validation without a device reads)
+  int rec_cap[LDC_FV_WIDE_BATCH_MAX];
+  int sweep_groups, gemm_groups;             // work-groups of a cell sweep and of a GEMM launch
+  FvWideTable t;                             // (pointers into the caller's device buffer)
+  WideGraphs gs;
 };
 
 namespace {
@@ -726,7 +827,7 @@ namespace {
 int wide_iteration(const ldc_fv_wide* h, int nb, hipStream_t st) {
   const FvWideArgs& a = h->a;
   const FvDesc& d = a.d;
-  const int nx = d.nx, ny = d.ny, n = nx * ny, G = a.G;
+  const int G = a.G, gg = (int)LDC_FV_WIDE_GEMM_GROUPS(d.nx, d.ny);
   int par = 0;
   WIDE_LAUNCH(fv_wide_assemble, G, kWT, a, par); par ^= 1;
   for (int it = 0; it < nb; ++it) {
@@ -738,18 +839,10 @@ int wide_iteration(const ldc_fv_wide* h, int nb, hipStream_t st) {
   }
   WIDE_LAUNCH(fv_wide_linfinish, 1, kWT, a, nb, par); par ^= 1;
   WIDE_LAUNCH(fv_wide_faces, G, kWT, a, par); par ^= 1;
-  double* w = d.work;
-  double *Cv = w + (int64_t)FV_C * n, *W1 = w + (int64_t)FV_W1 * n, *W2 = w + (int64_t)FV_W2 * n,
-         *Y = w + (int64_t)FV_Y * n;
-  const int tiles = ((ny + 15) / 16) * ((nx + 15) / 16), gg = (tiles + kWW - 1) / kWW;
-  const FvWideGemm g1 = {d.Qy, Cv, W1, 1, ny, nx, 1, ny, nx, ny};     // W1 = Qy^T C
-  const FvWideGemm g2 = {W1, d.Qx, W2, nx, 1, nx, 1, ny, nx, nx};     // W2 = W1 Qx / Lambda
-  const FvWideGemm g3 = {d.Qy, W2, W1, ny, 1, nx, 1, ny, nx, ny};     // W1 = Qy W2
-  const FvWideGemm g4 = {W1, d.Qx, Y, nx, 1, 1, nx, ny, nx, nx};      // Y = W1 Qx^T
-  WIDE_LAUNCH((fv_wide_gemm<true, false>), gg, kWT, a, g1, par);
-  WIDE_LAUNCH((fv_wide_gemm<false, true>), gg, kWT, a, g2, par);
-  WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, g3, par);
-  WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, g4, par);
+  WIDE_LAUNCH((fv_wide_gemm<true, false>), gg, kWT, a, wide_gemm_of(d, 0), par);
+  WIDE_LAUNCH((fv_wide_gemm<false, true>), gg, kWT, a, wide_gemm_of(d, 1), par);
+  WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, wide_gemm_of(d, 2), par);
+  WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, wide_gemm_of(d, 3), par);
   WIDE_LAUNCH(fv_wide_correct, G, kWT, a);
   WIDE_LAUNCH(fv_wide_fluxvort, G, kWT, a);
   WIDE_LAUNCH(fv_wide_sums, G, kWT, a);
@@ -757,13 +850,41 @@ int wide_iteration(const ldc_fv_wide* h, int nb, hipStream_t st) {
   return 0;
 }
 
+// the same chain for all trials of a batch: every launch carries the work-groups of all of them
+int wide_iteration(const ldc_fv_wide_batch* b, int nb, hipStream_t st) {
+  const FvWideTable& t = b->t;
+  const int G = b->sweep_groups, gg = b->gemm_groups, n = b->n;
+  int par = 0;
+  WIDE_LAUNCH(fv_wide_b_assemble, G, kWT, t, par); par ^= 1;
+  for (int it = 0; it < nb; ++it) {
+    WIDE_LAUNCH(fv_wide_b_bicg_p, G, kWT, t, it, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_b_bicg_v, G, kWT, t, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_b_bicg_s, G, kWT, t, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_b_bicg_t, G, kWT, t, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_b_bicg_x, G, kWT, t, it, par); par ^= 1;
+  }
+  WIDE_LAUNCH(fv_wide_b_linfinish, n, kWT, t, nb, par); par ^= 1;
+  WIDE_LAUNCH(fv_wide_b_faces, G, kWT, t, par); par ^= 1;
+  WIDE_LAUNCH((fv_wide_b_gemm<true, false>), gg, kWT, t, 0, par);
+  WIDE_LAUNCH((fv_wide_b_gemm<false, true>), gg, kWT, t, 1, par);
+  WIDE_LAUNCH((fv_wide_b_gemm<false, false>), gg, kWT, t, 2, par);
+  WIDE_LAUNCH((fv_wide_b_gemm<false, false>), gg, kWT, t, 3, par);
+  WIDE_LAUNCH(fv_wide_b_correct, G, kWT, t);
+  WIDE_LAUNCH(fv_wide_b_fluxvort, G, kWT, t);
+  WIDE_LAUNCH(fv_wide_b_sums, G, kWT, t);
+  WIDE_LAUNCH(fv_wide_b_record, n, kWT, t);
+  return 0;
+}
+
 // Budgets above this are launched one by one: the graph of an iteration has 11 + 5 nb nodes
 constexpr int kWideGraphMaxNb = 64;
 
-// The graph of ONE iteration with nb BiCGSTAB iterations: a linear chain captured on this unit's private stream (relaxed
-// mode: kernel launches only, no call elsewhere needs to be prohibited meanwhile), instantiated once and kept.
-int wide_graph(ldc_fv_wide* h, int nb, hipGraphExec_t* out) {
-  for (const auto& g : h->graphs)
+// The graph of ONE iteration of `h` (a lone handle or a batch) with nb BiCGSTAB iterations: a linear chain captured on
+// this unit's private stream (relaxed mode: kernel launches only, no call elsewhere needs to be prohibited meanwhile),
+// instantiated once and kept.
+template <class Handle>
+int wide_graph(Handle* h, int nb, hipGraphExec_t* out) {
+  for (const auto& g : h->gs.graphs)
     if (g.first == nb) { *out = g.second; return 0; }
   std::lock_guard<std::mutex> lock(g_wide_mutex);
   hipStream_t cs = nullptr;
@@ -782,9 +903,47 @@ int wide_graph(ldc_fv_wide* h, int nb, hipGraphExec_t* out) {
   const hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
   (void)hipGraphDestroy(g);
   if (ie != hipSuccess) return (int)ie;
-  h->graphs.emplace_back(nb, exec);
+  h->gs.graphs.emplace_back(nb, exec);
   *out = exec;
   return 0;
+}
+
+// `chains` iterations of `h` at nb BiCGSTAB iterations each on `st`, behind the `begin` launch the caller has made: the
+// handle's graph replayed, or every kernel on its own
+template <class Handle>
+int wide_chains(Handle* h, int chains, int nb, hipStream_t st) {
+  hipGraphExec_t exec = nullptr;
+  if (h->graph && nb <= kWideGraphMaxNb) {
+    const int rc = wide_graph(h, nb, &exec);
+    if (rc != 0) return rc;
+    if (!h->gs.done) {
+      const hipError_t e = hipEventCreateWithFlags(&h->gs.done, hipEventDisableTiming);
+      if (e != hipSuccess) return (int)e;
+    }
+  }
+  for (int k = 0; k < chains; ++k) {
+    if (exec) {
+      const hipError_t e = hipGraphLaunch(exec, st);
+      if (e != hipSuccess) return (int)e;
+    } else {
+      const int rc = wide_iteration(h, nb, st);
+      if (rc != 0) return rc;
+    }
+  }
+  if (exec) {
+    const hipError_t e = hipEventRecord(h->gs.done, st);
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
+}
+
+// destroy: wait for the last replay, then free the graphs
+void wide_graphs_free(WideGraphs& gs) {
+  if (gs.done) {
+    (void)hipEventSynchronize(gs.done);
+    (void)hipEventDestroy(gs.done);
+  }
+  for (const auto& g : gs.graphs) (void)hipGraphExecDestroy(g.second);
 }
 
 }  // namespace
@@ -820,18 +979,13 @@ int ldc_fv_wide_create(const struct ldc_fv_problem* pr, double* scratch, int64_t
   s->a.G = (int)LDC_FV_WIDE_GROUPS(pr->nx, pr->ny);
   s->device = dev;
   s->graph = LDC_FV_WIDE_GRAPH_DEFAULT;
-  s->done = nullptr;
   *out = s;
   return 0;
 }
 
 int ldc_fv_wide_destroy(ldc_fv_wide* h) {
   if (!h) return LDC_E_STATE;
-  if (h->done) {
-    (void)hipEventSynchronize(h->done);
-    (void)hipEventDestroy(h->done);
-  }
-  for (const auto& g : h->graphs) (void)hipGraphExecDestroy(g.second);
+  wide_graphs_free(h->gs);
   delete h;
   return 0;
 }
@@ -850,31 +1004,8 @@ int ldc_fv_wide_enqueue(ldc_fv_wide* h, int n_iters, int lin_budget, void* strea
   if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
   if (dev != h->device) return LDC_E_STATE;
   hipStream_t st = as_stream(stream);
-  const int nb = lin_budget < h->a.d.maxit ? lin_budget : h->a.d.maxit;
-  hipGraphExec_t exec = nullptr;
-  if (h->graph && nb <= kWideGraphMaxNb) {
-    const int rc = wide_graph(h, nb, &exec);
-    if (rc != 0) return rc;
-    if (!h->done) {
-      const hipError_t e = hipEventCreateWithFlags(&h->done, hipEventDisableTiming);
-      if (e != hipSuccess) return (int)e;
-    }
-  }
-  WIDE_LAUNCH(fv_wide_begin, 1, 64, h->a);
-  for (int k = 0; k < n_iters; ++k) {
-    if (exec) {
-      const hipError_t e = hipGraphLaunch(exec, st);
-      if (e != hipSuccess) return (int)e;
-    } else {
-      const int rc = wide_iteration(h, nb, st);
-      if (rc != 0) return rc;
-    }
-  }
-  if (exec) {
-    const hipError_t e = hipEventRecord(h->done, st);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
+  WIDE_LAUNCH(fv_wide_begin, 1, 64, h->a, n_iters);
+  return wide_chains(h, n_iters, lin_budget < h->a.d.maxit ? lin_budget : h->a.d.maxit, st);
 }
 
 int ldc_fv_wide_launches(const ldc_fv_wide* h, int lin_budget) {
@@ -890,6 +1021,93 @@ int ldc_fv_wide_status(ldc_fv_wide* h) {
   e = wide_copy_now(&ovf, reinterpret_cast<long long*>(h->a.scr) + WW_OVF, sizeof(ovf));
   if (e != hipSuccess) return (int)e;
   return nan_flag ? LDC_FV_E_NAN : (ovf ? LDC_FV_WIDE_E_BUDGET : 0);
+}
+
+int ldc_fv_wide_batch_create(ldc_fv_wide* const* hs, int n, void* table, int64_t table_len, ldc_fv_wide_batch** out) {
+  if (!out) return LDC_E_ARG;
+  *out = nullptr;
+  if (!hs || n < 1 || n > LDC_FV_WIDE_BATCH_MAX || !table) return LDC_E_ARG;
+  for (int q = 0; q < n; ++q)
+    if (!hs[q]) return LDC_E_STATE;
+  int64_t sweep = 0, gemm = 0;
+  for (int q = 0; q < n; ++q) {
+    for (int r = 0; r < q; ++r)
+      if (hs[r] == hs[q]) return LDC_E_ARG;
+    if (hs[q]->a.d.maxit != hs[0]->a.d.maxit) return LDC_E_ARG;
+    sweep += hs[q]->a.G;
+    gemm += LDC_FV_WIDE_GEMM_GROUPS(hs[q]->a.d.nx, hs[q]->a.d.ny);
+  }
+  if (table_len < LDC_FV_WIDE_BATCH_TABLE_LEN(n, sweep, gemm)) return LDC_E_ARG;
+  for (int q = 1; q < n; ++q)
+    if (hs[q]->device != hs[0]->device) return LDC_E_STATE;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
+  if (dev != hs[0]->device) return LDC_E_STATE;
+  ldc_fv_wide_batch* b = new (std::nothrow) ldc_fv_wide_batch;
+  if (!b) return LDC_E_STATE;
+  b->n = n; b->maxit = hs[0]->a.d.maxit; b->device = dev; b->graph = LDC_FV_WIDE_GRAPH_DEFAULT;
+  b->sweep_groups = (int)sweep; b->gemm_groups = (int)gemm;
+  // the image of the table: entries, the block map of the sweeps, that of the GEMMs
+  std::vector<char> image((size_t)LDC_FV_WIDE_BATCH_TABLE_LEN(n, sweep, gemm), 0);
+  FvWideEntry* entries = reinterpret_cast<FvWideEntry*>(image.data());
+  uint32_t* smap = reinterpret_cast<uint32_t*>(image.data() + sizeof(FvWideEntry) * (size_t)n);
+  uint32_t* gmap = smap + sweep;
+  for (int q = 0; q < n; ++q) {
+    entries[q].a = hs[q]->a;
+    b->rec_cap[q] = hs[q]->a.d.rec_cap;
+    const int gq = (int)LDC_FV_WIDE_GEMM_GROUPS(hs[q]->a.d.nx, hs[q]->a.d.ny);
+    for (int g = 0; g < hs[q]->a.G; ++g) *smap++ = (uint32_t)q << 16 | (uint32_t)g;
+    for (int g = 0; g < gq; ++g) *gmap++ = (uint32_t)q << 16 | (uint32_t)g;
+  }
+  char* base = static_cast<char*>(table);
+  b->t.entries = reinterpret_cast<const FvWideEntry*>(base);
+  b->t.sweep = reinterpret_cast<const uint32_t*>(base + sizeof(FvWideEntry) * (size_t)n);
+  b->t.gemm = b->t.sweep + sweep;
+  const hipError_t e = wide_copy_now(table, image.data(), image.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    delete b;
+    return (int)e;
+  }
+  *out = b;
+  return 0;
+}
+
+int ldc_fv_wide_batch_destroy(ldc_fv_wide_batch* b) {
+  if (!b) return LDC_E_STATE;
+  wide_graphs_free(b->gs);
+  delete b;
+  return 0;
+}
+
+int ldc_fv_wide_batch_set_graph(ldc_fv_wide_batch* b, int on) {
+  if (!b) return LDC_E_STATE;
+  if (on != 0 && on != 1) return LDC_E_ARG;
+  b->graph = on;
+  return 0;
+}
+
+int ldc_fv_wide_batch_enqueue(ldc_fv_wide_batch* b, const int32_t* n_iters, int lin_budget, void* stream) {
+  if (!b) return LDC_E_STATE;
+  if (!n_iters || lin_budget < 1 || b->n < 1 || b->n > LDC_FV_WIDE_BATCH_MAX) return LDC_E_ARG;
+  FvWideQuotas quotas = {};
+  int chains = 0;
+  for (int q = 0; q < b->n; ++q) {
+    if (n_iters[q] < 0 || n_iters[q] > b->rec_cap[q]) return LDC_E_ARG;
+    quotas.q[q] = n_iters[q];
+    if (n_iters[q] > chains) chains = n_iters[q];
+  }
+  if (chains < 1) return LDC_E_ARG;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
+  if (dev != b->device) return LDC_E_STATE;
+  hipStream_t st = as_stream(stream);
+  WIDE_LAUNCH(fv_wide_b_begin, b->n, 64, b->t, quotas);
+  return wide_chains(b, chains, lin_budget < b->maxit ? lin_budget : b->maxit, st);
+}
+
+int ldc_fv_wide_batch_launches(const ldc_fv_wide_batch* b, int lin_budget) {
+  if (!b || lin_budget < 1) return LDC_E_ARG;
+  return 11 + 5 * (lin_budget < b->maxit ? lin_budget : b->maxit);
 }
 
 }  // extern "C"

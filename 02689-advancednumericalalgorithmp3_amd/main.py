@@ -142,17 +142,21 @@ SG, FSG, FV = "solvers.spectral.sg.SGSolver", "solvers.spectral.fsg.FSGSolver", 
 FV_FSG = "solvers.fv.fsg.FVFSGSolver"        # coarse-to-fine sequences of finite-volume trials (solver=fv/fsg)
 FV_TARGETS = (FV, FV_FSG)
 FV_LAUNCH_MAX = 256        # LDC_FV_LAUNCH_MAX (include/ldc_fv.h): one finite-volume work-group per CU of an MI355X
+FV_WIDE_BATCH_MAX = 256    # LDC_FV_WIDE_BATCH_MAX: mapping="shared" trials of one batch object
 
 
 def batch_key(cfg: dict) -> tuple:
     """What the trials of one batch must share.  Spectral trials: solver class, N, level hierarchy, diagnostics flag and
     nx / ny (solver.ny=... overrides).  Finite-volume trials: the solver class alone -- the FV kernel advances any mix
     of sizes, schemes and parameters in one launch (solvers.fv.batched); sequenced trials (solver=fv/fsg) of any
-    sizes and depths form a batch of their own (BatchedFVFSGSolver)."""
+    sizes and depths form a batch of their own (BatchedFVFSGSolver).  Trials with mapping="shared" share every launch,
+    with each other only: a key of their own."""
     sv = cfg["solver"]
     if sv["_target_"] in FV_TARGETS:
         if sv.get("mapping", "cu") == "chip":     # a chip trial takes every CU: it never shares a launch (batch_sizes)
             return (sv["_target_"], "chip")
+        if sv.get("mapping", "cu") == "shared":   # shared trials share every launch, but only with each other
+            return (sv["_target_"], "shared")
         return (sv["_target_"],)
     return (sv["_target_"], int(cfg["N"]), int(sv.get("n_levels", 0)), bool(sv.get("diagnostics", True)),
             int(sv.get("nx", cfg["N"])), int(sv.get("ny", cfg["N"])))
@@ -178,10 +182,14 @@ def batch_sizes(key: tuple, count: int, max_batch: int, given: bool) -> list:
         return []
     if target in FV_TARGETS and key[1:] == ("chip",):
         return []
+    if key == (FV_FSG, "shared"):                 # sequenced shared trials have no batch: their levels are batches of one
+        return []
     if given or (target not in FV_TARGETS and int(key[1]) + 1 > 44):
         cap = max_batch
     else:
         cap = max(max_batch, FV_LAUNCH_MAX)
+    if key == (FV, "shared"):                     # one batch object of the library takes that many, whatever the user's cap
+        cap = min(cap, FV_WIDE_BATCH_MAX)
     return [min(cap, count - lo) for lo in range(0, count, cap)]
 
 

@@ -103,9 +103,11 @@ class FVParameters(Parameters):
     anderson_depth: int = 5
     anderson_start: int = 10
     # how a trial is laid on the device: "cu" (one work-group on one CU for its whole life; batches of them fill the
-    # chip) or "chip" (one kernel launch per phase over all CUs, 8 ... 1024 cells per axis, lone trials only), and the
-    # BiCGSTAB iterations the first chunk of a "chip" solve carries per SIMPLE iteration (doubled when a solve needs
-    # more).  Neither changes what is computed beyond rounding: they stay out of MLflow, like device
+    # chip), "chip" (one kernel launch per phase over all CUs, 8 ... 1024 cells per axis, lone trials only) or "shared"
+    # (the chip mapping's launches shared by all trials of a batch: for sweeps of fewer trials than CUs; bit-identical
+    # to "chip"), and the BiCGSTAB iterations the first chunk of a "chip" or "shared" solve carries per SIMPLE iteration
+    # (doubled when a solve needs more).  Neither changes what is computed beyond rounding: they stay out of MLflow,
+    # like device
     mapping: str = "cu"
     linear_budget: int = 12
 

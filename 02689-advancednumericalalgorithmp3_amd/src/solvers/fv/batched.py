@@ -14,6 +14,14 @@ work-groups resident at once and give up after a bounded spin.  So every FV chun
 ``ldc_lib.resident_lock``, like those launches do: in a mixed sweep an FV chunk and a co-resident spectral chunk take
 turns, while launch-path spectral batches of other streams still run beside either.
 
+Trials that are all ``mapping="shared"`` are one batch object of the library instead (``solver.SharedBatch``,
+``ldc_fv_wide_batch_*``): every phase of the iteration is ONE launch that carries the work-groups of all trials, min(256,
+cells / 256) each, so a handful of trials already spreads over the chip where the one-CU mapping would leave it idle.
+A trial is the same launches' work alone and in a batch: its results are bit-identical to its lone ``mapping="chip"``
+or ``"shared"`` solve.  A chunk hands every live trial a quota of iterations and everyone else quota 0, so finished
+trials stay in the batch object and cost empty work-groups; a trial whose momentum solves need more BiCGSTAB launches
+than the chunk carried is enqueued again on its own with twice the budget (``solver.advance_batch_with_budget``).
+
 ``BatchedFVFSGSolver`` is the same for coarse-to-fine sequences (solvers.fv.fsg): stage by stage, every stage a batch of
 ordinary trials, one ``prolong`` launch between stages.
 """
@@ -27,7 +35,7 @@ import numpy as np
 from ..base import WARMUP_ITERATIONS
 from . import ldc_fv_lib as F
 from .fsg import FVFSGSolver, level_tolerance
-from .solver import FVSolver, advance, postprocess, prolong
+from .solver import FVSolver, SharedBatch, advance, postprocess, prolong
 
 log = logging.getLogger(__name__)
 
@@ -73,6 +81,7 @@ class BatchedFVSolver:
     is kept in ``errors[index]`` instead of raised, and the other trials are not disturbed."""
 
     Solver = FVSolver
+    _shares_launches = True                   # mapping="shared" trials are taken (as one batch object of the library)
 
     def __init__(self, trials: list):
         if not trials:
@@ -80,7 +89,16 @@ class BatchedFVSolver:
         for t in trials:
             if t.get("mapping", "cu") == "chip":
                 raise ValueError("mapping='chip' inside a batch: a chip trial takes every CU, run it on its own")
-        self.solvers = []
+        maps = {t.get("mapping", "cu") for t in trials}
+        if "shared" in maps and not self._shares_launches:
+            raise ValueError(f"mapping='shared' in a {type(self).__name__}: sequenced trials do not share their launches "
+                             f"yet, run them one by one or with mapping='cu'")
+        if "shared" in maps and maps != {"shared"}:
+            raise ValueError(f"mapping='shared' beside mapping={sorted(maps - {'shared'})[0]!r} in one batch: the trials "
+                             f"of a batch either share every launch or have a CU each")
+        if "shared" in maps and len(trials) > F.WIDE_BATCH_MAX:
+            raise ValueError(f"{len(trials)} mapping='shared' trials in one batch: at most {F.WIDE_BATCH_MAX}")
+        self.solvers, self.shared = [], None
         try:
             for t in trials:
                 self.solvers.append(self.Solver(**t))
@@ -93,6 +111,12 @@ class BatchedFVSolver:
         if len(devs) != 1:
             self.close()
             raise ValueError(f"all trials of a batch must be on one device, got {sorted(devs)}")
+        if maps == {"shared"}:
+            try:
+                self.shared = SharedBatch(self.solvers)       # one batch object for the life of this one
+            except BaseException:
+                self.close()
+                raise
         self.errors = {}
         self.batch_seconds, self.batch_size = 0.0, len(self.solvers)
 
@@ -100,11 +124,27 @@ class BatchedFVSolver:
         return len(self.solvers)
 
     def close(self):
+        if getattr(self, "shared", None) is not None:
+            self.shared.close()
+            self.shared = None
         for s in self.solvers:
             s.close()
 
+    def set_wide_graph(self, on: bool):
+        """The launches of a batch of ``"shared"`` trials: one replayed hipGraph per iteration or every kernel on its own
+        (``FVSolver.set_wide_graph`` for the batch object)."""
+        if self.shared is None:
+            raise ValueError("set_wide_graph: only a batch of mapping='shared' trials has launches to capture")
+        self.shared.set_graph(on)
+
     def _step(self, live, k):
-        """One chunk of the live trials (solver.advance: one launch, one copy of the ctrl words, one of the rows)."""
+        """One chunk of the live trials (solver.advance: one launch, one copy of the ctrl words, one of the rows).
+
+        ``"shared"`` trials: quota ``k`` for the live ones and 0 for the others, in the launches of the one batch object;
+        back only when every live trial has done ``k`` iterations, latched or gone NaN (``SharedBatch.advance``)."""
+        if self.shared is not None:
+            out = self.shared.advance([k if q in live else 0 for q in range(len(self.solvers))])
+            return [out[q] for q in live]
         return advance([self.solvers[q] for q in live], k)
 
     def solve(self, max_iter: int = None):
@@ -132,7 +172,10 @@ class BatchedFVSolver:
     def _nan_error(s, total):
         """What a lone _advance raises for a trial whose kernel reports a NaN (ldc_fv_status -> LDC_FV_E_NAN)."""
         try:
-            F.check(F.lib().ldc_fv_status(s.handle), f"FV trial at iteration {total}")
+            if s.shared:                      # (a trial above 256 cells per axis has no one-CU handle to ask)
+                F.check(F.lib().ldc_fv_wide_status(s._wide), f"FV trial at iteration {total}")
+            else:
+                F.check(F.lib().ldc_fv_status(s.handle), f"FV trial at iteration {total}")
             raise RuntimeError(f"FV trial at iteration {total}: ctrl reports a NaN, ldc_fv_status does not")
         except Exception as exc:
             return exc
@@ -170,6 +213,7 @@ class BatchedFVFSGSolver(BatchedFVSolver):
     on a NaN on any level gets that level's ``LdcError`` in ``errors[index]`` and goes no further."""
 
     Solver = FVFSGSolver
+    _shares_launches = False                  # (its stages advance ordinary one-CU trials)
 
     def solve(self, max_iter: int = None):
         ps = [s.params for s in self.solvers]

@@ -19,6 +19,7 @@ ANDERSON_LAUNCH_MAX, ANDERSON_MAX_DEPTH, ANDERSON_STATE_LEN = 96, 16, 4
 ASTATE_COLUMNS, ASTATE_POSITION, ASTATE_SEEN, ASTATE_FALLBACKS = range(4)
 E_NAN = -5
 WIDE_MAX_N = 1024
+WIDE_BATCH_MAX, WIDE_BATCH_ENTRY_BYTES = 256, 256        # LDC_FV_WIDE_BATCH_MAX, LDC_FV_WIDE_BATCH_ENTRY_BYTES
 E_BUDGET = -6                  # ldc_fv_wide_status: the last enqueue ran out of BiCGSTAB launches (LDC_FV_WIDE_E_BUDGET)
 CTRL_DONE, CTRL_ITER, CTRL_NAN, CTRL_GIVEUP, CTRL_LIN_ITERS, CTRL_SOLVES = range(6)
 # slots of a result block of ldc_fv_post_enqueue (LDC_FV_POST_*)
@@ -57,7 +58,9 @@ class Anderson(C.Structure):
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
            "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
            "ldc_fv_anderson_enqueue", "ldc_fv_wide_create", "ldc_fv_wide_destroy", "ldc_fv_wide_enqueue",
-           "ldc_fv_wide_launches", "ldc_fv_wide_status", "ldc_fv_wide_set_graph")
+           "ldc_fv_wide_launches", "ldc_fv_wide_status", "ldc_fv_wide_set_graph", "ldc_fv_wide_batch_create",
+           "ldc_fv_wide_batch_destroy", "ldc_fv_wide_batch_enqueue", "ldc_fv_wide_batch_set_graph",
+           "ldc_fv_wide_batch_launches")
 
 _bound = None
 
@@ -85,6 +88,18 @@ def wide_scratch_len(nx: int, ny: int) -> int:
     return 80 + 30 * wide_groups(nx, ny)
 
 
+def wide_gemm_groups(nx: int, ny: int) -> int:
+    """Work-groups of one GEMM launch of a chip or shared trial (LDC_FV_WIDE_GEMM_GROUPS): four 16 x 16 tiles each."""
+    return (((ny + 15) // 16) * ((nx + 15) // 16) + 3) // 4
+
+
+def wide_batch_table_len(sizes) -> int:
+    """LDC_FV_WIDE_BATCH_TABLE_LEN for trials of ``sizes`` [(nx, ny)]: the BYTES of the batch's table."""
+    sizes = list(sizes)
+    return (WIDE_BATCH_ENTRY_BYTES * len(sizes)
+            + 4 * sum(wide_groups(nx, ny) + wide_gemm_groups(nx, ny) for nx, ny in sizes))
+
+
 def lib() -> C.CDLL:
     """The shared library with the FV entry points' signatures set (raises if it has not been built)."""
     global _bound
@@ -109,6 +124,11 @@ def lib() -> C.CDLL:
         L.ldc_fv_wide_launches.argtypes = [_dp, C.c_int]
         L.ldc_fv_wide_status.argtypes = [_dp]
         L.ldc_fv_wide_set_graph.argtypes = [_dp, C.c_int]
+        L.ldc_fv_wide_batch_create.argtypes = [C.POINTER(_dp), C.c_int, _dp, C.c_int64, C.POINTER(_dp)]
+        L.ldc_fv_wide_batch_destroy.argtypes = [_dp]
+        L.ldc_fv_wide_batch_enqueue.argtypes = [_dp, C.POINTER(C.c_int32), C.c_int, _dp]
+        L.ldc_fv_wide_batch_set_graph.argtypes = [_dp, C.c_int]
+        L.ldc_fv_wide_batch_launches.argtypes = [_dp, C.c_int]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -152,3 +172,18 @@ def anderson_enqueue(handles, blocks, n_iters: int, stream) -> None:
     arr = (_dp * len(handles))(*[h.value if isinstance(h, _dp) else h for h in handles])
     acc = (Anderson * len(blocks))(*blocks)
     check(lib().ldc_fv_anderson_enqueue(arr, acc, len(handles), int(n_iters), _dp(stream)), "ldc_fv_anderson_enqueue")
+
+
+def wide_batch_create(handles, table_ptr: int, table_len: int) -> _dp:
+    """The batch object of ``handles`` (ldc_fv_wide handles of one device) with its table in the caller's device buffer."""
+    arr = (_dp * len(handles))(*[h.value if isinstance(h, _dp) else h for h in handles])
+    out = _dp()
+    check(lib().ldc_fv_wide_batch_create(arr, len(handles), _dp(table_ptr), int(table_len), C.byref(out)),
+          "ldc_fv_wide_batch_create")
+    return out
+
+
+def wide_batch_enqueue(batch, quotas, lin_budget: int, stream) -> None:
+    """``quotas[q]`` iterations of trial q (0: the trial is left alone), all in the same launches; nothing synchronises."""
+    arr = (C.c_int32 * len(quotas))(*[int(k) for k in quotas])
+    check(lib().ldc_fv_wide_batch_enqueue(batch, arr, int(lin_budget), _dp(stream)), "ldc_fv_wide_batch_enqueue")

@@ -26,7 +26,7 @@ log = logging.getLogger(__name__)
 SCHEMES = {"Upwind": 0, "TVD": 1}
 VORTEX_METRICS = ("host", "device")
 ACCELERATIONS = ("none", "anderson")
-MAPPINGS = ("cu", "chip")
+MAPPINGS = ("cu", "chip", "shared")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
 
 
@@ -216,9 +216,135 @@ def advance_with_budget(step, start, k, budget, max_lin_iters):
     return rows, int(latch), int(nan), total, budget, retries
 
 
+def advance_batch_with_budget(step, starts, ks, budgets, max_lin_iters):
+    """``advance_with_budget`` for trials that share their launches (``mapping="shared"``): trial q stands at iteration
+    ``starts[q]`` and is to do ``ks[q]`` more (0: it is left alone), whatever BiCGSTAB budget they need.
+
+    ``step(quotas, budget)`` enqueues up to ``quotas[q]`` iterations of every trial in the same launches with ``budget``
+    BiCGSTAB iterations each, waits, and returns per trial (rows of the iterations it completed, latch, nan, iteration
+    count, overflow).  The first call carries every trial with ``ks[q] > 0`` at the largest of their budgets.  A trial
+    that overflowed has learnt that the call's budget is not enough: its own budget becomes twice that, at most
+    ``max_lin_iters``, and it is enqueued again with what is left of its count, beside the others that overflowed and
+    with quota 0 for everyone else; and so on until nobody overflows.  A trial that needed no more keeps its budget.
+    Returns per trial (rows, latch, nan, iteration count, budget now, retries): no iteration is lost or counted twice."""
+    import numpy as np
+    n = len(starts)
+    starts = [int(x) for x in starts]
+    totals, budgets, retries = list(starts), [int(b) for b in budgets], [0] * n
+    blocks, flags = [[] for _ in range(n)], [(0, 0)] * n
+    todo = [q for q in range(n) if ks[q] > 0]
+    while todo:
+        quotas = [0] * n
+        for q in todo:
+            quotas[q] = int(ks[q]) - (totals[q] - starts[q])
+        budget = max(budgets[q] for q in todo)
+        out = step(list(quotas), budget)
+        if len(out) != n:
+            raise RuntimeError("one result per trial expected")
+        again = []
+        for q, (rows, latch, nan, new_total, overflow) in enumerate(out):
+            if len(rows) != new_total - totals[q]:
+                raise RuntimeError(f"trial {q}: {len(rows)} record rows for iterations {totals[q]} ... {new_total}")
+            if quotas[q] == 0:
+                if new_total != totals[q]:
+                    raise RuntimeError(f"trial {q} had quota 0 and went from iteration {totals[q]} to {new_total}")
+                continue
+            blocks[q].append(rows)
+            totals[q] = int(new_total)
+            flags[q] = (int(latch), int(nan))
+            if latch or nan:
+                continue
+            if overflow:
+                if budget >= max_lin_iters:
+                    raise RuntimeError(f"trial {q}: linear budget {budget} >= max_lin_iters {max_lin_iters} reported "
+                                       f"an overflow")
+                budgets[q] = min(2 * budget, int(max_lin_iters))
+                retries[q] += 1
+                again.append(q)
+            elif totals[q] - starts[q] < ks[q]:
+                raise RuntimeError(f"trial {q}: device loop made no progress")
+        todo = again
+    return [(np.concatenate(b, axis=0) if b else np.zeros((0, F.REC_LEN)), latch, nan, total, budget, r)
+            for b, (latch, nan), total, budget, r in zip(blocks, flags, totals, budgets, retries)]
+
+
+class SharedBatch:
+    """``solvers`` (FVSolvers with ``mapping="shared"`` on one device, at most ``WIDE_BATCH_MAX``) as ONE batch object of
+    the library (``ldc_fv_wide_batch_*``): every phase launch carries the work-groups of all of them, and an enqueue gives
+    every trial its own quota of iterations.  The table the kernels look their work-group up in lives in a tensor of this
+    object.  A lone shared trial is a batch of one."""
+
+    def __init__(self, solvers, graph=None):
+        import torch
+        self.solvers = list(solvers)
+        if not 1 <= len(self.solvers) <= F.WIDE_BATCH_MAX:
+            raise ValueError(f"{len(self.solvers)} trials in one shared batch: 1 ... {F.WIDE_BATCH_MAX}")
+        self.device = self.solvers[0].device
+        self._wides = [s._wide.value for s in self.solvers]
+        self.handle = None
+        with torch.cuda.device(self.device):
+            self.table = torch.empty(F.wide_batch_table_len([(s.nx, s.ny) for s in self.solvers]), dtype=torch.uint8,
+                                     device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()      # (create copies the table on the library's stream)
+            self.handle = F.wide_batch_create(self._wides, self.table.data_ptr(), self.table.numel())
+        if graph is not None:
+            self.set_graph(graph)
+
+    def set_graph(self, on: bool):
+        F.check(F.lib().ldc_fv_wide_batch_set_graph(self.handle, int(bool(on))), "ldc_fv_wide_batch_set_graph")
+
+    def close(self):
+        if self.handle is not None:
+            F.lib().ldc_fv_wide_batch_destroy(self.handle)
+            self.handle = None
+
+    def _step(self, quotas, budget):
+        """ONE enqueue and ONE wait, then one copy each of the control words, the overflow words and the new record rows
+        (``advance_batch_with_budget``'s step)."""
+        import torch
+        from solvers.spectral import ldc_lib
+        from solvers.spectral.chunks import _words
+        dev, ss = self.device, self.solvers
+        index = torch.cuda.current_device() if dev.index is None else dev.index
+        with torch.cuda.device(dev):
+            with ldc_lib.resident_lock(index):
+                F.wide_batch_enqueue(self.handle, quotas, budget, torch.cuda.current_stream(dev).cuda_stream)
+                ctrl = _words([s.t["ctrl"] for s in ss])          # (synchronises the stream)
+            overflow = _words([s.t["scratch"][:1].view(torch.int64) for s in ss])[:, 0]
+            new = [int(c[F.CTRL_ITER]) - t for c, t in zip(ctrl, self._totals)]
+            got = [s.t["rec"][:m] for s, m in zip(ss, new) if m > 0]
+            rows = torch.cat(got).cpu().numpy() if got else np.zeros((0, F.REC_LEN))
+        out, lo = [], 0
+        for q, (c, m) in enumerate(zip(ctrl, new)):
+            out.append((rows[lo: lo + m].copy(), int(c[F.CTRL_DONE]), int(c[F.CTRL_NAN]), int(c[F.CTRL_ITER]),
+                        int(overflow[q])))
+            lo += max(m, 0)
+            self._totals[q] = int(c[F.CTRL_ITER])
+        return out
+
+    def advance(self, ks):
+        """``ks[q]`` iterations of trial q (0: left alone; at most its record ring), all in the same launches, whatever
+        budgets they need; per trial (rows of the new iterations, latch, nan, iteration count).  Every trial's
+        ``linear_budget`` and ``linear_budget_retries`` go on as a lone trial's do."""
+        import torch
+        from solvers.spectral.chunks import _words
+        ss = self.solvers
+        if [s._wide.value if s._wide is not None else None for s in ss] != self._wides:
+            raise RuntimeError("a trial of a shared batch has a new device handle: the batch's table is out of date")
+        with torch.cuda.device(self.device):
+            self._totals = [int(t) for t in _words([s.t["ctrl"] for s in ss])[:, F.CTRL_ITER]]
+        out = advance_batch_with_budget(self._step, list(self._totals), [int(k) for k in ks],
+                                        [s.linear_budget for s in ss], LINEAR_MAX_ITERATIONS)
+        for s, (_, _, _, _, budget, retries) in zip(ss, out):
+            s.linear_budget = budget
+            s.linear_budget_retries += retries
+        return [(rows, latch, nan, total) for rows, latch, nan, total, _, _ in out]
+
+
 class FVSolver(LidDrivenCavitySolver):
     """Collocated finite-volume SIMPLE solver; ``nx`` x ``ny`` cells (8 ... 256 each with ``mapping="cu"``, one
-    work-group per trial; 8 ... 1024 with ``mapping="chip"``, one launch per phase over the whole chip)."""
+    work-group per trial; 8 ... 1024 with ``mapping="chip"``, one launch per phase over the whole chip, and with
+    ``mapping="shared"``, the same launches shared by all trials of a batch)."""
 
     Parameters = FVParameters
     rho = 1.0
@@ -241,18 +367,19 @@ class FVSolver(LidDrivenCavitySolver):
             raise ValueError(f"anderson_start={p.anderson_start}: an iteration count, at least 1")
         self.accelerated = p.acceleration == "anderson"
         if p.mapping not in MAPPINGS:
-            raise ValueError(f"mapping={p.mapping!r}: 'cu' or 'chip'")
+            raise ValueError(f"mapping={p.mapping!r}: 'cu', 'chip' or 'shared'")
         if int(p.linear_budget) < 1:
             raise ValueError(f"linear_budget={p.linear_budget}: BiCGSTAB iterations per SIMPLE iteration, at least 1")
-        self.chip = p.mapping == "chip"
+        self.shared = p.mapping == "shared"       # the phase kernels of csrc/ldc_fv_wide.hip: a launch of its own per
+        self.chip = p.mapping == "chip" or self.shared        # phase ("chip") or one for all trials of a batch ("shared")
         nx, ny = int(p.nx), int(p.ny)
         max_n = F.WIDE_MAX_N if self.chip else F.MAX_N
         if not (F.MIN_N <= nx <= max_n and F.MIN_N <= ny <= max_n):
             raise ValueError(f"nx, ny = {nx}, {ny}: the FV kernel takes {F.MIN_N} ... {max_n} cells per axis "
                              f"with mapping={p.mapping!r}")
         if self.chip and self.accelerated:
-            raise ValueError("acceleration='anderson' with mapping='chip': the mixing kernel follows the one-CU kernel's "
-                             "launches only")
+            raise ValueError(f"acceleration='anderson' with mapping={p.mapping!r}: the mixing kernel follows the one-CU "
+                             f"kernel's launches only")
         # the one-CU handle beside the wide one wherever it exists: postprocess, prolong and start_from use it
         self._has_cu_handle = not self.chip or max(nx, ny) <= F.MAX_N
         if self._needs_cu_handle and not self._has_cu_handle:
@@ -300,6 +427,7 @@ class FVSolver(LidDrivenCavitySolver):
         self.linear_budget_retries = 0
         self._handle = None
         self._wide = None
+        self._batch1 = None                      # a "shared" trial alone: the batch object of one it is advanced through
         self.wide_graph = None                   # None: the library's default; set_wide_graph() chooses
         self._handle_tol = None
         self._make_handle(p.tolerance)
@@ -334,9 +462,14 @@ class FVSolver(LidDrivenCavitySolver):
                 self._wide = h
                 if self.wide_graph is not None:
                     F.check(F.lib().ldc_fv_wide_set_graph(h, int(self.wide_graph)), "ldc_fv_wide_set_graph")
+                if self.shared:
+                    self._batch1 = SharedBatch([self], self.wide_graph)
         self._handle_tol = tolerance
 
     def _destroy_handle(self):
+        if getattr(self, "_batch1", None) is not None:
+            self._batch1.close()
+            self._batch1 = None
         if self._handle is not None:
             F.lib().ldc_fv_destroy(self._handle)
             self._handle = None
@@ -347,11 +480,14 @@ class FVSolver(LidDrivenCavitySolver):
 
     def set_wide_graph(self, on: bool):
         """A ``"chip"`` trial's launches: one replayed hipGraph per iteration (True) or every kernel on its own (False).
-        The same kernels in the same order either way (tools/fv_wide_perf.py measures both)."""
+        The same kernels in the same order either way (tools/fv_wide_perf.py measures both).  A ``"shared"`` trial
+        alone: the same for its batch of one (a batch of several has ``BatchedFVSolver.set_wide_graph``)."""
         if not self.chip:
             raise ValueError("set_wide_graph: only a mapping='chip' trial has launches to capture")
         self.wide_graph = bool(on)
         F.check(F.lib().ldc_fv_wide_set_graph(self._wide, int(self.wide_graph)), "ldc_fv_wide_set_graph")
+        if self._batch1 is not None:
+            self._batch1.set_graph(self.wide_graph)
 
     def _require_cu_handle(self, what: str):
         if self._handle is None:
@@ -448,6 +584,11 @@ class FVSolver(LidDrivenCavitySolver):
 
     def _advance(self, n_iters: int):
         n_iters = max(1, min(int(n_iters), self.rec_cap))
+        if self.shared:
+            rows, done, nan, total = self._batch1.advance([n_iters])[0]
+            if nan:
+                F.check(F.lib().ldc_fv_wide_status(self._wide), f"FV trial at iteration {total}")
+            return rows, done, total
         if self.chip:
             start = int(self.t["ctrl"][F.CTRL_ITER].item())
             rows, done, nan, total, self.linear_budget, retries = advance_with_budget(

@@ -92,6 +92,20 @@
  *    enqueue clears the word).  With lin_budget >= max_lin_iters a solve still active is the accepted give-up of
  *    ctrl[3].  So the result does not depend on the budget;
  *  - scratch: LDC_FV_WIDE_SCRATCH_LEN doubles owned by the caller, the library's between two enqueues of one solve too.
+ *
+ * Several such trials in the same launches (ldc_fv_wide_batch_*): a batch object over 1 .. LDC_FV_WIDE_BATCH_MAX
+ * ldc_fv_wide handles of any sizes and parameters (one max_lin_iters, one device).  Every phase is then ONE launch that
+ * carries the work-groups of all trials -- the sum of LDC_FV_WIDE_GROUPS for a cell sweep, the sum of
+ * LDC_FV_WIDE_GEMM_GROUPS for a GEMM, one per trial for begin, linfinish and record -- and a work-group finds its trial
+ * and its index within it in a table in a device buffer of the caller's (LDC_FV_WIDE_BATCH_TABLE_LEN bytes, written once
+ * by create).  Per trial nothing changes: the same kernels' bodies, the same G, slots and order of every sum, so a trial's
+ * u, v, p, mdot, rec and ctrl are bit-identical to those of ldc_fv_wide_enqueue on its own handle.
+ *  - an enqueue hands every trial its own number of iterations (its quota, 0 .. its rec_cap; a scratch word that
+ *    `begin` writes) and runs max(quota) iteration chains; a trial stops at its quota, its latch, a NaN or its overflow,
+ *    and the launches after that cost it empty work-groups.  A trial with quota 0 is not touched at all;
+ *  - overflow and NaN are per trial: ldc_fv_wide_status of the trial's own handle.  The caller enqueues the trials that
+ *    overflowed again with a larger budget and quota 0 for everyone else;
+ *  - the table is never rebuilt: finished trials stay in the batch object.
  */
 #ifndef LDC_FV_H
 #define LDC_FV_H
@@ -124,6 +138,13 @@ extern "C" {
 /* work-groups of a sweep over the cells (one slot of partial sums each) and the caller's scratch, in doubles */
 #define LDC_FV_WIDE_GROUPS(nx, ny) ((((int64_t)(nx) * (ny) + 255) / 256) < 256 ? (((int64_t)(nx) * (ny) + 255) / 256) : 256)
 #define LDC_FV_WIDE_SCRATCH_LEN(nx, ny) (80 + 30 * LDC_FV_WIDE_GROUPS(nx, ny))
+/* several trials in the same launches (ldc_fv_wide_batch_*): trials per batch, work-groups of one trial's GEMM launches,   */
+/* and the BYTES of the caller's device buffer for the batch's table: n entries, then one word per work-group of a cell  */
+/* sweep (sweep_groups: the sum of LDC_FV_WIDE_GROUPS over the trials) and of a GEMM launch (gemm_groups: likewise)      */
+#define LDC_FV_WIDE_BATCH_MAX 256
+#define LDC_FV_WIDE_BATCH_ENTRY_BYTES 256
+#define LDC_FV_WIDE_GEMM_GROUPS(nx, ny) ((((int64_t)(ny) + 15) / 16 * (((nx) + 15) / 16) + 3) / 4)
+#define LDC_FV_WIDE_BATCH_TABLE_LEN(n, sweep_groups, gemm_groups) (LDC_FV_WIDE_BATCH_ENTRY_BYTES * (int64_t)(n) + 4 * ((int64_t)(sweep_groups) + (int64_t)(gemm_groups)))
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
 #define LDC_FV_DBG_GRAD_P 0        /* 2n: d/dx p, then d/dy p                                    */
@@ -194,6 +215,7 @@ struct ldc_fv_anderson {
 
 typedef struct ldc_fv ldc_fv;
 typedef struct ldc_fv_wide ldc_fv_wide;
+typedef struct ldc_fv_wide_batch ldc_fv_wide_batch;
 
 int ldc_fv_version(void);
 /* Validate (no device needed), then write the trial's descriptor into the tail of `work` (synchronous copy on the */
@@ -247,6 +269,26 @@ int ldc_fv_wide_set_graph(ldc_fv_wide *h, int on);
 int ldc_fv_wide_launches(const ldc_fv_wide *h, int lin_budget);
 /* 0, LDC_FV_E_NAN, or LDC_FV_WIDE_E_BUDGET when the last enqueue overflowed (wait for its stream first). */
 int ldc_fv_wide_status(ldc_fv_wide *h);
+/* n (1 .. LDC_FV_WIDE_BATCH_MAX) trials of any sizes and parameters, one device, advanced by the same launches.  `table` */
+/* is a device buffer of table_len >= LDC_FV_WIDE_BATCH_TABLE_LEN bytes owned by the caller and left alone until destroy. */
+/* Validation comes first and needs no device: LDC_E_ARG for a null list, n out of range or a null table; LDC_E_STATE for  */
+/* a null handle; LDC_E_ARG for a handle listed twice, trials whose max_lin_iters differ and a short table; LDC_E_STATE    */
+/* for handles of different devices.  Then the device: LDC_E_STATE when it is not the handles', and ONE synchronous copy   */
+/* of the table on the library's own stream.  The batch keeps a copy of every trial's arguments, not the handles: each      */
+/* trial may still be advanced and asked for its status through its own handle (one of the two in flight at a time).        */
+int ldc_fv_wide_batch_create(ldc_fv_wide *const *hs, int n, void *table, int64_t table_len, ldc_fv_wide_batch **out);
+int ldc_fv_wide_batch_destroy(ldc_fv_wide_batch *b);
+/* n_iters[q] (0 .. rec_cap of trial q, at least one above 0) SIMPLE iterations of trial q with lin_budget (>= 1) BiCGSTAB */
+/* iterations each: one launch that hands every trial its quota, then max(n_iters) iteration chains, every launch carrying */
+/* the work-groups of all trials.  A trial stops at its quota, its latch, a NaN or ITS overflow (ldc_fv_wide_status of its  */
+/* own handle tells which); a trial with quota 0 is not touched: u, v, p, mdot, rec and ctrl stay as they are.  LDC_E_STATE */
+/* for a null batch, then LDC_E_ARG, then the device.                                                                       */
+int ldc_fv_wide_batch_enqueue(ldc_fv_wide_batch *b, const int32_t *n_iters, int lin_budget, void *stream);
+/* As ldc_fv_wide_set_graph: one linear hipGraph of the batch's iteration per budget value up to 64, captured on the        */
+/* library's own stream and replayed on the caller's; destroy waits for the last replay.                                    */
+int ldc_fv_wide_batch_set_graph(ldc_fv_wide_batch *b, int on);
+/* Kernel launches of ONE iteration chain at that budget (an enqueue adds one): those of a lone trial.  Needs no device. */
+int ldc_fv_wide_batch_launches(const ldc_fv_wide_batch *b, int lin_budget);
 
 #ifdef __cplusplus
 }
