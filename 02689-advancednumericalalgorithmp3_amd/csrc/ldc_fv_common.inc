@@ -1,10 +1,14 @@
-// ldc_fv_common.inc -- what the translation units of the finite-volume solver share (include/ldc_fv.h):
-// ldc_kernels.hip (through ldc_fv_kernel.inc, the SIMPLE iteration), ldc_fv_post.hip (streamfunction and vortex
-// metrics), ldc_fv_prolong.hip (coarse-to-fine transfer of the state) and ldc_fv_anderson.hip (Anderson mixing).  Types and constants only: each unit keeps its own device functions, so neither unit's code object
-// depends on the other's.
+// ldc_fv_common.inc -- what all translation units of the finite-volume solver share (include/ldc_fv.h):
+// ldc_kernels.hip (through ldc_fv_kernel.inc, the SIMPLE iteration with one trial per CU), ldc_fv_wide.hip (the same
+// iteration by the whole chip), ldc_fv_post.hip (streamfunction and vortex metrics), ldc_fv_prolong.hip (coarse-to-fine
+// transfer of the state) and ldc_fv_anderson.hip (Anderson mixing).
+// Types, constants and the host-side fill of a descriptor only, no device function: each unit's code object holds
+// what that unit needs and depends on no other's.  The device functions that the two units of the SIMPLE iteration
+// share are in ldc_fv_cells.inc, which post, prolong and anderson do not include.
 #ifndef LDC_FV_COMMON_INC
 #define LDC_FV_COMMON_INC
 
+#include "ldc_hip.h"
 #include "ldc_fv.h"
 
 typedef double v4d __attribute__((ext_vector_type(4)));
@@ -35,6 +39,28 @@ struct FvDesc {
   long long *ctrl;
 };
 static_assert(sizeof(FvDesc) <= LDC_FV_DESC_DOUBLES * sizeof(double), "descriptor slot");
+
+// host: validate `pr` (not null) for a mapping that takes grids up to max_n x max_n and fill the descriptor from it.
+// 0 or LDC_E_ARG; needs no device.
+inline int fv_desc_of(const struct ldc_fv_problem* pr, int max_n, FvDesc* h) {
+  if (pr->nx < LDC_FV_MIN_N || pr->nx > max_n || pr->ny < LDC_FV_MIN_N || pr->ny > max_n) return LDC_E_ARG;
+  if (pr->scheme != 0 && pr->scheme != 1) return LDC_E_ARG;
+  if (pr->rec_cap < 1 || pr->warmup < 0 || pr->max_lin_iters < 1) return LDC_E_ARG;
+  if (!(pr->dx > 0) || !(pr->dy > 0) || !(pr->rho > 0) || !(pr->mu > 0)) return LDC_E_ARG;
+  if (!(pr->alpha_uv > 0 && pr->alpha_uv <= 1) || !(pr->alpha_p > 0 && pr->alpha_p <= 1)) return LDC_E_ARG;
+  if (!(pr->lin_tol > 0) || !(pr->tol >= 0)) return LDC_E_ARG;
+  const void* req[] = {pr->ulid, pr->Qx, pr->lamx, pr->Qy, pr->lamy, pr->u, pr->v, pr->p, pr->mdot, pr->work,
+                       pr->rec, pr->ctrl};
+  for (const void* q : req) if (!q) return LDC_E_ARG;
+  h->nx = pr->nx; h->ny = pr->ny; h->scheme = pr->scheme; h->rec_cap = pr->rec_cap; h->warmup = pr->warmup;
+  h->maxit = pr->max_lin_iters;
+  h->dx = pr->dx; h->dy = pr->dy; h->rho = pr->rho; h->mu = pr->mu; h->alpha_uv = pr->alpha_uv; h->alpha_p = pr->alpha_p;
+  h->lin_tol = pr->lin_tol; h->tol = pr->tol; h->lid = pr->lid_velocity;
+  h->ulid = pr->ulid; h->Qx = pr->Qx; h->lamx = pr->lamx; h->Qy = pr->Qy; h->lamy = pr->lamy;
+  h->u = pr->u; h->v = pr->v; h->p = pr->p; h->mdot = pr->mdot; h->work = pr->work; h->rec = pr->rec;
+  h->ctrl = reinterpret_cast<long long*>(pr->ctrl);
+  return 0;
+}
 
 }  // namespace
 

@@ -4,8 +4,12 @@
 //
 // Mapping: one kernel launch per phase of the SIMPLE iteration, up to 256 work-groups of 256 threads each, every cell
 // sweep a grid-stride loop.  The launch boundary is the only barrier between work-groups: nobody waits for anybody, so
-// there are no flags, no spin limits and no co-residency.  The arithmetic is that of ldc_fv_kernel.inc, phase by phase,
-// on the same work vectors (FvVec), so after one iteration `work` holds the intermediates ldc_fv_step_debug copies out.
+// there are no flags, no spin limits and no co-residency.  The arithmetic is NOT written here: every phase calls the
+// cell functions of ldc_fv_cells.inc, which ldc_fv_kernel.inc (one trial per CU) calls too, on the same work vectors
+// (FvVec), so after one iteration `work` holds the intermediates ldc_fv_step_debug copies out.  What this unit adds is
+// the mapping: the gate, the grid-stride cell loop, the slots the partial sums go through, `par`, the BiCGSTAB scalars
+// in scratch, the block maps of a batch and the graphs.  (Two cell bodies are copies, not calls: the x sweep of
+// wide_bicg_x and wide_correct; ldc_fv_cells.inc says why.)
 // One iteration is the chain
 //   assemble | min(lin_budget, max_lin_iters) x (p, v, s, t, x) | linfinish | faces | gemm x 4 | correct | fluxvort |
 //   sums | record
@@ -49,6 +53,7 @@
 
 #include "ldc_hip.h"
 #include "ldc_fv_common.inc"
+#include "ldc_fv_cells.inc"
 
 namespace {
 
@@ -87,12 +92,6 @@ struct FvWideTable {
 
 struct FvWideQuotas {
   int32_t q[LDC_FV_WIDE_BATCH_MAX];
-};
-
-struct FvKrylov {
-  double atol, nr2, rh, rh_prev, alpha, omega, beta;
-  bool act, brk, fin;
-  int its;
 };
 
 __device__ __forceinline__ long long* wide_words(const FvWideArgs& a) { return reinterpret_cast<long long*>(a.scr); }
@@ -173,92 +172,6 @@ __device__ __forceinline__ void wide_kry_store(double* K, int g, const FvKrylov 
   }
 }
 
-// what fv_bicgstab does with the sums of its last sweep, at the top of iteration `it` (or after the last one)
-__device__ __forceinline__ void wide_kry_after_x(FvKrylov (&s)[2], const double (&s4)[4], int it) {
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    if (!s[q].act) continue;
-    if (s[q].fin) { s[q].act = false; s[q].its = it; continue; }
-    s[q].nr2 = s4[2 * q]; s[q].rh_prev = s[q].rh; s[q].rh = s4[2 * q + 1];
-    s[q].its = it;
-  }
-}
-
-// the test at the head of iteration `it`: converged or broken down -> finished with `it` iterations
-__device__ __forceinline__ void wide_kry_head(FvKrylov (&s)[2], int it) {
-  const double rhotol = 2.220446049250313e-16 * 2.220446049250313e-16;
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    s[q].beta = 0;
-    if (!s[q].act) continue;
-    if (sqrt(s[q].nr2) < s[q].atol || fabs(s[q].rh) < rhotol || (it > 0 && fabs(s[q].omega) < rhotol)) {
-      s[q].act = false; s[q].its = it; continue;
-    }
-    if (it > 0) s[q].beta = (s[q].rh / s[q].rh_prev) * (s[q].alpha / s[q].omega);
-  }
-}
-
-__device__ __forceinline__ double fv_muscl(double r) {
-  return r > 0 ? fmax(0.0, fmin(fmin(2.0, 2.0 * r), 0.5 * (1 + r))) : 0.0;
-}
-
-// TVD deferred correction of a face (ldc_fv_kernel.inc: fv_dc; DESIGN.md FV-Q1)
-__device__ __forceinline__ double fv_dc(double m, double fP, double fN) {
-  double up, down, r;
-  const double F_low = m * (m >= 0 ? fP : fN);
-  if (m >= 0) {
-    up = fP; down = fN;
-    const double fW = 2 * fP - fN;
-    r = (fN - fP) / (fP - fW + 1e-12);
-  } else {
-    up = fN; down = fP;
-    const double fW = 2 * fN - fP;
-    r = (fP - fN) / (fN - fW + 1e-12);
-  }
-  const double psi = fv_muscl(r);
-  return m * (up + 0.5 * psi * (down - up)) - F_low;
-}
-
-// central-difference gradient with the reference's rules (ldc_fv_kernel.inc: fv_grad)
-__device__ __forceinline__ void fv_grad(const double* f, int c, int i, int j, int nx, int ny, double dx, double dy,
-                                        double& gx, double& gy) {
-  gx = 0.0; gy = 0.0;
-  if (c == 0) return;
-  const double fc = f[c];
-  double sx = 0.0, sy = 0.0;
-  int nxc = 0, nyc = 0;
-  if (i > 0 && c - 1 != 0) { sx += (f[c - 1] - fc) / (-dx); ++nxc; }
-  if (i < nx - 1) { sx += (f[c + 1] - fc) / dx; ++nxc; }
-  if (j > 0 && c - nx != 0) { sy += (f[c - nx] - fc) / (-dy); ++nyc; }
-  if (j < ny - 1) { sy += (f[c + nx] - fc) / dy; ++nyc; }
-  gx = nxc > 0 ? sx / nxc : 0.0;
-  gy = nyc > 0 ? sy / nyc : 0.0;
-}
-
-// y = (relaxed A) x at cell c: diag = aP / alpha_uv
-__device__ __forceinline__ double fv_matvec(const double* w, int n, const double* x, int c, int i, int j, int nx,
-                                            int ny, double inv_a) {
-  double y = (w[FV_AP * n + c] * inv_a) * x[c];
-  if (i > 0) y += w[FV_AW * n + c] * x[c - 1];
-  if (i < nx - 1) y += w[FV_AE * n + c] * x[c + 1];
-  if (j > 0) y += w[FV_AS * n + c] * x[c - nx];
-  if (j < ny - 1) y += w[FV_AN * n + c] * x[c + nx];
-  return y;
-}
-
-// geometry, coefficients and arrays of the trial, and this thread's cells: c = first, first + stride, ...
-struct WCtx {
-  const FvDesc& d;
-  int nx, ny, n, ldx, first, stride;
-  double dx, dy, V, rho, inv_a;
-  double *w, *fx, *fy;
-  __device__ __forceinline__ WCtx(const FvWideArgs& a, int g)
-      : d(a.d), nx(a.d.nx), ny(a.d.ny), n(nx * ny), ldx(nx + 1), first(g * kWT + threadIdx.x),
-        stride(a.G * kWT), dx(a.d.dx), dy(a.d.dy), V(dx * dy), rho(a.d.rho), inv_a(1.0 / a.d.alpha_uv), w(a.d.work),
-        fx(a.d.mdot), fy(a.d.mdot + ny * ldx) {}
-  __device__ __forceinline__ double* vec(FvVec k, int q = 0) const { return w + (k + q) * n; }
-};
-
 // ---- begin: the first launch of an enqueue (one work-group): the overflow word and the record row start at 0, the
 //      quota is the number of iterations the enqueue means for this trial
 __device__ __forceinline__ void wide_begin(const FvWideArgs& a, int quota) {
@@ -272,61 +185,9 @@ __device__ __forceinline__ void wide_begin(const FvWideArgs& a, int quota) {
 // ---- 1. grad p, the five diagonals, the relaxed right-hand sides, the BiCGSTAB start; slot: |b_u|^2, |b_v|^2
 __device__ __forceinline__ void wide_assemble(const FvWideArgs& a, int g, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a, g);
-  const FvDesc& d = x.d;
-  const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
-  double* const w = x.w;
-  const double *fx = x.fx, *fy = x.fy;
-  const double Dx = d.mu * x.dy / x.dx, Dy = d.mu * x.dx / x.dy, Dbx = d.mu * x.dy / (0.5 * x.dx),
-               Dby = d.mu * x.dx / (0.5 * x.dy), scale = (1.0 - d.alpha_uv) / d.alpha_uv;
-  const bool tvd = d.scheme == 1;
+  const FvCtx x(a.d);
   double b2[2] = {0.0, 0.0};
-  for (int c = x.first; c < n; c += x.stride) {
-    const int i = c % nx, j = c / nx;
-    double gx, gy;
-    fv_grad(d.p, c, i, j, nx, ny, x.dx, x.dy, gx, gy);
-    x.vec(FV_GPX)[c] = gx; x.vec(FV_GPY)[c] = gy;
-    double aP = 0.0, aW = 0.0, aE = 0.0, aS = 0.0, aN = 0.0, bu = 0.0, bv = 0.0;
-    const double uc = d.u[c], vc = d.v[c];
-    if (i > 0) {                 // west face: owner c-1, neighbour c
-      const double m = fx[j * ldx + i];
-      aP += Dx - fmin(m, 0.0); aW = -(fmax(m, 0.0) + Dx);
-      if (tvd) { bu += fv_dc(m, d.u[c - 1], uc); bv += fv_dc(m, d.v[c - 1], vc); }
-    } else {
-      aP += Dbx + (-fx[j * ldx]);
-    }
-    if (i < nx - 1) {            // east face: owner c
-      const double m = fx[j * ldx + i + 1];
-      aP += fmax(m, 0.0) + Dx; aE = fmin(m, 0.0) - Dx;
-      if (tvd) { bu -= fv_dc(m, uc, d.u[c + 1]); bv -= fv_dc(m, vc, d.v[c + 1]); }
-    } else {
-      aP += Dbx + fx[j * ldx + nx];
-    }
-    if (j > 0) {
-      const double m = fy[j * nx + i];
-      aP += Dy - fmin(m, 0.0); aS = -(fmax(m, 0.0) + Dy);
-      if (tvd) { bu += fv_dc(m, d.u[c - nx], uc); bv += fv_dc(m, d.v[c - nx], vc); }
-    } else {
-      aP += Dby + (-fy[i]);
-    }
-    if (j < ny - 1) {
-      const double m = fy[(j + 1) * nx + i];
-      aP += fmax(m, 0.0) + Dy; aN = fmin(m, 0.0) - Dy;
-      if (tvd) { bu -= fv_dc(m, uc, d.u[c + nx]); bv -= fv_dc(m, vc, d.v[c + nx]); }
-    } else {
-      const double mo = fy[ny * nx + i];
-      aP += Dby + mo;
-      bu += (Dby + mo) * d.ulid[i];
-    }
-    w[FV_AP * n + c] = aP; w[FV_AW * n + c] = aW; w[FV_AE * n + c] = aE;
-    w[FV_AS * n + c] = aS; w[FV_AN * n + c] = aN;
-    w[FV_BU * n + c] = bu; w[FV_BV * n + c] = bv;
-    const double hu = (bu - gx * x.V) + scale * aP * uc;      // Patankar relaxation (helpers.py:6-25)
-    const double hv = (bv - gy * x.V) + scale * aP * vc;
-    x.vec(FV_XU)[c] = 0.0; x.vec(FV_XV)[c] = 0.0;
-    x.vec(FV_RU)[c] = hu; x.vec(FV_RTU)[c] = hu; x.vec(FV_RV)[c] = hv; x.vec(FV_RTV)[c] = hv;
-    b2[0] += hu * hu; b2[1] += hv * hv;
-  }
+  for (int c = g * kWT + threadIdx.x; c < x.n; c += a.G * kWT) fv_cell_assemble(x, c, b2);
   wide_slot_put(wide_slots(a, par ^ 1), g, 0, b2, lds);
 }
 
@@ -335,36 +196,30 @@ __device__ __forceinline__ void wide_assemble(const FvWideArgs& a, int g, int pa
 // p: the scalars from the sums of the launch before (it = 0: |b|^2 of assemble), the head test; p and phat
 __device__ __forceinline__ void wide_bicg_p(const FvWideArgs& a, int g, int it, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a, g);
-  const int n = x.n;
+  const FvCtx x(a.d);
   FvKrylov s[2];
   if (it == 0) {
     double b2[2];
     wide_slot_sum(wide_slots(a, par), a.G, 0, b2, lds);
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const double bn = sqrt(b2[q]);
-      s[q].nr2 = b2[q]; s[q].rh = b2[q]; s[q].rh_prev = 0; s[q].alpha = 0; s[q].omega = 0; s[q].beta = 0; s[q].its = 0;
-      s[q].atol = x.d.lin_tol * bn;
-      s[q].act = bn != 0.0; s[q].brk = false; s[q].fin = false;
-    }
+    for (int q = 0; q < 2; ++q) fv_kry_start(s[q], b2[q], x.d.lin_tol);
   } else {
     wide_kry_load(wide_kry(a, par), s);
     double s4[4];
     wide_slot_sum(wide_slots(a, par), a.G, 0, s4, lds);
-    wide_kry_after_x(s, s4, it);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) fv_kry_after_x(s[q], s4[2 * q], s4[2 * q + 1], it);
   }
-  wide_kry_head(s, it);
+#pragma unroll
+  for (int q = 0; q < 2; ++q) fv_kry_head(s[q], it);
   wide_kry_store(wide_kry(a, par ^ 1), g, s);
   if (!s[0].act && !s[1].act) return;
-  for (int c = x.first; c < n; c += x.stride) {
-    const double dg = x.w[FV_AP * n + c] * x.inv_a;
+  for (int c = g * kWT + threadIdx.x; c < x.n; c += a.G * kWT) {
+    const double dg = x.w[FV_AP * x.n + c] * x.inv_a;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       if (!s[q].act) continue;
-      double *p = x.vec(FV_PU, q), *r = x.vec(FV_RU, q);
-      const double pp = it > 0 ? (p[c] - s[q].omega * x.vec(FV_VU, q)[c]) * s[q].beta + r[c] : r[c];
-      p[c] = pp; x.vec(FV_PHU, q)[c] = pp / dg;
+      fv_cell_p(x, c, q, it, s[q], dg);
     }
   }
 }
@@ -372,20 +227,18 @@ __device__ __forceinline__ void wide_bicg_p(const FvWideArgs& a, int g, int it, 
 // v = A phat; slot: rtilde . v
 __device__ __forceinline__ void wide_bicg_v(const FvWideArgs& a, int g, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a, g);
-  const int nx = x.nx, ny = x.ny, n = x.n;
+  const FvCtx x(a.d);
   FvKrylov s[2];
   wide_kry_load(wide_kry(a, par), s);
   wide_kry_store(wide_kry(a, par ^ 1), g, s);
   if (!s[0].act && !s[1].act) return;
   double s2[2] = {0, 0};
-  for (int c = x.first; c < n; c += x.stride) {
-    const int i = c % nx, j = c / nx;
+  for (int c = g * kWT + threadIdx.x; c < x.n; c += a.G * kWT) {
+    const int i = c % x.nx, j = c / x.nx;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       if (!s[q].act) continue;
-      const double y = fv_matvec(x.w, n, x.vec(FV_PHU, q), c, i, j, nx, ny, x.inv_a);
-      x.vec(FV_VU, q)[c] = y; s2[q] += x.vec(FV_RTU, q)[c] * y;
+      fv_cell_v(x, c, i, j, q, s2[q]);
     }
   }
   wide_slot_put(wide_slots(a, par ^ 1), g, 0, s2, lds);
@@ -394,31 +247,23 @@ __device__ __forceinline__ void wide_bicg_v(const FvWideArgs& a, int g, int par,
 // alpha; s = r - alpha v (into r) and shat
 __device__ __forceinline__ void wide_bicg_s(const FvWideArgs& a, int g, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a, g);
-  const int n = x.n;
+  const FvCtx x(a.d);
   FvKrylov s[2];
   wide_kry_load(wide_kry(a, par), s);
   if (s[0].act || s[1].act) {
     double s2[2];
     wide_slot_sum(wide_slots(a, par), a.G, 0, s2, lds);
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      s[q].brk = false;
-      if (!s[q].act) continue;
-      if (s2[q] == 0.0) { s[q].brk = true; continue; }
-      s[q].alpha = s[q].rh / s2[q];
-    }
+    for (int q = 0; q < 2; ++q) fv_kry_alpha(s[q], s2[q]);
   }
   wide_kry_store(wide_kry(a, par ^ 1), g, s);
   if (!s[0].act && !s[1].act) return;
-  for (int c = x.first; c < n; c += x.stride) {
-    const double dg = x.w[FV_AP * n + c] * x.inv_a;
+  for (int c = g * kWT + threadIdx.x; c < x.n; c += a.G * kWT) {
+    const double dg = x.w[FV_AP * x.n + c] * x.inv_a;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       if (!s[q].act || s[q].brk) continue;
-      double* r = x.vec(FV_RU, q);
-      const double sv = r[c] - s[q].alpha * x.vec(FV_VU, q)[c];
-      r[c] = sv; x.vec(FV_SHU, q)[c] = sv / dg;
+      fv_cell_s(x, c, q, s[q], dg);
     }
   }
 }
@@ -426,20 +271,18 @@ __device__ __forceinline__ void wide_bicg_s(const FvWideArgs& a, int g, int par,
 // t = A shat; slot: s.s, t.s, t.t per component
 __device__ __forceinline__ void wide_bicg_t(const FvWideArgs& a, int g, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a, g);
-  const int nx = x.nx, ny = x.ny, n = x.n;
+  const FvCtx x(a.d);
   FvKrylov s[2];
   wide_kry_load(wide_kry(a, par), s);
   wide_kry_store(wide_kry(a, par ^ 1), g, s);
   if (!s[0].act && !s[1].act) return;
   double s3[6] = {0, 0, 0, 0, 0, 0};
-  for (int c = x.first; c < n; c += x.stride) {
-    const int i = c % nx, j = c / nx;
+  for (int c = g * kWT + threadIdx.x; c < x.n; c += a.G * kWT) {
+    const int i = c % x.nx, j = c / x.nx;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       if (!s[q].act || s[q].brk) continue;
-      const double t = fv_matvec(x.w, n, x.vec(FV_SHU, q), c, i, j, nx, ny, x.inv_a), sv = x.vec(FV_RU, q)[c];
-      x.vec(FV_TU, q)[c] = t; s3[3 * q] += sv * sv; s3[3 * q + 1] += t * sv; s3[3 * q + 2] += t * t;
+      fv_cell_t(x, c, i, j, q, s3 + 3 * q);
     }
   }
   wide_slot_put(wide_slots(a, par ^ 1), g, 0, s3, lds);
@@ -448,29 +291,22 @@ __device__ __forceinline__ void wide_bicg_t(const FvWideArgs& a, int g, int par,
 // omega (or the early finish on |s|); x and r; slot: r.r, rtilde.r per component
 __device__ __forceinline__ void wide_bicg_x(const FvWideArgs& a, int g, int it, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a, g);
-  const int n = x.n;
+  const FvCtx x(a.d);
   FvKrylov s[2];
   wide_kry_load(wide_kry(a, par), s);
   if (s[0].act || s[1].act) {
     double s3[6];
     wide_slot_sum(wide_slots(a, par), a.G, 0, s3, lds);
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      s[q].fin = false;                      // fin: converged on |s|: x += alpha phat and stop
-      if (!s[q].act) continue;
-      if (s[q].brk) { s[q].act = false; s[q].its = it + 1; continue; }
-      if (sqrt(s3[3 * q]) < s[q].atol) { s[q].fin = true; continue; }
-      s[q].omega = s3[3 * q + 1] / s3[3 * q + 2];
-    }
+    for (int q = 0; q < 2; ++q) fv_kry_omega(s[q], s3[3 * q], s3[3 * q + 1], s3[3 * q + 2], it);
   }
   wide_kry_store(wide_kry(a, par ^ 1), g, s);
   if (!s[0].act && !s[1].act) return;
   double s4[4] = {0, 0, 0, 0};
-  for (int c = x.first; c < n; c += x.stride) {
+  for (int c = g * kWT + threadIdx.x; c < x.n; c += a.G * kWT) {
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      if (!s[q].act) continue;
+    for (int q = 0; q < 2; ++q) {               // (a copy of the x sweep of fv_bicgstab, ldc_fv_kernel.inc: a change to
+      if (!s[q].act) continue;                  // one goes into the other; ldc_fv_cells.inc says why)
       double *xs = x.vec(FV_XU, q), *ph = x.vec(FV_PHU, q);
       if (s[q].fin) xs[c] += s[q].alpha * ph[c];
       else {
@@ -493,11 +329,13 @@ __device__ __forceinline__ void wide_linfinish(const FvWideArgs& a, int nb, int 
   wide_kry_load(wide_kry(a, par), s);
   double s4[4];
   wide_slot_sum(wide_slots(a, par), a.G, 0, s4, lds);
-  wide_kry_after_x(s, s4, nb);
+#pragma unroll
+  for (int q = 0; q < 2; ++q) fv_kry_after_x(s[q], s4[2 * q], s4[2 * q + 1], nb);
   long long giveups = 0, lin_iters = 0;
   bool overflow = false;
   if (nb < a.d.maxit) {
-    wide_kry_head(s, nb);                   // (what iteration nb would find first)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) fv_kry_head(s[q], nb);        // (what iteration nb would find first)
     overflow = s[0].act || s[1].act;
   } else {
     giveups = (s[0].act ? 1 : 0) + (s[1].act ? 1 : 0);
@@ -514,40 +352,11 @@ __device__ __forceinline__ void wide_linfinish(const FvWideArgs& a, int nb, int 
 //         is the cell-0 entry of the pinned solve (the first GEMM puts it in as it reads C)
 __device__ __forceinline__ void wide_faces(const FvWideArgs& a, int g, int par, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a, g);
-  const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
-  double* const w = x.w;
-  double *fx = x.fx, *fy = x.fy;
-  const double V = x.V;
+  const FvCtx x(a.d);
   double csum[1] = {0.0};
-  for (int c = x.first; c < n; c += x.stride) {
-    const int i = c % nx, j = c / nx;
-    const double DP = V / (w[FV_AP * n + c] + 1e-14);
-    double flux[4];                      // W, E, S, N in +x / +y
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      const bool xdir = f < 2;
-      const int o = f == 0 ? c - 1 : f == 1 ? c + 1 : f == 2 ? c - nx : c + nx;
-      const bool wall = f == 0 ? i == 0 : f == 1 ? i == nx - 1 : f == 2 ? j == 0 : j == ny - 1;
-      if (wall) { flux[f] = 0.0; continue; }     // boundary velocity has no normal component
-      const int P = (f == 0 || f == 2) ? o : c, N = (f == 0 || f == 2) ? c : o;
-      const double g = 0.5;
-      const double* st = xdir ? x.vec(FV_XU) : x.vec(FV_XV);
-      const double* gp = xdir ? x.vec(FV_GPX) : x.vec(FV_GPY);
-      const double DPc = P == c ? DP : V / (w[FV_AP * n + P] + 1e-14);
-      const double DNc = N == c ? DP : V / (w[FV_AP * n + N] + 1e-14);
-      const double Uf = (1.0 - g) * st[P] + g * st[N];
-      const double gbar = g * gp[N] + (1.0 - g) * gp[P];          // interpolate_to_face(grad_p)
-      const double gin = (1.0 - g) * gp[P] + g * gp[N];           // rhie_chow.py's inline interpolation (FV-Q2)
-      const double Df = g * DNc + (1.0 - g) * DPc;
-      flux[f] = x.rho * ((Uf - Df * (gbar - gin)) * (xdir ? x.dy : x.dx));
-    }
-    if (i == 0) fx[j * ldx] = flux[0];
-    fx[j * ldx + i + 1] = flux[1];
-    if (j == 0) fy[i] = flux[2];
-    fy[(j + 1) * nx + i] = flux[3];
-    const double rhs = c == 0 ? 0.0 : -((flux[1] - flux[0]) + (flux[3] - flux[2]));
-    x.vec(FV_C)[c] = rhs;
+  for (int c = g * kWT + threadIdx.x; c < x.n; c += a.G * kWT) {
+    double rhs;
+    fv_cell_faces(x, c, rhs);
     csum[0] += rhs;
   }
   wide_slot_put(wide_slots(a, par ^ 1), g, 0, csum, lds);
@@ -585,41 +394,23 @@ __device__ __forceinline__ void wide_gemm(const FvWideArgs& a, int gb, const FvW
     b00 = -csum[0];
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int M = g.M, N = g.N, K = g.K;
-  const int tn = (N + 15) >> 4, tiles = ((M + 15) >> 4) * tn;
+  const int tn = (g.N + 15) >> 4, tiles = ((g.M + 15) >> 4) * tn;
   const int t = gb * kWW + w;
   if (t >= tiles) return;
-  const int r0 = (t / tn) * 16, c0 = (t % tn) * 16;
-  const int ar = r0 + (lane & 15), bc = c0 + (lane & 15), kq = lane >> 4;
-  v4d acc = {0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    const int k = k0 + kq;
-    const double av = (ar < M && k < K) ? g.A[ar * g.sar + k * g.sak] : 0.0;
-    double bv = (bc < N && k < K) ? g.B[k * g.sbk + bc * g.sbc] : 0.0;
-    if (FIRST && k == 0 && bc == 0) bv = b00;
-    acc = MFMA_F64(av, bv, acc);
-  }
-  const double ax = a.d.dy / a.d.dx, ay = a.d.dx / a.d.dy;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int row = r0 + (lane >> 4) + 4 * q, col = c0 + (lane & 15);
-    if (row < M && col < N) {
-      double val = acc[q];
-      if (SCALE) val = (row == 0 && col == 0) ? 0.0 : val * (1.0 / (ax * a.d.lamx[col] + ay * a.d.lamy[row]));
-      g.C[row * N + col] = val;
-    }
-  }
+  fv_gemm_tile<SCALE, FIRST>(g.A, g.sar, g.sak, g.B, g.sbk, g.sbc, g.C, g.M, g.N, g.K, (t / tn) * 16, (t % tn) * 16, lane,
+                             a.d.lamx, a.d.lamy, a.d.dy / a.d.dx, a.d.dx / a.d.dy, b00);
 }
 
-// ---- 5. u' = -D grad p', u = u* + u', p += alpha_p p'; record sums 0 .. 6 of this work-group
+// ---- 5. u' = -D grad p', u = u* + u', p += alpha_p p'; record sums 0 .. 6 of this work-group.  The cell body is a copy
+//         of fv_correct's in ldc_fv_kernel.inc (ldc_fv_cells.inc, 5.): a change to one goes into the other
 __device__ __forceinline__ void wide_correct(const FvWideArgs& a, int g, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a, g);
+  const FvCtx x(a.d);
   const FvDesc& d = x.d;
   const int nx = x.nx, ny = x.ny, n = x.n;
   const double y0 = x.vec(FV_Y)[0];
   double part[7] = {0, 0, 0, 0, 0, 0, 0};
-  for (int c = x.first; c < n; c += x.stride) {
+  for (int c = g * kWT + threadIdx.x; c < n; c += a.G * kWT) {
     const int i = c % nx, j = c / nx;
     double gx, gy;
     fv_grad(x.vec(FV_Y), c, i, j, nx, ny, x.dx, x.dy, gx, gy);
@@ -639,48 +430,18 @@ __device__ __forceinline__ void wide_correct(const FvWideArgs& a, int g, double*
 // ---- 6. mdot += rho interp(u', v') . S (walls: rho u'_P |S|, FV-Q4); vorticity with ghost cells; record sum 8
 __device__ __forceinline__ void wide_fluxvort(const FvWideArgs& a, int g, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a, g);
-  const FvDesc& d = x.d;
-  const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
-  double *fx = x.fx, *fy = x.fy;
-  const double dx = x.dx, dy = x.dy, rho = x.rho;
+  const FvCtx x(a.d);
   double part[1] = {0.0};
-  for (int c = x.first; c < n; c += x.stride) {
-    const int i = c % nx, j = c / nx;
-    const double *up = x.vec(FV_UP), *vp = x.vec(FV_VP);
-    const double ue = i < nx - 1 ? 0.5 * up[c + 1] + (1.0 - 0.5) * up[c] : up[c];
-    const double vn = j < ny - 1 ? 0.5 * vp[c + nx] + (1.0 - 0.5) * vp[c] : vp[c];
-    if (i == 0) fx[j * ldx] += rho * (up[c] * dy);
-    fx[j * ldx + i + 1] += rho * (ue * dy);
-    if (j == 0) fy[i] += rho * (vp[c] * dx);
-    fy[(j + 1) * nx + i] += rho * (vn * dx);
-    const double vE = i < nx - 1 ? d.v[c + 1] : -d.v[c], vW = i > 0 ? d.v[c - 1] : -d.v[c];
-    const double uN = j < ny - 1 ? d.u[c + nx] : 2 * d.lid - d.u[c], uS = j > 0 ? d.u[c - nx] : -d.u[c];
-    const double wc = (vE - vW) / (2 * dx) - (uN - uS) / (2 * dy);
-    x.vec(FV_OMEGA)[c] = wc;
-    part[0] += wc * wc;
-  }
+  for (int c = g * kWT + threadIdx.x; c < x.n; c += a.G * kWT) fv_cell_flux_vorticity(x, c, part[0]);
   wide_slot_put(wide_rec_slots(a), g, 8, part, lds);
 }
 
 // ---- 7a. |div mdot|^2 and |grad omega|^2: record sums 7 and 9
 __device__ __forceinline__ void wide_sums(const FvWideArgs& a, int g, double* lds) {
   if (wide_gate(a)) return;
-  const WCtx x(a, g);
-  const int nx = x.nx, ny = x.ny, n = x.n, ldx = x.ldx;
-  const double *fx = x.fx, *fy = x.fy;
+  const FvCtx x(a.d);
   double p7[1] = {0.0}, p9[1] = {0.0};
-  for (int c = x.first; c < n; c += x.stride) {
-    const int i = c % nx, j = c / nx;
-    const double* om = x.vec(FV_OMEGA);
-    const double dv = (fx[j * ldx + i + 1] - fx[j * ldx + i]) + (fy[(j + 1) * nx + i] - fy[j * nx + i]);
-    p7[0] += dv * dv;
-    const double wc = om[c];
-    const double wE = i < nx - 1 ? om[c + 1] : -wc, wW = i > 0 ? om[c - 1] : -wc;
-    const double wN = j < ny - 1 ? om[c + nx] : -wc, wS = j > 0 ? om[c - nx] : -wc;
-    const double gx = (wE - wW) / (2 * x.dx), gy = (wN - wS) / (2 * x.dy);
-    p9[0] += gx * gx + gy * gy;
-  }
+  for (int c = g * kWT + threadIdx.x; c < x.n; c += a.G * kWT) fv_cell_div_palinstrophy(x, c, p7[0], p9[0]);
   wide_slot_put(wide_rec_slots(a), g, 7, p7, lds);
   wide_slot_put(wide_rec_slots(a), g, 9, p9, lds);
 }
@@ -692,16 +453,11 @@ __device__ __forceinline__ void wide_record(const FvWideArgs& a, double* lds) {
   double part[kWS];
   wide_slot_sum(wide_rec_slots(a), a.G, 0, part, lds);
   const double V = d.dx * d.dy;
-  const double chu = sqrt(part[0]) / (sqrt(part[1]) + 1e-12), chv = sqrt(part[2]) / (sqrt(part[3]) + 1e-12);
-  const double rel = chu > chv ? chu : chv;
+  const double rel = fv_rec_rel(part);
   if (threadIdx.x == 0) {
     long long* w = wide_words(a);
     const long long k = w[WW_ROW], iter = d.ctrl[1];
-    if (k >= 0 && k < d.rec_cap) {
-      double* row = d.rec + k * LDC_FV_REC_LEN;
-      row[0] = rel; row[1] = sqrt(part[4]); row[2] = sqrt(part[5]); row[3] = sqrt(part[7]);
-      row[4] = 0.5 * (part[6] * V); row[5] = 0.5 * (part[8] * V); row[6] = 0.5 * (part[9] * V); row[7] = 0.0;
-    }
+    if (k >= 0 && k < d.rec_cap) fv_rec_row(d.rec + k * LDC_FV_REC_LEN, rel, part, V);
     w[WW_ROW] = k + 1;
     if (rel != rel) d.ctrl[2] = 1;
     else if (iter >= d.warmup && rel < d.tol) d.ctrl[0] = 1;
@@ -953,28 +709,16 @@ extern "C" {
 int ldc_fv_wide_create(const struct ldc_fv_problem* pr, double* scratch, int64_t scratch_len, ldc_fv_wide** out) {
   if (!pr || !out) return LDC_E_ARG;
   *out = nullptr;
-  if (pr->nx < LDC_FV_MIN_N || pr->nx > LDC_FV_WIDE_MAX_N || pr->ny < LDC_FV_MIN_N || pr->ny > LDC_FV_WIDE_MAX_N) return LDC_E_ARG;
-  if (pr->scheme != 0 && pr->scheme != 1) return LDC_E_ARG;
-  if (pr->rec_cap < 1 || pr->warmup < 0 || pr->max_lin_iters < 1) return LDC_E_ARG;
-  if (!(pr->dx > 0) || !(pr->dy > 0) || !(pr->rho > 0) || !(pr->mu > 0)) return LDC_E_ARG;
-  if (!(pr->alpha_uv > 0 && pr->alpha_uv <= 1) || !(pr->alpha_p > 0 && pr->alpha_p <= 1)) return LDC_E_ARG;
-  if (!(pr->lin_tol > 0) || !(pr->tol >= 0)) return LDC_E_ARG;
-  const void* req[] = {pr->ulid, pr->Qx, pr->lamx, pr->Qy, pr->lamy, pr->u, pr->v, pr->p, pr->mdot, pr->work,
-                       pr->rec, pr->ctrl, scratch};
-  for (const void* q : req) if (!q) return LDC_E_ARG;
+  FvDesc h;
+  const int rc = fv_desc_of(pr, LDC_FV_WIDE_MAX_N, &h);
+  if (rc != 0) return rc;
+  if (!scratch) return LDC_E_ARG;
   if (scratch_len < LDC_FV_WIDE_SCRATCH_LEN(pr->nx, pr->ny)) return LDC_E_ARG;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
   ldc_fv_wide* s = new (std::nothrow) ldc_fv_wide;
   if (!s) return LDC_E_STATE;
-  FvDesc& h = s->a.d;
-  h.nx = pr->nx; h.ny = pr->ny; h.scheme = pr->scheme; h.rec_cap = pr->rec_cap; h.warmup = pr->warmup;
-  h.maxit = pr->max_lin_iters;
-  h.dx = pr->dx; h.dy = pr->dy; h.rho = pr->rho; h.mu = pr->mu; h.alpha_uv = pr->alpha_uv; h.alpha_p = pr->alpha_p;
-  h.lin_tol = pr->lin_tol; h.tol = pr->tol; h.lid = pr->lid_velocity;
-  h.ulid = pr->ulid; h.Qx = pr->Qx; h.lamx = pr->lamx; h.Qy = pr->Qy; h.lamy = pr->lamy;
-  h.u = pr->u; h.v = pr->v; h.p = pr->p; h.mdot = pr->mdot; h.work = pr->work; h.rec = pr->rec;
-  h.ctrl = reinterpret_cast<long long*>(pr->ctrl);
+  s->a.d = h;
   s->a.scr = scratch;
   s->a.G = (int)LDC_FV_WIDE_GROUPS(pr->nx, pr->ny);
   s->device = dev;

@@ -3053,4 +3053,5 @@ int ldc_stream_destroy(void* stream) {
 
 }  // extern "C"
 
+#include "ldc_fv_cells.inc"       // the finite-volume cell arithmetic, shared with ldc_fv_wide.hip
 #include "ldc_fv_kernel.inc"      // the finite-volume SIMPLE solver (include/ldc_fv.h)

@@ -76,6 +76,39 @@ def test_one_iteration_from_the_work_vectors_matches_reference_intermediates(fv,
     s.close()
 
 
+@pytest.mark.parametrize("tag", ["N16", "12x20", "13x17 TVD"])
+def test_assembly_leaves_the_same_bits_under_both_mappings(fv, tag):
+    """The assembly of a cell is one function (csrc/ldc_fv_cells.inc) for the one-CU and the chip mapping, and its
+    results depend on no sum over cells: after one iteration from the same state the nine work vectors grad p (2), the
+    five diagonals and the deferred-correction sources b_u, b_v are equal bit for bit.  States: the two of g14_fv_step
+    (Upwind) and the seeded 13 x 17 state of g15_fv_step under TVD (both signs of the face fluxes)."""
+    if tag.endswith("TVD"):
+        tag = tag.split()[0]
+        g = np.load(GOLD / "g15_fv_step.npz")
+        m = dict(json.loads((GOLD / "g15_fv_step.json").read_text())[tag], convection_scheme="TVD")
+    else:
+        g = np.load(GOLD / "g14_fv_step.npz")
+        m = json.loads((GOLD / "g14_fv_step.json").read_text())[tag]
+    seed = [g[f"{tag}_{k}0"] for k in ("u", "v", "p", "mdot")]
+    left = {}
+    for mapping in ("cu", "chip"):
+        s = _make(fv, m, mapping=mapping, Lx=m.get("Lx", 1.0), Ly=m.get("Ly", 1.0),
+                  lid_velocity=m.get("lid_velocity", 1.0))
+        s.set_state(*seed)
+        _, _, total = s._advance(1)
+        assert total == 1
+        n = s.n_cells
+        w = s.t["work"].cpu().numpy()
+        left[mapping] = {name: w[k * n: (k + count) * n].copy()
+                         for name, (k, count) in dict(grad_p=(GPX, 2), diag=(AP, 5), b=(BU, 2)).items()}
+        s.close()
+    for name, v in left["cu"].items():
+        assert np.all(np.isfinite(v)) and np.any(v != 0.0), name
+        diff = float(np.max(np.abs(left["chip"][name] - v)))
+        print(f"{tag} {m['convection_scheme']} {name}: max |chip - cu| = {diff:.2e}")
+        assert np.array_equal(left["chip"][name], v), name
+
+
 def test_upwind_trajectories_match_reference(fv):
     g = np.load(GOLD / "g14_fv_traj.npz")
     for tag, m in json.loads((GOLD / "g14_fv_traj.json").read_text()).items():
