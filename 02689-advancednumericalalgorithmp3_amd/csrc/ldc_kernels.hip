@@ -1596,7 +1596,10 @@ __global__ __launch_bounds__(kMfmaBounds) void gemm_nt_kernel(const GemmArgs a) 
 // ---------------------------------------------------------------------------------------
 // vortex extrema (sg.py:621-709): first index in C order wins ties, like numpy.argmin/argmax
 // ---------------------------------------------------------------------------------------
+// A NaN node is never chosen (every comparison with it is false); a list without a candidate -- every node NaN, or no node
+// inside a corner region -- keeps kNoCandidate and comes back as index -1, value NaN, and nothing is loaded for it.
 struct Best { double v; int idx; };
+constexpr int kNoCandidate = 0x7fffffff;         // above every node index q < Mx * My
 __device__ __forceinline__ void take_min(Best& b, double v, int idx) {
   if (v < b.v || (v == b.v && idx < b.idx)) { b.v = v; b.idx = idx; }
 }
@@ -1611,16 +1614,16 @@ __global__ __launch_bounds__(1024) void extrema_kernel(const double* Psi, const 
   __shared__ int si[5][1024];
   const int t = threadIdx.x;
   const double inf = __builtin_huge_val();
-  Best b[5] = {{inf, 0x7fffffff}, {-inf, 0x7fffffff}, {-inf, 0x7fffffff}, {-inf, 0x7fffffff}, {-inf, 0x7fffffff}};
+  Best b[5] = {{inf, kNoCandidate}, {-inf, kNoCandidate}, {-inf, kNoCandidate}, {-inf, kNoCandidate}, {-inf, kNoCandidate}};
   for (int q = t; q < M * My; q += 1024) {       // (M x My nodes: x index i < M, y index j < My)
     const int i = q / My, j = q % My;
     const int idx = i * LD + j;
     const double p = Psi[idx], w = W[idx], xi = x[i], yj = y[j];
     take_min(b[0], p, q);
     take_max(b[1], fabs(w), q);
-    take_max(b[2], (xi > 0.5 && yj < 0.5) ? p : -inf, q);
-    take_max(b[3], (xi < 0.5 && yj < 0.5) ? p : -inf, q);
-    take_max(b[4], (xi < 0.5 && yj > 0.5) ? p : -inf, q);
+    if (xi > 0.5 && yj < 0.5) take_max(b[2], p, q);       // (a node outside a region is no candidate of it)
+    if (xi < 0.5 && yj < 0.5) take_max(b[3], p, q);
+    if (xi < 0.5 && yj > 0.5) take_max(b[4], p, q);
   }
   for (int k = 0; k < 5; ++k) { sv[k][t] = b[k].v; si[k][t] = b[k].idx; }
   __syncthreads();
@@ -1636,9 +1639,14 @@ __global__ __launch_bounds__(1024) void extrema_kernel(const double* Psi, const 
   }
   if (t < 5) {
     const int q = si[t][0];
-    const int i = q / My, j = q % My;
-    out_idx[t] = i * LD + j;
-    out_val[t] = (t == 1) ? W[i * LD + j] : sv[t][0];
+    if (q == kNoCandidate) {                     // no candidate: every node NaN, or none inside the region
+      out_idx[t] = -1;
+      out_val[t] = __builtin_nan("");
+    } else {
+      const int i = q / My, j = q % My;
+      out_idx[t] = i * LD + j;
+      out_val[t] = (t == 1) ? W[i * LD + j] : sv[t][0];
+    }
   }
 }
 

@@ -507,6 +507,8 @@ class SGSolver(LidDrivenCavitySolver):
         val = self.d["ext_val"].cpu().numpy()
         idx = self.d["ext_idx"].cpu().numpy()
         W = self.d["W"].cpu().numpy()
+        if idx[0] < 0 or idx[1] < 0:             # the kernel found no candidate: every node of psi or of omega is NaN
+            raise ValueError("no finite node")
         at = lambda k: divmod(int(idx[k]), self.LD)          # noqa: E731
         x, y = self.x_nodes, self.y_nodes
         i, j = at(0)
@@ -515,8 +517,8 @@ class SGSolver(LidDrivenCavitySolver):
         i, j = at(1)
         out.update(omega_max=float(val[1]), omega_max_x=float(x[i]), omega_max_y=float(y[j]))
         for k, name in ((2, "BR"), (3, "BL"), (4, "TL")):
-            i, j = at(k)
-            if val[k] > 0:
+            if idx[k] >= 0 and val[k] > 0:       # (index -1: no node inside the region, or only NaN ones)
+                i, j = at(k)
                 vals = (float(val[k]), float(W[i, j]), float(x[i]), float(y[j]))
             else:
                 vals = (0.0, 0.0, 0.0, 0.0)

@@ -306,6 +306,11 @@ int ldc_poisson_fastdiag(const double *Qx, const double *Qxinv, const double *Qy
                          int Mi, int LD, void *stream);
 /* argmin psi, argmax |omega| and the three corner maxima (sg.py:621-709).               */
 /* out_val[5], out_idx[5] (flat index ix*LD+iy): 0 primary, 1 |omega| max, 2 BR, 3 BL, 4 TL */
+/* Contract: ties go to the first node in C order (ix, then iy), as numpy.argmin / argmax; */
+/* out_val[1] is the SIGNED omega at the arg-max of |omega|; the corner regions are strict   */
+/* (x > 0.5 or x < 0.5, y likewise: a node at 0.5 belongs to none); a NaN node is never      */
+/* chosen (comparisons with NaN are false).  A list with no candidate -- every node NaN, or  */
+/* no node inside the region -- returns out_idx = -1 and out_val = NaN, and loads nothing.   */
 int ldc_vortex_extrema(const double *Psi, const double *W, const double *x, const double *y,
                        int M, int LD, double *out_val, int32_t *out_idx, void *stream);
 /* the same on an Mx x My node grid (nx != ny)                                             */
