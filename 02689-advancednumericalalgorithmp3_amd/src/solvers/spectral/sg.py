@@ -131,6 +131,7 @@ class SGSolver(LidDrivenCavitySolver):
         self._eig = None
         self._smoother_mode(False)
         self._edge_fix_pending = False
+        self._edge_off = {}          # tail layout: how far the uploaded u, v are off their boundary values at index M-1
         self.reset_state()
 
     # ------------------------------------------------------------------ host-side setup
@@ -243,8 +244,18 @@ class SGSolver(LidDrivenCavitySolver):
             self.d[transposed_name].copy_(t.t())
 
     def set_state(self, u=None, v=None, p=None):
-        """Upload (flat or 2-D) host arrays; p lives on the (N-1)^2 inner grid."""
+        """Upload (flat or 2-D) host arrays; p lives on the (N-1)^2 inner grid.
+
+        The first residual is taken from the state as uploaded (residual_fields shows it), every stage imposes the boundary
+        values.  In the tail layout no tile rewrites index M-1 and the kernels take that row / column of phi^n for boundary
+        values that never change (include/ldc_hip.h, ldc_problem::U): iterating from u, v that hold anything else there is
+        refused (ValueError, when the iterations are asked for: _prime)."""
         Mx, My = self.Mx, self.My
+        if self.tail:
+            for name, a, lid in (("u", u, self.u_lid), ("v", v, 0.0)):
+                if a is not None:
+                    a = np.asarray(a, float).reshape(Mx, My)
+                    self._edge_off[name] = float(max(np.max(np.abs(a[-1, :-1])), np.max(np.abs(a[:, -1] - lid))))
         if u is not None:
             self._upload_full("U", np.asarray(u, float).reshape(Mx, My), "UT")
         if v is not None:
@@ -260,7 +271,8 @@ class SGSolver(LidDrivenCavitySolver):
         if self.tail:
             # Index M-1 is never rewritten by the tiles.  The RK stage buffers must carry the
             # boundary VALUES there (the reference re-imposes them after every stage); phi^n itself
-            # keeps whatever was uploaded for the first iteration and is corrected right after it.
+            # keeps what was uploaded for the first iteration (its stage 1 reads it) and gets the boundary
+            # values right after it (chunks.advance) -- the same values, or _prime refuses to iterate.
             self._write_boundary_edges(("UA", "UAT", "VA", "VAT"))
             self._write_boundary_edges(("UB", "UBT", "VB", "VBT"))
             self._edge_fix_pending = True
@@ -288,6 +300,7 @@ class SGSolver(LidDrivenCavitySolver):
             self.d[tname][:My, :Mx] = a.t()
         self.d["P"].zero_()
         self.d["P"][1: Mx - 1, 1: My - 1] = p_inner
+        self._edge_off = {}          # (the FSG prolongation: the east wall holds the lid speed on purpose, quirk Q2)
         self.set_state()
 
     def reset_state(self):
@@ -379,6 +392,10 @@ class SGSolver(LidDrivenCavitySolver):
 
     def _prime(self):
         if not self._primed:
+            for name, off in self._edge_off.items():
+                if not off <= 1e-12 * max(1.0, abs(self.params.lid_velocity)):
+                    raise ValueError(f"{name} is off its boundary values by {off:.3g} on the row / column of index M-1 = "
+                                     f"{self.M - 1}: in the tail layout (N = {self.M - 1}) the kernels take them from there")
             self._abi("ldc_prime", self._handle)
             self._primed = True
 

@@ -127,7 +127,14 @@ typedef struct ldc_problem {
   const double *wx, *wy;    /* quadrature weights, length LD       (sg.py:489-490)     */
   const double *ulid;       /* lid profile u_lid(x_i), length LD   (corner.py:80-112)  */
   const double *DxL, *D2xL, *DyL, *D2yL; /* column M-1 of Dx, D2x, Dy, D2y as contiguous length-LD vectors */
-  /* state phi^n and its transposed copies                                              */
+  /* state phi^n and its transposed copies.  An uploaded state need not carry the boundary values inside the tiles: the
+     first residual is taken from it as it is, every stage imposes them.  In the tail layout no tile rewrites index M-1,
+     and every kernel takes the node there for a boundary value that never changes: phi^n MUST carry the boundary values
+     on the row and the column of index M-1 (east wall 0, lid ulid, v = 0), or the record of the first iteration (relative
+     change, E, Z, P) is formed with what was uploaded there.  SGSolver.set_state refuses such host arrays.  The one
+     upload that breaks this on purpose is the FSG prolongation (the reference's quirk Q2 leaves the lid speed on the east
+     wall): its trajectory is the reference's, the relative change of its first record omits that line.  The first
+     iteration after an upload runs on the launch path (n_iters = 1), whose stage 1 reads index M-1 of phi^n itself.      */
   double *U, *UT, *V, *VT, *P;
   /* RK stage buffers (sg.py:438-442), ping-pong A/B.  Of the velocity buffers the kernels maintain only the
      packed twins (UAK ...); the row-major forms below are read at index M-1 only (boundary values, written by
