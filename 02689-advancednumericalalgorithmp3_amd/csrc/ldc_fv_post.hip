@@ -21,6 +21,10 @@
 //
 // The post blocks reach the device through fv_post_stage_kernel: the structs travel as kernel arguments and one thread
 // per trial writes them behind the descriptor.  Stream-ordered, no host synchronisation, no library-owned staging.
+//
+// ldc_fv_wide.hip holds COPIES of the bodies of fv_post_vorticity, fv_post_gemm, fv_post_extrema and of the result block
+// of fv_post_kernel (fv_wide_post_*: the same chain for a chip or shared trial, one launch per phase): a change to one
+// goes into the other.
 
 #include <hip/hip_runtime.h>
 #include <limits.h>

@@ -12,6 +12,10 @@
 // The kernel is memory-bound and tiny (a fine trial is at most 256 x 256 cells): plain loops over cells and faces, one
 // element per thread and pass, no LDS, no reduction.  The arithmetic is the one tests/fv_prolong_numpy.py states; with
 // contraction off it has no multiply-add that the compiler could fuse, so both round alike.
+//
+// ldc_fv_wide.hip holds COPIES of FvAxis, fv_prolong_node, fv_prolong_at and of the loop bodies of fv_prolong_cells and
+// fv_prolong_fluxes (fv_wide_prolong_*: the same transfer for chip or shared trials, two launches per pair): a change to
+// one goes into the other.
 
 #include <hip/hip_runtime.h>
 #include <math.h>

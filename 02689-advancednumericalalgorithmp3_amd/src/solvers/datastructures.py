@@ -93,8 +93,10 @@ class FVParameters(Parameters):
     # --- additions of the MI355X build (optional, defaults keep reference behaviour) ---
     device: str = "cuda:0"
     check_every: int = 2048        # iterations enqueued between host polls of the latch
-    # streamfunction and vortex metrics after a solve: "host" (SciPy sparse solve, one trial after another) or "device"
-    # (ldc_fv_post_enqueue, all trials of a batch in one launch); not given: LDC_FV_VORTEX_METRICS may choose
+    # streamfunction and vortex metrics after a solve: "host" (SciPy sparse solve, one trial after another), "device"
+    # (ldc_fv_post_enqueue, all trials of a batch in one launch, one work-group per trial, at most 256 cells per axis) or
+    # "chip" (ldc_fv_wide_post_enqueue, the whole chip per trial, 8 ... 1024 cells per axis, mapping "chip" or "shared"
+    # only); not given: LDC_FV_VORTEX_METRICS may choose
     vortex_metrics: str = field(default_factory=lambda: os.environ.get("LDC_FV_VORTEX_METRICS", "host"))
     # Anderson acceleration of the outer iteration (ldc_fv_anderson_enqueue): "none" or "anderson", the number of
     # difference columns kept (1 ... 16) and the iteration count from which the iterates are mixed.  Real parameters of

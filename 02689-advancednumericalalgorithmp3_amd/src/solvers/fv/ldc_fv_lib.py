@@ -60,7 +60,8 @@ EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue"
            "ldc_fv_anderson_enqueue", "ldc_fv_wide_create", "ldc_fv_wide_destroy", "ldc_fv_wide_enqueue",
            "ldc_fv_wide_launches", "ldc_fv_wide_status", "ldc_fv_wide_set_graph", "ldc_fv_wide_batch_create",
            "ldc_fv_wide_batch_destroy", "ldc_fv_wide_batch_enqueue", "ldc_fv_wide_batch_set_graph",
-           "ldc_fv_wide_batch_launches")
+           "ldc_fv_wide_batch_launches", "ldc_fv_wide_post_enqueue", "ldc_fv_wide_post_launches",
+           "ldc_fv_wide_prolong_enqueue")
 
 _bound = None
 
@@ -86,6 +87,12 @@ def wide_groups(nx: int, ny: int) -> int:
 def wide_scratch_len(nx: int, ny: int) -> int:
     """LDC_FV_WIDE_SCRATCH_LEN: control words, two copies of the BiCGSTAB scalars, three sets of slot sums."""
     return 80 + 30 * wide_groups(nx, ny)
+
+
+def wide_post_scratch_len(nx: int, ny: int) -> int:
+    """LDC_FV_WIDE_POST_SCRATCH_LEN: one slot of 12 doubles per work-group of a cell sweep (five keys, five cells, two
+    not-finite flags)."""
+    return 12 * wide_groups(nx, ny)
 
 
 def wide_gemm_groups(nx: int, ny: int) -> int:
@@ -129,6 +136,9 @@ def lib() -> C.CDLL:
         L.ldc_fv_wide_batch_enqueue.argtypes = [_dp, C.POINTER(C.c_int32), C.c_int, _dp]
         L.ldc_fv_wide_batch_set_graph.argtypes = [_dp, C.c_int]
         L.ldc_fv_wide_batch_launches.argtypes = [_dp, C.c_int]
+        L.ldc_fv_wide_post_enqueue.argtypes = [_dp, C.POINTER(Post), _dp, C.c_int64, _dp]
+        L.ldc_fv_wide_post_launches.argtypes = [_dp]
+        L.ldc_fv_wide_prolong_enqueue.argtypes = [_dp, _dp, _dp]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -187,3 +197,15 @@ def wide_batch_enqueue(batch, quotas, lin_budget: int, stream) -> None:
     """``quotas[q]`` iterations of trial q (0: the trial is left alone), all in the same launches; nothing synchronises."""
     arr = (C.c_int32 * len(quotas))(*[int(k) for k in quotas])
     check(lib().ldc_fv_wide_batch_enqueue(batch, arr, int(lin_budget), _dp(stream)), "ldc_fv_wide_batch_enqueue")
+
+
+def wide_post_enqueue(wide, post: Post, scratch_ptr: int, scratch_len: int, stream) -> None:
+    """omega, psi and the result block of ONE chip or shared trial (its ``ldc_fv_wide`` handle) by the whole chip: the
+    launches of ``ldc_fv_wide_post_launches``, all enqueued; nothing synchronises."""
+    check(lib().ldc_fv_wide_post_enqueue(wide, C.byref(post), _dp(scratch_ptr), int(scratch_len), _dp(stream)),
+          "ldc_fv_wide_post_enqueue")
+
+
+def wide_prolong_enqueue(coarse, fine, stream) -> None:
+    """fine <- the prolongation of coarse, both ``ldc_fv_wide`` handles of one device: two launches over the chip."""
+    check(lib().ldc_fv_wide_prolong_enqueue(coarse, fine, _dp(stream)), "ldc_fv_wide_prolong_enqueue")

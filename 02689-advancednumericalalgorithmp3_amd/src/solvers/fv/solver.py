@@ -7,7 +7,8 @@ record rows and the latch.  ``acceleration="anderson"`` mixes the iterates on th
 (``ldc_fv_anderson_enqueue``: one launch per iteration and a mixing launch after it, still one wait per chunk).  The host computes, once per trial, the eigenvectors of the 1-D Neumann Laplacians that the
 kernel's exact pressure-correction solve uses, and, once per solve, the vortex metrics: on the host with SciPy's sparse
 solve (``vortex_metrics="host"``, the default) or on the device (``"device"``: ``ldc_fv_post_enqueue``, one work-group
-per trial, the same quantities by the same rules).
+per trial, the same quantities by the same rules; ``"chip"``: ``ldc_fv_wide_post_enqueue``, the whole chip per trial, for
+``mapping="chip"`` and ``"shared"`` trials of up to 1024 cells per axis, the same bits as ``"device"`` where both exist).
 """
 from __future__ import annotations
 
@@ -24,7 +25,7 @@ from . import ldc_fv_lib as F
 log = logging.getLogger(__name__)
 
 SCHEMES = {"Upwind": 0, "TVD": 1}
-VORTEX_METRICS = ("host", "device")
+VORTEX_METRICS = ("host", "device", "chip")
 ACCELERATIONS = ("none", "anderson")
 MAPPINGS = ("cu", "chip", "shared")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
@@ -90,16 +91,41 @@ def mask_bounds(xs, ys):
             int(np.count_nonzero(ys < 0.5)), int(ys.size - np.count_nonzero(ys > 0.5)))
 
 
+def post_route(vortex_metrics: str, has_cu_handle: bool) -> str:
+    """The entry that post-processes a trial: ``"chip"`` (``ldc_fv_wide_post_enqueue``, a chain of launches over the
+    whole chip for this trial alone) when the trial asks for it or has no one-CU handle, else ``"cu"``
+    (``ldc_fv_post_enqueue``, one work-group, beside the other such trials of the call)."""
+    return "chip" if vortex_metrics == "chip" or not has_cu_handle else "cu"
+
+
+def prolong_route(coarse_has_cu: bool, fine_has_cu: bool, coarse_chip: bool, fine_chip: bool) -> str:
+    """The entry that prolongs a (coarse, fine) pair: ``"cu"`` (``ldc_fv_prolong_enqueue``) when both trials have a one-CU
+    handle; else ``"chip"`` (``ldc_fv_wide_prolong_enqueue``), which takes the whole-chip handles of both: a trial without
+    one is a ``ValueError``."""
+    if coarse_has_cu and fine_has_cu:
+        return "cu"
+    if coarse_chip and fine_chip:
+        return "chip"
+    raise ValueError(f"prolong: a trial above {F.MAX_N} cells per axis is prolonged through the whole-chip handles of both "
+                     f"trials, and one of them has none: give the coarse trial mapping='chip' (or 'shared')")
+
+
 def postprocess(trials):
     """omega, psi and the vortex extrema of ``trials`` (FVSolvers on one device, none in flight) on the device: one
-    launch per 256 trials, then ONE copy of all result blocks.  ``psi`` and ``omega`` stay on the device as
-    ``t["psi"]``, ``t["omega"]``; every trial keeps its row of the result blocks for ``compute_vortex_metrics``."""
+    launch per 256 trials of the one-CU route and one chain of launches per trial of the chip route (``post_route``),
+    then ONE copy of all result blocks.  ``psi`` and ``omega`` stay on the device as ``t["psi"]``, ``t["omega"]``; every
+    trial keeps its row of the result blocks for ``compute_vortex_metrics``."""
     import torch
     from solvers.spectral import ldc_lib
     if not trials:
         return
-    for s in trials:
-        s._require_cu_handle("postprocess")
+    routes = [post_route(s.params.vortex_metrics, s._has_cu_handle) for s in trials]
+    for s, route in zip(trials, routes):
+        if route == "cu":
+            s._require_cu_handle("postprocess")
+        elif s._wide is None:
+            raise ValueError(f"postprocess: a trial of {s.nx} x {s.ny} cells with mapping={s.params.mapping!r} has no "
+                             f"whole-chip handle")
     dev = trials[0].device
     index = torch.cuda.current_device() if dev.index is None else dev.index
     with torch.cuda.device(dev):
@@ -117,10 +143,20 @@ def postprocess(trials):
             posts.append(F.Post(Sx=Sx.data_ptr(), lamx=lamx.data_ptr(), Sy=Sy.data_ptr(), lamy=lamy.data_ptr(),
                                 ix_lt=ix_lt, ix_gt=ix_gt, jy_lt=jy_lt, jy_gt=jy_gt, psi=s.t["psi"].data_ptr(),
                                 omega=s.t["omega"].data_ptr(), result=results[q].data_ptr()))
+        cu = [q for q, route in enumerate(routes) if route == "cu"]
+        chip = [q for q, route in enumerate(routes) if route == "chip"]
+        for q in chip:
+            if "post_scratch" not in trials[q].t:
+                trials[q].t["post_scratch"] = torch.zeros(F.wide_post_scratch_len(trials[q].nx, trials[q].ny),
+                                                          dtype=torch.float64, device=dev)
         with ldc_lib.resident_lock(index):
-            for lo in range(0, len(trials), F.LAUNCH_MAX):
-                F.post_enqueue([s.handle for s in trials[lo: lo + F.LAUNCH_MAX]], posts[lo: lo + F.LAUNCH_MAX],
-                               torch.cuda.current_stream(dev).cuda_stream)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for lo in range(0, len(cu), F.LAUNCH_MAX):
+                part = cu[lo: lo + F.LAUNCH_MAX]
+                F.post_enqueue([trials[q].handle for q in part], [posts[q] for q in part], stream)
+            for q in chip:
+                scratch = trials[q].t["post_scratch"]
+                F.wide_post_enqueue(trials[q]._wide, posts[q], scratch.data_ptr(), scratch.numel(), stream)
             rows = results.cpu().numpy()          # (synchronises the stream)
     for s, row in zip(trials, rows):
         s._post = row.copy()
@@ -132,7 +168,11 @@ def prolong(pairs):
     centres and the boundary values, p pinned at cell 0, mdot from the new u and v).  One call of the library for all pairs, which it checks together and
     launches ``PROLONG_LAUNCH_MAX`` (128) at a time, one work-group each; the fine trials' control words, records and work vectors are left alone (a ``solve()`` zeroes the
     control words itself), and so are the coarse trials.  A fine trial must not be the coarse or the fine trial of
-    another pair of the same call: chain levels with one call per level."""
+    another pair of the same call: chain levels with one call per level.
+
+    A pair with a trial above 256 cells per axis (no one-CU handle) goes through ``ldc_fv_wide_prolong_enqueue`` instead,
+    two launches over the whole chip per pair, the same arithmetic; both its trials must then be ``mapping="chip"`` or
+    ``"shared"`` trials (``prolong_route``)."""
     import torch
     from solvers.spectral import ldc_lib
     pairs = list(pairs)
@@ -140,15 +180,28 @@ def prolong(pairs):
         return
     dev = pairs[0][1].device
     index = torch.cuda.current_device() if dev.index is None else dev.index
-    for c, f in pairs:
+    routes = [prolong_route(c._has_cu_handle, f._has_cu_handle, c.chip, f.chip) for c, f in pairs]
+    for (c, f), route in zip(pairs, routes):
         for s in (c, f):
-            s._require_cu_handle("prolong")
+            if route == "cu":
+                s._require_cu_handle("prolong")
+            elif s._wide is None:
+                raise ValueError(f"prolong: a trial of {s.nx} x {s.ny} cells has no whole-chip handle")
             if (torch.cuda.current_device() if s.device.index is None else s.device.index) != index:
                 raise ValueError("prolong: all trials must be on one device")
+    cu = [pair for pair, route in zip(pairs, routes) if route == "cu"]
+    chip = [pair for pair, route in zip(pairs, routes) if route == "chip"]
+    if chip:        # (the library checks the one-CU pairs of a call together; with others beside them the rule is kept here)
+        for q, (_, f) in enumerate(pairs):
+            if any(f is c2 or (r != q and f is f2) for r, (c2, f2) in enumerate(pairs)):
+                raise ValueError("prolong: a fine trial is the coarse or the fine trial of another pair of the call")
     with torch.cuda.device(dev):
         with ldc_lib.resident_lock(index):
-            F.prolong_enqueue([c.handle for c, _ in pairs], [f.handle for _, f in pairs],
-                              torch.cuda.current_stream(dev).cuda_stream)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if cu:
+                F.prolong_enqueue([c.handle for c, _ in cu], [f.handle for _, f in cu], stream)
+            for c, f in chip:
+                F.wide_prolong_enqueue(c._wide, f._wide, stream)
             torch.cuda.current_stream(dev).synchronize()      # (the lock goes back with the CUs free)
     for _, f in pairs:
         f._post = None
@@ -344,7 +397,8 @@ class SharedBatch:
 class FVSolver(LidDrivenCavitySolver):
     """Collocated finite-volume SIMPLE solver; ``nx`` x ``ny`` cells (8 ... 256 each with ``mapping="cu"``, one
     work-group per trial; 8 ... 1024 with ``mapping="chip"``, one launch per phase over the whole chip, and with
-    ``mapping="shared"``, the same launches shared by all trials of a batch)."""
+    ``mapping="shared"``, the same launches shared by all trials of a batch).  ``streamfunction()``, ``vorticity()``,
+    ``vortex_metrics="chip"``, ``prolong`` and ``start_from`` take a chip or shared trial of any of these sizes."""
 
     Parameters = FVParameters
     rho = 1.0
@@ -358,7 +412,7 @@ class FVSolver(LidDrivenCavitySolver):
         if p.convection_scheme == "TVD" and p.limiter != "MUSCL":
             raise ValueError(f"limiter={p.limiter!r}: the TVD scheme of the reference is MUSCL")
         if p.vortex_metrics not in VORTEX_METRICS:
-            raise ValueError(f"vortex_metrics={p.vortex_metrics!r}: 'host' or 'device'")
+            raise ValueError(f"vortex_metrics={p.vortex_metrics!r}: 'host', 'device' or 'chip'")
         if p.acceleration not in ACCELERATIONS:
             raise ValueError(f"acceleration={p.acceleration!r}: 'none' or 'anderson'")
         if not 1 <= int(p.anderson_depth) <= F.ANDERSON_MAX_DEPTH:
@@ -381,6 +435,9 @@ class FVSolver(LidDrivenCavitySolver):
             raise ValueError(f"acceleration='anderson' with mapping={p.mapping!r}: the mixing kernel follows the one-CU "
                              f"kernel's launches only")
         # the one-CU handle beside the wide one wherever it exists: postprocess, prolong and start_from use it
+        if p.vortex_metrics == "chip" and not self.chip:
+            raise ValueError(f"vortex_metrics='chip' with mapping={p.mapping!r}: the post-processing chain over the whole "
+                             f"chip takes mapping='chip' or 'shared' trials")
         self._has_cu_handle = not self.chip or max(nx, ny) <= F.MAX_N
         if self._needs_cu_handle and not self._has_cu_handle:
             raise ValueError(f"{self._needs_cu_handle} of {nx} x {ny} cells: the prolongation takes at most {F.MAX_N} "
@@ -520,6 +577,12 @@ class FVSolver(LidDrivenCavitySolver):
         import torch
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    def start_from(self, other: "FVSolver"):
+        """This trial's state from ``other``'s (any FV trial of the same device and the same domain Lx, Ly; its grid and
+        its other parameters may differ) by one prolongation (``prolong``): a coarser trial to start from, or a trial of
+        this size at another Re to continue from."""
+        prolong([(other, self)])
+
     # ---- state access (tests, tools) -------------------------------------------------------------------
     def set_state(self, u, v, p, mdot):
         """Overwrite the device state: u, v, p per cell (c = j*nx + i), mdot in the [fx | fy] face layout."""
@@ -643,7 +706,7 @@ class FVSolver(LidDrivenCavitySolver):
         return psi
 
     def compute_vortex_metrics(self) -> dict:
-        if self.params.vortex_metrics == "device":
+        if self.params.vortex_metrics in ("device", "chip"):
             return self._device_vortex_metrics()
         omega = self._vorticity()
         psi = self._streamfunction(omega)
@@ -664,7 +727,7 @@ class FVSolver(LidDrivenCavitySolver):
                 out.update({f"psi_{name}": 0.0, f"psi_{name}_x": 0.0, f"psi_{name}_y": 0.0})
         return out
 
-    # ---- the same on the device (ldc_fv_post_enqueue) ------------------------------------------------------
+    # ---- the same on the device (ldc_fv_post_enqueue, ldc_fv_wide_post_enqueue) ------------------------------
     def _device_vortex_metrics(self) -> dict:
         """The host branch's dict from the trial's result block: the block ``postprocess`` left (a batch post-processes
         its trials together), or one of a launch of its own."""

@@ -106,6 +106,22 @@
  *  - overflow and NaN are per trial: ldc_fv_wide_status of the trial's own handle.  The caller enqueues the trials that
  *    overflowed again with a larger budget and quota 0 for everyone else;
  *  - the table is never rebuilt: finished trials stay in the batch object.
+ *
+ * Post-processing and prolongation of such a trial (ldc_fv_wide_post_enqueue, ldc_fv_wide_prolong_enqueue; the same
+ * unit): what ldc_fv_post_enqueue and ldc_fv_prolong_enqueue do for a trial of up to LDC_FV_MAX_N cells per axis, by the
+ * chip mapping's rules for LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N: one launch per phase, a grid that depends on (nx, ny) alone,
+ * the launch boundary the only barrier, no work-group reading what another of the same launch writes.
+ *  - post: omega | W1 = Sy^T F | W2 = W1 Sx / Lambda | W1 = Sy W2 | psi = W1 Sx^T | extrema | result, seven launches
+ *    (ldc_fv_wide_post_launches).  The cell sweeps take LDC_FV_WIDE_GROUPS work-groups, a GEMM
+ *    LDC_FV_WIDE_GEMM_GROUPS(nx - 2, ny - 2); every work-group leaves its five (key, cell) candidates and its not-finite
+ *    flags in a slot of the caller's scratch (LDC_FV_WIDE_POST_SCRATCH_LEN doubles) and `result`, one work-group, merges
+ *    them by (larger key, then lower cell), which does not depend on the grouping.  The arithmetic, the operands and the
+ *    order of every sum are those of ldc_fv_post_enqueue: psi, omega and the result block are its bits.  Read: u, v, the
+ *    sizes.  Written: psi, omega, result, work vectors 24 and 25, the scratch; not ctrl, rec, the state or the scratch of
+ *    the solve;
+ *  - prolong: a launch for u, v, p at the fine cells (every thread recomputes the interpolated p at fine cell 0, so
+ *    p[0] is exactly 0.0) and one for mdot, LDC_FV_WIDE_GROUPS of the fine trial each; the arithmetic of
+ *    ldc_fv_prolong_enqueue with no multiply-add contracted, so the fine u, v, p, mdot are its bits.
  */
 #ifndef LDC_FV_H
 #define LDC_FV_H
@@ -145,6 +161,9 @@ extern "C" {
 #define LDC_FV_WIDE_BATCH_ENTRY_BYTES 256
 #define LDC_FV_WIDE_GEMM_GROUPS(nx, ny) ((((int64_t)(ny) + 15) / 16 * (((nx) + 15) / 16) + 3) / 4)
 #define LDC_FV_WIDE_BATCH_TABLE_LEN(n, sweep_groups, gemm_groups) (LDC_FV_WIDE_BATCH_ENTRY_BYTES * (int64_t)(n) + 4 * ((int64_t)(sweep_groups) + (int64_t)(gemm_groups)))
+/* the caller's scratch of ldc_fv_wide_post_enqueue, in doubles: one slot per work-group of a cell sweep (five keys, five  */
+/* cells, two not-finite flags)                                                                                           */
+#define LDC_FV_WIDE_POST_SCRATCH_LEN(nx, ny) (12 * LDC_FV_WIDE_GROUPS(nx, ny))
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
 #define LDC_FV_DBG_GRAD_P 0        /* 2n: d/dx p, then d/dy p                                    */
@@ -289,6 +308,19 @@ int ldc_fv_wide_batch_enqueue(ldc_fv_wide_batch *b, const int32_t *n_iters, int 
 int ldc_fv_wide_batch_set_graph(ldc_fv_wide_batch *b, int on);
 /* Kernel launches of ONE iteration chain at that budget (an enqueue adds one): those of a lone trial.  Needs no device. */
 int ldc_fv_wide_batch_launches(const ldc_fv_wide_batch *b, int lin_budget);
+/* omega, psi and the result block of ONE trial that is not in flight, by the whole chip: the launches of                  */
+/* ldc_fv_wide_post_launches on `stream`, nothing synchronises.  `post` as for ldc_fv_post_enqueue; `scratch` is a device    */
+/* buffer of scratch_len >= LDC_FV_WIDE_POST_SCRATCH_LEN(nx, ny) doubles owned by the caller.  Validation comes first and  */
+/* needs no device: LDC_E_STATE for a null handle; LDC_E_ARG for a null post, a null pointer in it, a negative bound, a     */
+/* null or short scratch; then LDC_E_NODEVICE, or LDC_E_STATE when the current device is not the handle's.                   */
+int ldc_fv_wide_post_enqueue(ldc_fv_wide *h, const struct ldc_fv_post *post, double *scratch, int64_t scratch_len, void *stream);
+/* Kernel launches of that chain (7).  Needs no device; LDC_E_ARG for a null handle. */
+int ldc_fv_wide_post_launches(const ldc_fv_wide *h);
+/* fine <- the prolongation of coarse (any two sizes of LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N, one domain, one device, neither  */
+/* in flight): two launches on `stream`.  Written: the fine trial's u, v, p and mdot, nothing else.  Validation comes first */
+/* and needs no device: LDC_E_STATE for a null handle; LDC_E_ARG for coarse == fine and for two domains (nx dx or ny dy      */
+/* differ beyond 1e-12 relative); then LDC_E_NODEVICE, or LDC_E_STATE for a handle of another device.                        */
+int ldc_fv_wide_prolong_enqueue(ldc_fv_wide *coarse, ldc_fv_wide *fine, void *stream);
 
 #ifdef __cplusplus
 }
