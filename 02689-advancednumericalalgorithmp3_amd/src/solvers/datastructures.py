@@ -72,6 +72,9 @@ class SpectralParameters(Parameters):
                                    # launch per chunk, the trial on one XCD, N <= 79), 4 = the trial-per-CU kernel (M <= 44),
                                    # 5 = the chip-wide kernel (one launch per chunk, N = 81 ... 256), -1 = the library's
                                    # choice (include/ldc_hip.h): 3 / 5 where they apply; same results to rounding
+    # where the reported vortices sit: "none" (the collocation node of the grid extremum, as the reference) or "newton"
+    # (the stationary point of the interpolant of psi, ldc_vortex_refine).  Changes reported metrics: it goes to MLflow
+    vortex_refine: str = "none"
 
     def to_mlflow(self) -> dict:
         skip = {"device", "check_every", "graph_iters", "nan_guard", "diagnostics", "persistent"}

@@ -25,7 +25,7 @@ import time
 import numpy as np
 
 from . import chunks, ldc_lib as L
-from .sg import SGSolver
+from .sg import SGSolver, refine_vortices_together
 from ..base import WARMUP_ITERATIONS
 
 log = logging.getLogger(__name__)
@@ -160,6 +160,7 @@ class BatchedSGSolver:
         wall = time.perf_counter() - t0
         self.batch_seconds, self.batch_size = wall, len(self.solvers)
         its_all = max(1, sum(total for _, total, _ in out))
+        refine_vortices_together(self.solvers)
         for s, (done, total, hist) in zip(self.solvers, out):
             s.history = hist
             s._store_results(hist[WARMUP_ITERATIONS:], total, done == 1, wall * total / its_all)

@@ -18,7 +18,7 @@ import numpy as np
 
 from .chunks import run_to_tolerance
 from .operators.transfer_operators import prolongation_matrix
-from .sg import SGSolver
+from .sg import SGSolver, refine_vortices_together
 from ..base import EN, PN, REL, RP, RU, RV, ZN
 
 log = logging.getLogger(__name__)
@@ -155,6 +155,7 @@ def run_ladder(fines, run_level, tolerances, caps) -> float:
         alive = [q for q, (done, _, _) in zip(alive, out) if done != 2]
     wall = time.perf_counter() - t0
     its_all = max(1, sum(total))
+    refine_vortices_together(fines)       # (one call and one copy for all trials that ask for sub-grid vortex centres)
     for q, s in enumerate(fines):
         for lvl in ladders[q][:-1]:
             lvl.close()

@@ -56,6 +56,18 @@ class Problem(C.Structure):
     )
 
 
+class RefineJob(C.Structure):
+    """Mirror of ``struct ldc_refine_job`` (ldc_vortex_refine)."""
+    _fields_ = ([(n, _dp) for n in ("Psi", "W", "x", "y", "wx", "wy", "Dx", "Dy", "idx", "out")]
+                + [(n, C.c_int32) for n in ("Mx", "My", "LD", "LDD")])
+
+
+REFINE_OUT_LEN, REFINE_MAX_STEPS, REFINE_MAX_M = 32, 20, 257     # LDC_REFINE_*
+# status of one refined extremum (include/ldc_hip.h); anything but REFINED carries the grid node's values
+REFINE_STATUS = ("refined", "no grid candidate", "indefinite", "clipped", "not converged", "worse than the node or left the region",
+                 "not finite")
+
+
 class LdcError(RuntimeError):
     pass
 
@@ -107,6 +119,7 @@ def lib() -> C.CDLL:
     L.ldc_poisson_fastdiag.argtypes = [_dp] * 10 + [C.c_int, C.c_int, _dp]
     L.ldc_vortex_extrema.argtypes = [_dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]
     L.ldc_vortex_extrema_xy.argtypes = [_dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]
+    L.ldc_vortex_refine.argtypes = [C.POINTER(RefineJob), C.c_int, _dp]
     L.ldc_pack.argtypes = [_dp, _dp, C.c_int, _dp]
     L.ldc_debug_ablate.argtypes = [_dp, C.c_int]
     L.ldc_debug_stamps.argtypes = [_dp, C.c_void_p]
@@ -129,7 +142,7 @@ EXPORTS = (
     "ldc_solver_enqueue", "ldc_solver_set_graph_iters", "ldc_solver_set_persistent", "ldc_solver_status", "ldc_solver_mode", "ldc_batch_mode", "ldc_device_info", "ldc_attribute_rounds",
     "ldc_residual_debug", "ldc_gemm_nt",
     "ldc_batch_workspace_bytes", "ldc_batch_create", "ldc_batch_destroy", "ldc_batch_enqueue", "ldc_wide_trials_per_launch",
-    "ldc_poisson_fastdiag", "ldc_vortex_extrema", "ldc_vortex_extrema_xy", "ldc_mfma_selftest", "ldc_mfma_peak", "ldc_debug_ablate", "ldc_debug_stamps",
+    "ldc_poisson_fastdiag", "ldc_vortex_extrema", "ldc_vortex_extrema_xy", "ldc_vortex_refine", "ldc_mfma_selftest", "ldc_mfma_peak", "ldc_debug_ablate", "ldc_debug_stamps",
     "ldc_pack", "ldc_stream_priority_range", "ldc_stream_create", "ldc_stream_destroy", "ldc_timing_build",
 )
 

@@ -76,6 +76,51 @@ def _interior_eigenbasis(D2: np.ndarray):
     return hit
 
 
+VORTEX_REFINE = ("none", "newton")
+
+
+def barycentric_weights(kind: str, x: np.ndarray) -> np.ndarray:
+    """Barycentric weights of the nodes x of one axis, scaled to max |w| = 1 (any common scale cancels in the formula).
+    Chebyshev-Gauss-Lobatto: the closed form (-1)^j delta_j, delta = 1/2 at both ends.  Any other nodes (Legendre-Gauss-
+    Lobatto): 1 / prod_{k != j} (x_j - x_k) in long double, the differences scaled by 4 / L so that the product stays of
+    order one for every size the solver takes."""
+    m = x.size
+    if str(kind).lower() == "chebyshev":
+        w = (-1.0) ** np.arange(m)
+        w[[0, -1]] *= 0.5
+        return w
+    xl = np.asarray(x, dtype=np.longdouble)
+    gap = (xl[:, None] - xl[None, :]) * (np.longdouble(4) / abs(xl[-1] - xl[0]))
+    gap[np.arange(m), np.arange(m)] = 1
+    w = 1 / np.prod(gap, axis=1)
+    return np.asarray(w / np.max(np.abs(w)), dtype=np.float64)
+
+
+def refine_vortices_together(solvers) -> None:
+    """The sub-grid vortex centres of every solver that asks for them (vortex_refine="newton") in ONE ldc_vortex_refine call
+    and ONE copy of their result blocks, as solvers.fv.solver.postprocess does for the FV trials of a batch: the psi and
+    grid-extrema launches stay per trial, each solver keeps its block for its next compute_vortex_metrics().  The kernel's
+    work-groups share nothing, so a trial's block is bit-identical to its lone solve's."""
+    import torch
+    todo = [s for s in solvers if getattr(s.params, "vortex_refine", "none") == "newton"]
+    if not todo:
+        return
+    dev = todo[0].device
+    out = torch.zeros((len(todo), L.REFINE_OUT_LEN), dtype=torch.float64, device=dev)
+    jobs = (L.RefineJob * len(todo))()
+    for k, s in enumerate(todo):
+        s._enqueue_extrema()
+        s._fill_refine_job(jobs[k], out[k])
+    with torch.cuda.device(dev):
+        L.check(L.lib().ldc_vortex_refine(jobs, len(todo), L.stream_ptr(dev)), "ldc_vortex_refine")
+    vals = torch.stack([s.d["ext_val"] for s in todo])
+    idxs = torch.stack([s.d["ext_idx"] for s in todo])
+    todo[0]._sync()
+    blocks, vals, idxs = out.cpu().numpy(), vals.cpu().numpy(), idxs.cpu().numpy()
+    for k, s in enumerate(todo):
+        s._refined = (blocks[k], vals[k], idxs[k])
+
+
 class _ArraysView:
     """``solver.arrays.u / .v / .p`` as host copies of the device state (flat, like the
     reference's SpectralSolverFields); assigning uploads."""
@@ -108,6 +153,11 @@ class SGSolver(LidDrivenCavitySolver):
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
         p = self.params
+        if p.vortex_refine not in VORTEX_REFINE:
+            raise ValueError(f"Unknown vortex_refine: {p.vortex_refine!r}. Use one of {VORTEX_REFINE}")
+        self.vortex_refine_status = None     # per (primary, BR, BL, TL) after a refined compute_vortex_metrics()
+        self._refined = None                 # (result block, extrema values, indices) left by refine_vortices_together
+        self._refine_w = None
         kind = p.basis_type.lower()
         if kind == "chebyshev":
             self.basis_x = ChebyshevLobattoBasis(domain=(0.0, p.Lx))
@@ -515,11 +565,16 @@ class SGSolver(LidDrivenCavitySolver):
         self._sync()
         return full[:Mx, :My].cpu().numpy(), self.x_full, self.y_full
 
-    def compute_vortex_metrics(self) -> dict:
+    def _enqueue_extrema(self):
         self._compute_streamfunction()          # leaves psi in S4 and omega in W
         self._abi("ldc_vortex_extrema_xy",
                   self.d["S4"].data_ptr(), self.d["W"].data_ptr(), self.d["x"].data_ptr(), self.d["y"].data_ptr(),
                   self.Mx, self.My, self.LD, self.d["ext_val"].data_ptr(), self.d["ext_idx"].data_ptr())
+
+    def compute_vortex_metrics(self) -> dict:
+        if self.params.vortex_refine == "newton":
+            return self._refined_vortex_metrics()
+        self._enqueue_extrema()
         self._sync()
         val = self.d["ext_val"].cpu().numpy()
         idx = self.d["ext_idx"].cpu().numpy()
@@ -540,4 +595,43 @@ class SGSolver(LidDrivenCavitySolver):
             else:
                 vals = (0.0, 0.0, 0.0, 0.0)
             out[f"psi_{name}"], out[f"omega_{name}"], out[f"psi_{name}_x"], out[f"psi_{name}_y"] = vals
+        return out
+
+    # ---- sub-grid vortex centres (vortex_refine="newton"; include/ldc_hip.h, ldc_vortex_refine) -----------------------
+    def _fill_refine_job(self, job, out):
+        """One ldc_refine_job of this solver: psi in S4, omega in W, the grid extrema in ext_idx, the result in ``out``.
+        The first-derivative matrices are the solver's own device copies (row-major, pitch LD); the barycentric weights
+        are uploaded at the first use."""
+        if self._refine_w is None:
+            import torch
+            kind = self.params.basis_type
+            w = np.zeros((2, self.LD))
+            w[0, : self.Mx], w[1, : self.My] = barycentric_weights(kind, self.x_nodes), barycentric_weights(kind, self.y_nodes)
+            self._refine_w = torch.from_numpy(w).to(self.device)
+        d = self.d
+        for name, t in (("Psi", d["S4"]), ("W", d["W"]), ("x", d["x"]), ("y", d["y"]), ("wx", self._refine_w[0]),
+                        ("wy", self._refine_w[1]), ("Dx", d["Dx"]), ("Dy", d["Dy"]), ("idx", d["ext_idx"]), ("out", out)):
+            setattr(job, name, t.data_ptr())
+        job.Mx, job.My, job.LD, job.LDD = self.Mx, self.My, self.LD, self.LD
+
+    def _refined_vortex_metrics(self) -> dict:
+        """The vortex table with the primary vortex and the corner eddies at the stationary points of the interpolant of
+        psi; omega_max* stays on the grid (the maximum of |omega| lies on the lid).  An extremum whose refinement did not
+        end with status 0 keeps its grid node's values (vortex_refine_status says which)."""
+        if self._refined is None:
+            refine_vortices_together([self])
+        (block, val, idx), self._refined = self._refined, None
+        if idx[0] < 0 or idx[1] < 0:             # the kernel found no candidate: every node of psi or of omega is NaN
+            raise ValueError("no finite node")
+        self.vortex_refine_status = tuple(int(block[8 * e]) for e in range(4))
+        for e, name in enumerate(("primary", "BR", "BL", "TL")):
+            if self.vortex_refine_status[e] >= 2:
+                log.warning("vortex_refine: %s vortex kept its grid node (%s after %d steps)", name,
+                            L.REFINE_STATUS[self.vortex_refine_status[e]], int(block[8 * e + 5]))
+        i, j = divmod(int(idx[1]), self.LD)
+        out = dict(psi_min=float(block[3]), psi_min_x=float(block[1]), psi_min_y=float(block[2]), omega_center=float(block[4]),
+                   omega_max=float(val[1]), omega_max_x=float(self.x_nodes[i]), omega_max_y=float(self.y_nodes[j]))
+        for e, name in ((1, "BR"), (2, "BL"), (3, "TL")):
+            x, y, psi, om = (float(v) for v in block[8 * e + 1: 8 * e + 5])
+            out[f"psi_{name}"], out[f"omega_{name}"], out[f"psi_{name}_x"], out[f"psi_{name}_y"] = psi, om, x, y
         return out

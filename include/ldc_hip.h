@@ -324,6 +324,34 @@ int ldc_vortex_extrema(const double *Psi, const double *W, const double *x, cons
 int ldc_vortex_extrema_xy(const double *Psi, const double *W, const double *x, const double *y,
                           int Mx, int My, int LD, double *out_val, int32_t *out_idx, void *stream);
 
+/* Sub-grid vortex centres (csrc/ldc_vortex_refine.hip; no counterpart in the reference, which reports every centre at a  */
+/* collocation node): Newton's method on the gradient of the tensor-product Lagrange interpolant of Psi, started at the    */
+/* grid extrema that ldc_vortex_extrema_xy left in `idx` (entries 0, 2, 3, 4: primary minimum, BR, BL, TL maxima; idx    */
+/* holds at least 5 entries; the maximum of |omega|, entry 1, lies on the lid and stays on the grid) and kept inside the  */
+/* box of the neighbouring nodes.  `jobs` is a HOST array of n jobs, every pointer in a job a DEVICE pointer: Psi, W      */
+/* element (ix, iy) at ix*LD + iy as in ldc_vortex_extrema_xy, x / y the nodes, wx / wy barycentric weights of the nodes   */
+/* (any common scale per axis cancels), Dx / Dy the first-derivative matrices, row-major with leading dimension LDD.      */
+/* One work-group per (job, extremum); the library packs as many jobs into a launch as the kernel arguments hold and      */
+/* launches chunk after chunk; a job's result does not depend on what else is in the call, bit for bit.                   */
+/* out[8 e + 0..7] of extremum e = 0..3 (primary, BR, BL, TL): status, x, y, psi, omega, Newton steps taken, |grad psi| at  */
+/* the last iterate, 0.  status 0 refined; 1 no grid candidate (index < 0, or a corner value <= 0): x, y, psi, omega are  */
+/* zeros; 2 the Hessian is not definite the right way ABOVE ROUNDING (each diagonal entry beyond 3 max(Mx, My) 2^-53 times   */
+/* the sum of the magnitudes of its own terms, det beyond the same floors carried through its products); 3 the converged step was clipped to the box; 4 not converged after  */
+/* LDC_REFINE_MAX_STEPS; 5 psi worse than at the node, or a corner eddy left its region (strict, as the grid masks);       */
+/* 6 not finite.  On 2 ... 6 x, y, psi, omega are the grid node's, bit for bit: a refinement never reports a worse        */
+/* extremum than the node.  Converged: both components of the step taken are at most 1e-13 of the axis length.            */
+/* LDC_E_ARG before any launch: a null pointer, n < 1, Mx or My < 3 or > LDC_REFINE_MAX_M, LD < My, LDD < max(Mx, My).     */
+#define LDC_REFINE_OUT_LEN 32
+#define LDC_REFINE_MAX_STEPS 20
+#define LDC_REFINE_MAX_M 257
+typedef struct ldc_refine_job {
+  const double *Psi, *W, *x, *y, *wx, *wy, *Dx, *Dy;
+  const int32_t *idx;
+  double *out;
+  int32_t Mx, My, LD, LDD;
+} ldc_refine_job;
+int ldc_vortex_refine(const struct ldc_refine_job *jobs, int n, void *stream);
+
 /* Timing experiments.  The switches exist only in the INSTRUMENTED build of the library (csrc/ldc_kernels.hip       */
 /* compiled with -DLDC_TIMING -> lib/libldc_hip_timing.so, loaded by tools/kbench.py, kstamps.py, pstamps.py,          */
 /* ab_masks.py); in the product library the kernels carry no switch and both calls return LDC_E_STATE.                 */
