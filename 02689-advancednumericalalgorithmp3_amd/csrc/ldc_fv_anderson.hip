@@ -155,6 +155,7 @@ __device__ __forceinline__ void fv_anderson_gram(const FvAaHist& H, int n3, int 
 }
 
 // ---- 3. (A + lambda I) gamma = b by Cholesky, one thread; false: a pivot that is not > 0 or a gamma that is not finite
+//         (wide_mix_solve of ldc_fv_wide_anderson.inc is a copy: a change to one goes into the other)
 __device__ __forceinline__ bool fv_anderson_solve(int m, double (*A)[kFvAaDepth + 1], const double* b, double* gamma) {
   double tr = 0.0;
   for (int i = 0; i < m; ++i) tr += A[i][i];

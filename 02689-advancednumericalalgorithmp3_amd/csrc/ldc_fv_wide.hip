@@ -13,6 +13,8 @@
 // One iteration is the chain
 //   assemble | min(lin_budget, max_lin_iters) x (p, v, s, t, x) | linfinish | faces | gemm x 4 | correct | fluxvort |
 //   sums | record
+// and, for a trial with Anderson mixing attached (ldc_fv_wide_set_anderson; ldc_fv_wide_anderson.inc), behind it
+//   push | mix | close
 // Rules every kernel keeps:
 //  - the grid is a function of (nx, ny) alone;
 //  - a work-group writes its partial sums to its own slot; the NEXT launch lets every work-group add all slots in one
@@ -20,7 +22,8 @@
 //  - no work-group reads a word another work-group of the same launch writes: the slots and the BiCGSTAB scalars exist
 //    twice and alternate by launch (`par`), and the latch, the NaN word, the overflow word and the record row are
 //    written by launches of ONE work-group only (begin, linfinish, record);
-//  - every kernel but `begin` starts at the gate: latch, NaN word or overflow word set -> return at once.
+//  - every kernel but `begin` starts at the gate: latch, NaN word or overflow word set -> return at once (the mixing
+//    launches have a gate of their own: ctrl[1] == astate[2] -> return at once).
 // The data-dependent BiCGSTAB loop is a fixed number of launches; once both components have finished their launches
 // only carry the scalars on.  A component still active after lin_budget < max_lin_iters iterations sets the overflow
 // word in `linfinish`, BEFORE u, v, p or mdot have been touched (assemble and BiCGSTAB write work vectors only), and
@@ -77,14 +80,25 @@ struct FvWideArgs {
   int G;                                    // work-groups of a sweep
 };
 
+// The per-trial Anderson mixing block (ldc_fv_wide_set_anderson; ldc_fv_wide_anderson.inc): in the handle, by value in the
+// lone kernels' arguments, behind FvWideArgs in the table entry.  All zero: no mixing.
+struct FvWideMix {
+  double* hist;
+  long long* astate;
+  double* mscr;
+  int depth, start;
+};
+static_assert(sizeof(FvWideMix) == 32, "the mixing block");
+
 // The table of a batch in the caller's device buffer (LDC_FV_WIDE_BATCH_TABLE_LEN bytes): n entries, then the block map
 // of the cell sweeps (sum of G_q words) and that of the GEMMs (sum of LDC_FV_WIDE_GEMM_GROUPS words), one word
 // q << 16 | g per work-group, trial after trial.
 struct FvWideEntry {
   FvWideArgs a;
-  char pad[LDC_FV_WIDE_BATCH_ENTRY_BYTES - sizeof(FvWideArgs)];
+  FvWideMix m;
+  char pad[LDC_FV_WIDE_BATCH_ENTRY_BYTES - sizeof(FvWideArgs) - sizeof(FvWideMix)];
 };
-static_assert(sizeof(FvWideEntry) == LDC_FV_WIDE_BATCH_ENTRY_BYTES, "table entry");
+static_assert(sizeof(FvWideEntry) == LDC_FV_WIDE_BATCH_ENTRY_BYTES && sizeof(FvWideArgs) == 208, "table entry");
 static_assert(LDC_FV_WIDE_BATCH_MAX <= 1 << 15 && LDC_FV_WIDE_GEMM_GROUPS(LDC_FV_WIDE_MAX_N, LDC_FV_WIDE_MAX_N) <= 1 << 16,
               "a block-map word");
 
@@ -470,6 +484,9 @@ __device__ __forceinline__ void wide_record(const FvWideArgs& a, double* lds) {
   }
 }
 
+// ---- 8. Anderson mixing behind `record`, for a trial that has it attached: push | mix | close
+#include "ldc_fv_wide_anderson.inc"
+
 // ---- the kernels: every phase for a lone trial (arguments by value, g = blockIdx.x) and for a batch (the table)
 #define WIDE_LDS __shared__ double lds[kWW * kWS]
 // the trial and the work-group of this block of a batch launch, from a block map / for one work-group per trial
@@ -521,6 +538,30 @@ __global__ __launch_bounds__(kWT) void fv_wide_b_sums(FvWideTable t) { WIDE_LDS;
 __global__ __launch_bounds__(kWT) void fv_wide_record(FvWideArgs a) { WIDE_LDS; wide_record(a, lds); }
 __global__ __launch_bounds__(kWT) void fv_wide_b_record(FvWideTable t) { WIDE_LDS; WIDE_SINGLE; wide_record(a, lds); }
 
+__global__ __launch_bounds__(kWT) void fv_wide_mix_push(FvWideArgs a, FvWideMix x) {
+  __shared__ double part[kWW][kWMixSums];
+  wide_mix_push(a, x, blockIdx.x, part);
+}
+__global__ __launch_bounds__(kWT) void fv_wide_b_mix_push(FvWideTable t) {
+  __shared__ double part[kWW][kWMixSums];
+  WIDE_MAPPED(sweep);
+  wide_mix_push(a, t.entries[m_ >> 16].m, g, part);
+}
+__global__ __launch_bounds__(kWT) void fv_wide_mix_mix(FvWideArgs a, FvWideMix x) {
+  __shared__ WideMixLds s;
+  wide_mix_mix(a, x, blockIdx.x, s);
+}
+__global__ __launch_bounds__(kWT) void fv_wide_b_mix_mix(FvWideTable t) {
+  __shared__ WideMixLds s;
+  WIDE_MAPPED(sweep);
+  wide_mix_mix(a, t.entries[m_ >> 16].m, g, s);
+}
+__global__ __launch_bounds__(64) void fv_wide_mix_close(FvWideArgs a, FvWideMix x) { wide_mix_close(a, x); }
+__global__ __launch_bounds__(64) void fv_wide_b_mix_close(FvWideTable t) {
+  WIDE_SINGLE;
+  wide_mix_close(a, t.entries[blockIdx.x].m);
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 std::mutex g_wide_mutex;
@@ -562,14 +603,19 @@ struct WideGraphs {
 struct ldc_fv_wide {
   FvWideArgs a;
   int device;
-  int graph;                                 // replay ONE captured iteration per budget (ldc_fv_wide_set_graph)
+  short graph;                               // replay ONE captured iteration per budget (ldc_fv_wide_set_graph)
+  short mixing;                              // the iteration ends on the mixing chain (m.depth > 0).  Here, not in `m`:
+                                             // ldc_fv_wide_launches reads nothing behind these first 216 bytes
+  FvWideMix m;                               // ldc_fv_wide_set_anderson; all zero: no mixing
   WideGraphs gs;
 };
+static_assert(sizeof(FvWideArgs) + sizeof(int) + 2 * sizeof(short) == 216, "the head of a handle");
 
 struct ldc_fv_wide_batch {
   int n, maxit, device, graph;               // (the head, with rec_cap, is all that validation without a device reads)
   int rec_cap[LDC_FV_WIDE_BATCH_MAX];
   int sweep_groups, gemm_groups;             // work-groups of a cell sweep and of a GEMM launch
+  int mixing;                                // some trial has mixing attached: every chain ends on the mixing launches
   FvWideTable t;                             // (pointers into the caller's device buffer)
   WideGraphs gs;
 };
@@ -607,6 +653,11 @@ int wide_iteration(const ldc_fv_wide* h, int nb, hipStream_t st) {
   WIDE_LAUNCH(fv_wide_fluxvort, G, kWT, a);
   WIDE_LAUNCH(fv_wide_sums, G, kWT, a);
   WIDE_LAUNCH(fv_wide_record, 1, kWT, a);
+  if (h->mixing) {
+    WIDE_LAUNCH(fv_wide_mix_push, G, kWT, a, h->m);
+    WIDE_LAUNCH(fv_wide_mix_mix, G, kWT, a, h->m);
+    WIDE_LAUNCH(fv_wide_mix_close, 1, 64, a, h->m);
+  }
   return 0;
 }
 
@@ -633,10 +684,15 @@ int wide_iteration(const ldc_fv_wide_batch* b, int nb, hipStream_t st) {
   WIDE_LAUNCH(fv_wide_b_fluxvort, G, kWT, t);
   WIDE_LAUNCH(fv_wide_b_sums, G, kWT, t);
   WIDE_LAUNCH(fv_wide_b_record, n, kWT, t);
+  if (b->mixing) {
+    WIDE_LAUNCH(fv_wide_b_mix_push, G, kWT, t);
+    WIDE_LAUNCH(fv_wide_b_mix_mix, G, kWT, t);
+    WIDE_LAUNCH(fv_wide_b_mix_close, n, 64, t);
+  }
   return 0;
 }
 
-// Budgets above this are launched one by one: the graph of an iteration has 11 + 5 nb nodes
+// Budgets above this are launched one by one: the graph of an iteration has 11 + 5 nb nodes (and the mixing chain's)
 constexpr int kWideGraphMaxNb = 64;
 
 // The graph of ONE iteration of `h` (a lone handle or a batch) with nb BiCGSTAB iterations: a linear chain captured on
@@ -697,13 +753,16 @@ int wide_chains(Handle* h, int chains, int nb, hipStream_t st) {
   return 0;
 }
 
-// destroy: wait for the last replay, then free the graphs
+// destroy, and a new mixing block (the graphs hold the old one by value): wait for the last replay, then free the graphs.
+// A handle that has captured nothing makes no device call here.
 void wide_graphs_free(WideGraphs& gs) {
   if (gs.done) {
     (void)hipEventSynchronize(gs.done);
     (void)hipEventDestroy(gs.done);
+    gs.done = nullptr;
   }
   for (const auto& g : gs.graphs) (void)hipGraphExecDestroy(g.second);
+  gs.graphs.clear();
 }
 
 }  // namespace
@@ -727,6 +786,8 @@ int ldc_fv_wide_create(const struct ldc_fv_problem* pr, double* scratch, int64_t
   s->a.G = (int)LDC_FV_WIDE_GROUPS(pr->nx, pr->ny);
   s->device = dev;
   s->graph = LDC_FV_WIDE_GRAPH_DEFAULT;
+  s->mixing = 0;
+  s->m = FvWideMix{};
   *out = s;
   return 0;
 }
@@ -745,6 +806,28 @@ int ldc_fv_wide_set_graph(ldc_fv_wide* h, int on) {
   return 0;
 }
 
+int ldc_fv_wide_set_anderson(ldc_fv_wide* h, const struct ldc_fv_anderson* acc, double* scratch, int64_t scratch_len) {
+  if (!h) return LDC_E_STATE;
+  FvWideMix m = {};
+  if (acc) {
+    if (acc->depth < 0 || acc->depth > LDC_FV_ANDERSON_MAX_DEPTH || acc->start < 1 || !acc->astate) return LDC_E_ARG;
+    if (acc->depth > 0) {
+      const int nx = h->a.d.nx, ny = h->a.d.ny;
+      if (!acc->hist || acc->hist_len < LDC_FV_ANDERSON_HIST_LEN(nx, ny, acc->depth)) return LDC_E_ARG;
+      if (!scratch || scratch_len < LDC_FV_WIDE_ANDERSON_SCRATCH_LEN(nx, ny, acc->depth)) return LDC_E_ARG;
+      m.hist = acc->hist;
+      m.astate = reinterpret_cast<long long*>(acc->astate);
+      m.mscr = scratch;
+      m.depth = acc->depth;
+      m.start = acc->start;
+    }
+  }
+  wide_graphs_free(h->gs);
+  h->m = m;
+  h->mixing = m.depth > 0 ? 1 : 0;
+  return 0;
+}
+
 int ldc_fv_wide_enqueue(ldc_fv_wide* h, int n_iters, int lin_budget, void* stream) {
   if (!h) return LDC_E_STATE;
   if (n_iters < 1 || n_iters > h->a.d.rec_cap || lin_budget < 1) return LDC_E_ARG;
@@ -758,7 +841,7 @@ int ldc_fv_wide_enqueue(ldc_fv_wide* h, int n_iters, int lin_budget, void* strea
 
 int ldc_fv_wide_launches(const ldc_fv_wide* h, int lin_budget) {
   if (!h || lin_budget < 1) return LDC_E_ARG;
-  return 11 + 5 * (lin_budget < h->a.d.maxit ? lin_budget : h->a.d.maxit);
+  return 11 + 5 * (lin_budget < h->a.d.maxit ? lin_budget : h->a.d.maxit) + (h->mixing ? kWideMixLaunches : 0);
 }
 
 int ldc_fv_wide_status(ldc_fv_wide* h) {
@@ -794,7 +877,7 @@ int ldc_fv_wide_batch_create(ldc_fv_wide* const* hs, int n, void* table, int64_t
   ldc_fv_wide_batch* b = new (std::nothrow) ldc_fv_wide_batch;
   if (!b) return LDC_E_STATE;
   b->n = n; b->maxit = hs[0]->a.d.maxit; b->device = dev; b->graph = LDC_FV_WIDE_GRAPH_DEFAULT;
-  b->sweep_groups = (int)sweep; b->gemm_groups = (int)gemm;
+  b->sweep_groups = (int)sweep; b->gemm_groups = (int)gemm; b->mixing = 0;
   // the image of the table: entries, the block map of the sweeps, that of the GEMMs
   std::vector<char> image((size_t)LDC_FV_WIDE_BATCH_TABLE_LEN(n, sweep, gemm), 0);
   FvWideEntry* entries = reinterpret_cast<FvWideEntry*>(image.data());
@@ -802,6 +885,8 @@ int ldc_fv_wide_batch_create(ldc_fv_wide* const* hs, int n, void* table, int64_t
   uint32_t* gmap = smap + sweep;
   for (int q = 0; q < n; ++q) {
     entries[q].a = hs[q]->a;
+    entries[q].m = hs[q]->m;
+    if (hs[q]->mixing) b->mixing = 1;
     b->rec_cap[q] = hs[q]->a.d.rec_cap;
     const int gq = (int)LDC_FV_WIDE_GEMM_GROUPS(hs[q]->a.d.nx, hs[q]->a.d.ny);
     for (int g = 0; g < hs[q]->a.G; ++g) *smap++ = (uint32_t)q << 16 | (uint32_t)g;
@@ -855,7 +940,7 @@ int ldc_fv_wide_batch_enqueue(ldc_fv_wide_batch* b, const int32_t* n_iters, int 
 
 int ldc_fv_wide_batch_launches(const ldc_fv_wide_batch* b, int lin_budget) {
   if (!b || lin_budget < 1) return LDC_E_ARG;
-  return 11 + 5 * (lin_budget < b->maxit ? lin_budget : b->maxit);
+  return 11 + 5 * (lin_budget < b->maxit ? lin_budget : b->maxit) + (b->mixing ? kWideMixLaunches : 0);
 }
 
 }  // extern "C"

@@ -67,6 +67,8 @@ def make_record(cfg: dict, solver, out_dir: Path, t0: float) -> dict:
         rec["kernel_mode"] = int(solver.kernel_mode)
     if hasattr(solver, "level_iterations"):     # a sequenced finite-volume solve: the iterations of every level, coarse -> fine
         rec["level_iterations"] = [int(k) for k in solver.level_iterations]
+    if hasattr(solver, "counters"):             # a finite-volume solve: the device's counters (linear solves, Anderson fallbacks)
+        rec["counters"] = solver.counters()
     if int(cfg["Re"]) in V.GHIA_RE:
         rec["ghia"] = solver.ghia_error()
     m = solver.metrics

@@ -101,9 +101,10 @@ class FVParameters(Parameters):
     # "chip" (ldc_fv_wide_post_enqueue, the whole chip per trial, 8 ... 1024 cells per axis, mapping "chip" or "shared"
     # only); not given: LDC_FV_VORTEX_METRICS may choose
     vortex_metrics: str = field(default_factory=lambda: os.environ.get("LDC_FV_VORTEX_METRICS", "host"))
-    # Anderson acceleration of the outer iteration (ldc_fv_anderson_enqueue): "none" or "anderson", the number of
-    # difference columns kept (1 ... 16) and the iteration count from which the iterates are mixed.  Real parameters of
-    # a run: they go to MLflow
+    # Anderson acceleration of the outer iteration: "none", "anderson" (ldc_fv_anderson_enqueue, mapping "cu") or
+    # "anderson_chip" (ldc_fv_wide_set_anderson: the same mixing as three launches over the whole chip, mapping "chip"
+    # or "shared"), the number of difference columns kept (1 ... 16) and the iteration count from which the iterates
+    # are mixed.  Real parameters of a run: they go to MLflow
     acceleration: str = "none"
     anderson_depth: int = 5
     anderson_start: int = 10

@@ -20,6 +20,7 @@ ASTATE_COLUMNS, ASTATE_POSITION, ASTATE_SEEN, ASTATE_FALLBACKS = range(4)
 E_NAN = -5
 WIDE_MAX_N = 1024
 WIDE_BATCH_MAX, WIDE_BATCH_ENTRY_BYTES = 256, 256        # LDC_FV_WIDE_BATCH_MAX, LDC_FV_WIDE_BATCH_ENTRY_BYTES
+WIDE_ANDERSON_LAUNCHES = 3     # LDC_FV_WIDE_ANDERSON_LAUNCHES: push | mix | close behind every iteration
 E_BUDGET = -6                  # ldc_fv_wide_status: the last enqueue ran out of BiCGSTAB launches (LDC_FV_WIDE_E_BUDGET)
 CTRL_DONE, CTRL_ITER, CTRL_NAN, CTRL_GIVEUP, CTRL_LIN_ITERS, CTRL_SOLVES = range(6)
 # slots of a result block of ldc_fv_post_enqueue (LDC_FV_POST_*)
@@ -61,7 +62,7 @@ EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue"
            "ldc_fv_wide_launches", "ldc_fv_wide_status", "ldc_fv_wide_set_graph", "ldc_fv_wide_batch_create",
            "ldc_fv_wide_batch_destroy", "ldc_fv_wide_batch_enqueue", "ldc_fv_wide_batch_set_graph",
            "ldc_fv_wide_batch_launches", "ldc_fv_wide_post_enqueue", "ldc_fv_wide_post_launches",
-           "ldc_fv_wide_prolong_enqueue")
+           "ldc_fv_wide_prolong_enqueue", "ldc_fv_wide_set_anderson")
 
 _bound = None
 
@@ -93,6 +94,11 @@ def wide_post_scratch_len(nx: int, ny: int) -> int:
     """LDC_FV_WIDE_POST_SCRATCH_LEN: one slot of 12 doubles per work-group of a cell sweep (five keys, five cells, two
     not-finite flags)."""
     return 12 * wide_groups(nx, ny)
+
+
+def wide_anderson_scratch_len(nx: int, ny: int, depth: int) -> int:
+    """LDC_FV_WIDE_ANDERSON_SCRATCH_LEN: 8 words, then per work-group of a sweep b[depth] and the lower triangle of A."""
+    return 8 + wide_groups(nx, ny) * (depth * (depth + 3) // 2)
 
 
 def wide_gemm_groups(nx: int, ny: int) -> int:
@@ -139,6 +145,7 @@ def lib() -> C.CDLL:
         L.ldc_fv_wide_post_enqueue.argtypes = [_dp, C.POINTER(Post), _dp, C.c_int64, _dp]
         L.ldc_fv_wide_post_launches.argtypes = [_dp]
         L.ldc_fv_wide_prolong_enqueue.argtypes = [_dp, _dp, _dp]
+        L.ldc_fv_wide_set_anderson.argtypes = [_dp, C.POINTER(Anderson), _dp, C.c_int64]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -209,3 +216,10 @@ def wide_post_enqueue(wide, post: Post, scratch_ptr: int, scratch_len: int, stre
 def wide_prolong_enqueue(coarse, fine, stream) -> None:
     """fine <- the prolongation of coarse, both ``ldc_fv_wide`` handles of one device: two launches over the chip."""
     check(lib().ldc_fv_wide_prolong_enqueue(coarse, fine, _dp(stream)), "ldc_fv_wide_prolong_enqueue")
+
+
+def wide_set_anderson(wide, block, scratch_ptr: int = None, scratch_len: int = 0) -> None:
+    """Attach the mixing chain to an ``ldc_fv_wide`` handle (``block``: an ``Anderson`` of depth >= 1, with the mixing
+    scratch) or detach it (``None`` or depth 0).  A batch copies the block when it is created: attach first."""
+    check(lib().ldc_fv_wide_set_anderson(wide, C.byref(block) if block is not None else None, _dp(scratch_ptr),
+                                         int(scratch_len)), "ldc_fv_wide_set_anderson")

@@ -4,7 +4,9 @@ Contract: reference src/solvers/fv/solver.py (the iteration, :170-257), base.py:
 :359-450 (E, Z, P), :569-760 (streamfunction and vortex extrema).  Every SIMPLE iteration runs in the HIP kernel of
 include/ldc_fv.h -- one work-group per trial, ``check_every`` iterations per launch -- and the host only reads the
 record rows and the latch.  ``acceleration="anderson"`` mixes the iterates on the device after every iteration
-(``ldc_fv_anderson_enqueue``: one launch per iteration and a mixing launch after it, still one wait per chunk).  The host computes, once per trial, the eigenvectors of the 1-D Neumann Laplacians that the
+(``ldc_fv_anderson_enqueue``: one launch per iteration and a mixing launch after it, still one wait per chunk);
+``acceleration="anderson_chip"`` is the same mixing for ``mapping="chip"`` and ``"shared"`` trials, three launches over
+the whole chip behind every iteration (``ldc_fv_wide_set_anderson``).  The host computes, once per trial, the eigenvectors of the 1-D Neumann Laplacians that the
 kernel's exact pressure-correction solve uses, and, once per solve, the vortex metrics: on the host with SciPy's sparse
 solve (``vortex_metrics="host"``, the default) or on the device (``"device"``: ``ldc_fv_post_enqueue``, one work-group
 per trial, the same quantities by the same rules; ``"chip"``: ``ldc_fv_wide_post_enqueue``, the whole chip per trial, for
@@ -26,7 +28,7 @@ log = logging.getLogger(__name__)
 
 SCHEMES = {"Upwind": 0, "TVD": 1}
 VORTEX_METRICS = ("host", "device", "chip")
-ACCELERATIONS = ("none", "anderson")
+ACCELERATIONS = ("none", "anderson", "anderson_chip")
 MAPPINGS = ("cu", "chip", "shared")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
 
@@ -414,12 +416,13 @@ class FVSolver(LidDrivenCavitySolver):
         if p.vortex_metrics not in VORTEX_METRICS:
             raise ValueError(f"vortex_metrics={p.vortex_metrics!r}: 'host', 'device' or 'chip'")
         if p.acceleration not in ACCELERATIONS:
-            raise ValueError(f"acceleration={p.acceleration!r}: 'none' or 'anderson'")
+            raise ValueError(f"acceleration={p.acceleration!r}: 'none', 'anderson' or 'anderson_chip'")
         if not 1 <= int(p.anderson_depth) <= F.ANDERSON_MAX_DEPTH:
             raise ValueError(f"anderson_depth={p.anderson_depth}: 1 ... {F.ANDERSON_MAX_DEPTH} columns")
         if int(p.anderson_start) < 1:
             raise ValueError(f"anderson_start={p.anderson_start}: an iteration count, at least 1")
-        self.accelerated = p.acceleration == "anderson"
+        self.accelerated = p.acceleration == "anderson"      # the one-CU mixing path: advance() routes on it
+        self.mixed_chip = p.acceleration == "anderson_chip"  # the mixing chain of the chip mapping, attached to the handle
         if p.mapping not in MAPPINGS:
             raise ValueError(f"mapping={p.mapping!r}: 'cu', 'chip' or 'shared'")
         if int(p.linear_budget) < 1:
@@ -433,7 +436,10 @@ class FVSolver(LidDrivenCavitySolver):
                              f"with mapping={p.mapping!r}")
         if self.chip and self.accelerated:
             raise ValueError(f"acceleration='anderson' with mapping={p.mapping!r}: the mixing kernel follows the one-CU "
-                             f"kernel's launches only")
+                             f"kernel's launches only (a chip or shared trial takes acceleration='anderson_chip')")
+        if self.mixed_chip and not self.chip:
+            raise ValueError(f"acceleration='anderson_chip' with mapping={p.mapping!r}: the mixing chain over the whole "
+                             f"chip takes mapping='chip' or 'shared' trials (a one-CU trial takes acceleration='anderson')")
         # the one-CU handle beside the wide one wherever it exists: postprocess, prolong and start_from use it
         if p.vortex_metrics == "chip" and not self.chip:
             raise ValueError(f"vortex_metrics='chip' with mapping={p.mapping!r}: the post-processing chain over the whole "
@@ -476,8 +482,10 @@ class FVSolver(LidDrivenCavitySolver):
             ctrl=torch.zeros(F.CTRL_LEN, dtype=torch.int64, device=self.device),
             # the mixing kernel's words: every trial has them (a plain trial rides in an accelerated call at depth 0)
             astate=torch.zeros(F.ANDERSON_STATE_LEN, dtype=torch.int64, device=self.device))
-        if self.accelerated:
+        if self.accelerated or self.mixed_chip:
             self.t["hist"] = torch.zeros(F.anderson_hist_len(nx, ny, int(p.anderson_depth)), **f64)
+        if self.mixed_chip:
+            self.t["mix_scratch"] = torch.zeros(F.wide_anderson_scratch_len(nx, ny, int(p.anderson_depth)), **f64)
         if self.chip:
             self.t["scratch"] = torch.zeros(F.wide_scratch_len(nx, ny), **f64)
         self.linear_budget = int(p.linear_budget)        # grows when a solve overflows it (advance_with_budget)
@@ -519,6 +527,9 @@ class FVSolver(LidDrivenCavitySolver):
                 self._wide = h
                 if self.wide_graph is not None:
                     F.check(F.lib().ldc_fv_wide_set_graph(h, int(self.wide_graph)), "ldc_fv_wide_set_graph")
+                if self.mixed_chip:               # (before the batch of one below: a batch copies the block)
+                    F.wide_set_anderson(h, self._anderson_block(), self.t["mix_scratch"].data_ptr(),
+                                        self.t["mix_scratch"].numel())
                 if self.shared:
                     self._batch1 = SharedBatch([self], self.wide_graph)
         self._handle_tol = tolerance
@@ -552,9 +563,10 @@ class FVSolver(LidDrivenCavitySolver):
                              f"(at most {F.MAX_N} cells per axis)")
 
     def _anderson_block(self) -> F.Anderson:
-        """This trial's block of an ``anderson_enqueue`` call: its depth and history, depth 0 for a plain trial."""
+        """This trial's block of an ``anderson_enqueue`` call (or of ``wide_set_anderson``): its depth and history, depth
+        0 for a plain trial."""
         p = self.params
-        if not self.accelerated:
+        if not (self.accelerated or self.mixed_chip):
             return F.Anderson(depth=0, start=1, hist=None, hist_len=0, astate=self.t["astate"].data_ptr())
         return F.Anderson(depth=int(p.anderson_depth), start=int(p.anderson_start), hist=self.t["hist"].data_ptr(),
                           hist_len=self.t["hist"].numel(), astate=self.t["astate"].data_ptr())

@@ -1,5 +1,5 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
- * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip).
+ * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -107,6 +107,35 @@
  *    overflowed again with a larger budget and quota 0 for everyone else;
  *  - the table is never rebuilt: finished trials stay in the batch object.
  *
+ * Anderson acceleration of such a trial (ldc_fv_wide_set_anderson; csrc/ldc_fv_wide_anderson.inc, part of the same unit):
+ * the algorithm above, word for word -- the same map, hist, A and b over the first 3n entries with the columns in slot
+ * order, lambda, Cholesky by one thread, x_next over all L entries with p[0] written as 0.0, the same fallback and the same
+ * four astate words -- by the chip mapping's rules.  A handle with a mixing block attached ends every iteration on three
+ * more launches behind `record` (LDC_FV_WIDE_ANDERSON_LAUNCHES), part of the captured iteration like the others:
+ *  - push (LDC_FV_WIDE_GROUPS work-groups, grid-stride over the entries): f, the new columns dG and dF, g_prev and f_prev
+ *    (an iteration that is not mixed keeps g as the next x here); then the work-group's partial sums of b and of the lower
+ *    triangle of A into its own slot of the mixing scratch;
+ *  - mix (the same grid): every work-group adds the slots in one fixed order (thread t takes slot t), solves the m x m
+ *    system itself -- the same numbers by the same instructions everywhere -- and mixes its entries; work-group 0 leaves
+ *    the fell flag in the scratch;
+ *  - close (one work-group): astate.
+ *  - the gate: every one of the three returns at once when ctrl[1] == astate[2], that is when `record` has counted no
+ *    iteration since the last close: the trial latched or met a NaN earlier, the iteration overflowed (it changed nothing
+ *    and is enqueued again), the quota is done, or it is 0.  The quota word is NOT read: the last iteration of a quota is
+ *    mixed like any other, so a solve does not depend on where its enqueues end.  With ctrl[0] or ctrl[2] set by this
+ *    iteration only astate[2] moves.  push and mix write neither ctrl nor astate; close, one work-group per trial, is
+ *    the only launch that writes astate.  The record rows are in place already: nothing is moved;
+ *  - mixing scratch: LDC_FV_WIDE_ANDERSON_SCRATCH_LEN doubles owned by the caller, the library's between two enqueues of
+ *    one solve: 8 int64 words (word 0: the last mix took the fallback), then one slot per work-group of
+ *    depth (depth + 3) / 2 doubles: b[depth], then the lower triangle of A by rows.  hist takes (2 depth + 3) L doubles
+ *    (LDC_FV_ANDERSON_HIST_LEN): 0.55 GB at 1024 x 1024 with depth 5, 1.5 GB with depth 16;
+ *  - in a batch the block travels in the trial's table entry (ldc_fv_wide_batch_create copies it: attach first), the
+ *    three launches carry the work-groups of all trials, and a trial without a block returns from them before it reads
+ *    anything: it is bit-identical to its plain run.  A batch without any block runs the plain chain, launch for launch.
+ *  Sums run in a fixed order (per thread in increasing index, wave shuffles, the waves in order from LDS, the slots by
+ *  thread), so lone runs, batches, graphs and repeats agree bit for bit, whatever the budget and the enqueues' lengths.
+ *  The order differs from the one-CU mixing kernel's: the two agree to rounding.
+ *
  * Post-processing and prolongation of such a trial (ldc_fv_wide_post_enqueue, ldc_fv_wide_prolong_enqueue; the same
  * unit): what ldc_fv_post_enqueue and ldc_fv_prolong_enqueue do for a trial of up to LDC_FV_MAX_N cells per axis, by the
  * chip mapping's rules for LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N: one launch per phase, a grid that depends on (nx, ny) alone,
@@ -164,6 +193,10 @@ extern "C" {
 /* the caller's scratch of ldc_fv_wide_post_enqueue, in doubles: one slot per work-group of a cell sweep (five keys, five  */
 /* cells, two not-finite flags)                                                                                           */
 #define LDC_FV_WIDE_POST_SCRATCH_LEN(nx, ny) (12 * LDC_FV_WIDE_GROUPS(nx, ny))
+/* Anderson mixing of a chip or shared trial (ldc_fv_wide_set_anderson): the launches it adds to an iteration, and the     */
+/* caller's mixing scratch in doubles: 8 words, then per work-group of a sweep b[depth] and the lower triangle of A        */
+#define LDC_FV_WIDE_ANDERSON_LAUNCHES 3
+#define LDC_FV_WIDE_ANDERSON_SCRATCH_LEN(nx, ny, depth) (8 + LDC_FV_WIDE_GROUPS(nx, ny) * ((int64_t)(depth) * ((depth) + 3) / 2))
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
 #define LDC_FV_DBG_GRAD_P 0        /* 2n: d/dx p, then d/dy p                                    */
@@ -284,8 +317,18 @@ int ldc_fv_wide_enqueue(ldc_fv_wide *h, int n_iters, int lin_budget, void *strea
 /* on = 0: every kernel is launched on its own.  Same kernels, same order, same results.  A new handle starts with      */
 /* LDC_FV_WIDE_GRAPH_DEFAULT.  destroy waits for the last replay before it frees the graphs.                            */
 int ldc_fv_wide_set_graph(ldc_fv_wide *h, int on);
-/* Kernel launches of ONE iteration at that budget (an enqueue adds one).  Needs no device. */
+/* Kernel launches of ONE iteration at that budget (an enqueue adds one), LDC_FV_WIDE_ANDERSON_LAUNCHES of them the mixing */
+/* chain's when the handle has one.  Needs no device. */
 int ldc_fv_wide_launches(const ldc_fv_wide *h, int lin_budget);
+/* Attach Anderson mixing to the handle (acc->depth 1 .. LDC_FV_ANDERSON_MAX_DEPTH), or detach it (acc == NULL or depth 0): */
+/* every iteration of ldc_fv_wide_enqueue then ends on the mixing chain.  `acc` is the struct of ldc_fv_anderson_enqueue;   */
+/* `scratch` is a device buffer of scratch_len >= LDC_FV_WIDE_ANDERSON_SCRATCH_LEN(nx, ny, depth) doubles owned by the       */
+/* caller.  Call it between solves, with nothing of the handle in flight: zero astate exactly when ctrl is zeroed.  The      */
+/* handle's captured iterations are freed (after the last replay): they are captured again with the new block.  Validation */
+/* comes first and needs no device: LDC_E_STATE for a null handle; LDC_E_ARG for depth outside 0 .. 16, start < 1, a null    */
+/* astate, and with depth > 0 a null hist, a hist_len below LDC_FV_ANDERSON_HIST_LEN, a null or short scratch.  A batch      */
+/* copies the block at ldc_fv_wide_batch_create: attach before creating it.                                                  */
+int ldc_fv_wide_set_anderson(ldc_fv_wide *h, const struct ldc_fv_anderson *acc, double *scratch, int64_t scratch_len);
 /* 0, LDC_FV_E_NAN, or LDC_FV_WIDE_E_BUDGET when the last enqueue overflowed (wait for its stream first). */
 int ldc_fv_wide_status(ldc_fv_wide *h);
 /* n (1 .. LDC_FV_WIDE_BATCH_MAX) trials of any sizes and parameters, one device, advanced by the same launches.  `table` */
@@ -293,7 +336,8 @@ int ldc_fv_wide_status(ldc_fv_wide *h);
 /* Validation comes first and needs no device: LDC_E_ARG for a null list, n out of range or a null table; LDC_E_STATE for  */
 /* a null handle; LDC_E_ARG for a handle listed twice, trials whose max_lin_iters differ and a short table; LDC_E_STATE    */
 /* for handles of different devices.  Then the device: LDC_E_STATE when it is not the handles', and ONE synchronous copy   */
-/* of the table on the library's own stream.  The batch keeps a copy of every trial's arguments, not the handles: each      */
+/* of the table on the library's own stream.  The batch keeps a copy of every trial's arguments and of its mixing block    */
+/* (ldc_fv_wide_set_anderson: attach before create), not the handles: each                                                  */
 /* trial may still be advanced and asked for its status through its own handle (one of the two in flight at a time).        */
 int ldc_fv_wide_batch_create(ldc_fv_wide *const *hs, int n, void *table, int64_t table_len, ldc_fv_wide_batch **out);
 int ldc_fv_wide_batch_destroy(ldc_fv_wide_batch *b);
@@ -306,7 +350,8 @@ int ldc_fv_wide_batch_enqueue(ldc_fv_wide_batch *b, const int32_t *n_iters, int 
 /* As ldc_fv_wide_set_graph: one linear hipGraph of the batch's iteration per budget value up to 64, captured on the        */
 /* library's own stream and replayed on the caller's; destroy waits for the last replay.                                    */
 int ldc_fv_wide_batch_set_graph(ldc_fv_wide_batch *b, int on);
-/* Kernel launches of ONE iteration chain at that budget (an enqueue adds one): those of a lone trial.  Needs no device. */
+/* Kernel launches of ONE iteration chain at that budget (an enqueue adds one): those of a lone trial, with the mixing      */
+/* chain's when any trial of the batch has mixing attached.  Needs no device.                                               */
 int ldc_fv_wide_batch_launches(const ldc_fv_wide_batch *b, int lin_budget);
 /* omega, psi and the result block of ONE trial that is not in flight, by the whole chip: the launches of                  */
 /* ldc_fv_wide_post_launches on `stream`, nothing synchronises.  `post` as for ldc_fv_post_enqueue; `scratch` is a device    */
