@@ -18,6 +18,11 @@
 //
 // Sums run in a fixed order: per thread in increasing index, xor shuffles inside a wave, the eight waves in order from
 // LDS (as fv_post_kernel reduces).  So a trial's result does not depend on what else is in the launch.
+//
+// The arithmetic is NOT written here: the constants, the view of hist, push and mix for one entry, one entry into a row
+// block of the Gram sums and the Cholesky solve are the functions of ldc_fv_anderson_cells.inc, which the chip mapping
+// calls too (ldc_fv_wide_anderson.inc).  What this unit adds is the mapping: the launch arguments, the record-row
+// shuffle, the gate and astate, the loops of a work-group of 512 threads, the sums over its eight waves and the barriers.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -25,16 +30,11 @@
 
 #include "ldc_hip.h"
 #include "ldc_fv_common.inc"
+#include "ldc_fv_anderson_cells.inc"
 
 namespace {
 
 typedef const __attribute__((address_space(4))) char* kernarg_ptr;
-
-constexpr int kFvAaDepth = LDC_FV_ANDERSON_MAX_DEPTH;
-constexpr int kFvAaRows = 4;                             // rows of A per pass of phase 2
-constexpr int kFvAaSums = kFvAaRows * (kFvAaDepth + 1);  // per pass: 4 x (16 entries of A, 1 of b)
-constexpr double kFvAaLambda = 1e-12;
-static_assert(kFvAaDepth % kFvAaRows == 0, "row blocks");
 
 struct FvAndersonLaunch {                                  // 32 bytes per trial
   const FvDesc* d[LDC_FV_ANDERSON_LAUNCH_MAX];
@@ -74,72 +74,23 @@ __device__ __forceinline__ void fv_anderson_record(const FvDesc& d, int j, bool 
   }
 }
 
-// the trial's vectors of L = 3n + faces doubles inside hist
-struct FvAaHist {
-  long long L;
-  double *x, *gp, *fp, *dG, *dF;
-  __device__ __forceinline__ FvAaHist(double* h, long long L_, int depth)
-      : L(L_), x(h), gp(h + L_), fp(h + 2 * L_), dG(h + 3 * L_), dF(h + (3 + depth) * L_) {}
-};
-
-// entry e of [u | v | p | mdot]
-__device__ __forceinline__ double* fv_state_at(const FvDesc& d, int n, int e) {
-  return e < n ? d.u + e : (e < 2 * n ? d.v + (e - n) : (e < 3 * n ? d.p + (e - 2 * n) : d.mdot + (e - 3 * n)));
-}
-
 // ---- 1. f = g - x; the new columns into ring slot `slot` (push); g_prev = g, f_prev = f; without mixing x = g at once
 __device__ __forceinline__ void fv_anderson_push(const FvDesc& d, const FvAaHist& H, int n, bool has_f, bool push,
                                                  int slot, bool keep_g) {
   const int L = (int)H.L;
   double *dGs = H.dG + slot * H.L, *dFs = H.dF + slot * H.L;
-  for (int e = threadIdx.x; e < L; e += kFvThreads) {
-    const double g = *fv_state_at(d, n, e);
-    if (has_f) {
-      const double f = g - H.x[e];
-      if (push) {
-        dGs[e] = g - H.gp[e];
-        dFs[e] = f - H.fp[e];
-      }
-      H.gp[e] = g;
-      H.fp[e] = f;
-    }
-    if (keep_g) H.x[e] = g;
-  }
+  for (int e = threadIdx.x; e < L; e += kFvThreads) fv_anderson_push_entry(d, H, n, e, has_f, push, dGs, dFs, keep_g);
   __syncthreads();
 }
 
 // ---- 2. A[i][k] = dF_i . dF_k, b[i] = dF_i . f over the first n3 entries, rows i0 .. i0 + 3 per pass
 __device__ __forceinline__ void fv_anderson_gram(const FvAaHist& H, int n3, int m, double (*part)[kFvAaSums],
                                                  double (*A)[kFvAaDepth + 1], double* b) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int i0 = 0; i0 < m; i0 += kFvAaRows) {
     double acc[kFvAaRows][kFvAaDepth + 1];
-#pragma unroll
-    for (int r = 0; r < kFvAaRows; ++r)
-#pragma unroll
-      for (int k = 0; k <= kFvAaDepth; ++k) acc[r][k] = 0.0;
-    for (int e = threadIdx.x; e < n3; e += kFvThreads) {
-      double c[kFvAaDepth + 1];
-#pragma unroll
-      for (int k = 0; k < kFvAaDepth; ++k) c[k] = k < m ? H.dF[k * H.L + e] : 0.0;
-      c[kFvAaDepth] = H.fp[e];
-#pragma unroll
-      for (int r = 0; r < kFvAaRows; ++r) {
-        const double rv = i0 + r < m ? H.dF[(i0 + r) * H.L + e] : 0.0;
-#pragma unroll
-        for (int k = 0; k <= kFvAaDepth; ++k) acc[r][k] = fma(rv, c[k], acc[r][k]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < kFvAaRows; ++r) {
-#pragma unroll
-      for (int k = 0; k <= kFvAaDepth; ++k) {
-        double s = acc[r][k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) part[w][r * (kFvAaDepth + 1) + k] = s;
-      }
-    }
+    fv_anderson_acc_clear(acc);
+    for (int e = threadIdx.x; e < n3; e += kFvThreads) fv_anderson_acc_entry(H, m, i0, e, acc);
+    fv_anderson_acc_wave(acc, part);
     __syncthreads();
     if (threadIdx.x < kFvAaSums) {
       double s = part[0][threadIdx.x];
@@ -154,54 +105,12 @@ __device__ __forceinline__ void fv_anderson_gram(const FvAaHist& H, int n3, int 
   }
 }
 
-// ---- 3. (A + lambda I) gamma = b by Cholesky, one thread; false: a pivot that is not > 0 or a gamma that is not finite
-//         (wide_mix_solve of ldc_fv_wide_anderson.inc is a copy: a change to one goes into the other)
-__device__ __forceinline__ bool fv_anderson_solve(int m, double (*A)[kFvAaDepth + 1], const double* b, double* gamma) {
-  double tr = 0.0;
-  for (int i = 0; i < m; ++i) tr += A[i][i];
-  const double lam = kFvAaLambda * tr / m;
-  for (int i = 0; i < m; ++i) A[i][i] += lam;
-  for (int i = 0; i < m; ++i) {                            // the lower triangle becomes R^T
-    for (int k = 0; k <= i; ++k) {
-      double s = A[i][k];
-      for (int q = 0; q < k; ++q) s -= A[i][q] * A[k][q];
-      if (k == i) {
-        if (!(s > 0.0)) return false;
-        A[i][i] = sqrt(s);
-      } else {
-        A[i][k] = s / A[k][k];
-      }
-    }
-  }
-  for (int i = 0; i < m; ++i) {
-    double s = b[i];
-    for (int q = 0; q < i; ++q) s -= A[i][q] * gamma[q];
-    gamma[i] = s / A[i][i];
-  }
-  for (int i = m - 1; i >= 0; --i) {
-    double s = gamma[i];
-    for (int q = i + 1; q < m; ++q) s -= A[q][i] * gamma[q];
-    gamma[i] = s / A[i][i];
-  }
-  for (int i = 0; i < m; ++i)
-    if (!(fabs(gamma[i]) <= 1.7976931348623157e308)) return false;
-  return true;
-}
-
-// ---- 4. x_next = g - sum_i gamma_i dG_i (slot order) into the state and x; the pinned cell's p is written as 0.0.
-//         The fallback leaves the state (it is g) and keeps g as x.
+// ---- 3. is fv_anderson_solve of ldc_fv_anderson_cells.inc, which thread 0 calls on A, b and gamma in LDS
+// ---- 4. x_next into the state and x, every entry
 __device__ __forceinline__ void fv_anderson_mix(const FvDesc& d, const FvAaHist& H, int n, int m, bool fell,
                                                 const double* gamma) {
   const int L = (int)H.L;
-  for (int e = threadIdx.x; e < L; e += kFvThreads) {
-    double xn = H.gp[e];
-    if (!fell) {
-      for (int k = 0; k < m; ++k) xn -= gamma[k] * H.dG[k * H.L + e];
-      if (e == 2 * n) xn = 0.0;
-      *fv_state_at(d, n, e) = xn;
-    }
-    H.x[e] = xn;
-  }
+  for (int e = threadIdx.x; e < L; e += kFvThreads) fv_anderson_mix_entry(d, H, n, e, m, fell, gamma);
 }
 
 __global__ __launch_bounds__(kFvThreads) void fv_anderson_kernel(FvAndersonLaunch, int j, int n_iters) {
@@ -249,8 +158,6 @@ __global__ __launch_bounds__(kFvThreads) void fv_anderson_kernel(FvAndersonLaunc
     T.astate[3] = fallbacks + (fell ? 1 : 0);
   }
 }
-
-inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 }  // namespace
 

@@ -2,9 +2,10 @@
 // ldc_kernels.hip (through ldc_fv_kernel.inc, the SIMPLE iteration with one trial per CU), ldc_fv_wide.hip (the same
 // iteration by the whole chip), ldc_fv_post.hip (streamfunction and vortex metrics), ldc_fv_prolong.hip (coarse-to-fine
 // transfer of the state) and ldc_fv_anderson.hip (Anderson mixing).
-// Types, constants and the host-side fill of a descriptor only, no device function: each unit's code object holds
-// what that unit needs and depends on no other's.  The device functions that the two units of the SIMPLE iteration
-// share are in ldc_fv_cells.inc, which post, prolong and anderson do not include.
+// Types, constants and host-side helpers (the fill of a descriptor, as_stream) only, no device function: each unit's
+// code object holds what that unit needs and depends on no other's.  The device functions that two mappings share are
+// in ldc_fv_cells.inc (the SIMPLE iteration), ldc_fv_post_cells.inc, ldc_fv_prolong_cells.inc and
+// ldc_fv_anderson_cells.inc, each included only by the units that call it.
 #ifndef LDC_FV_COMMON_INC
 #define LDC_FV_COMMON_INC
 
@@ -39,6 +40,9 @@ struct FvDesc {
   long long *ctrl;
 };
 static_assert(sizeof(FvDesc) <= LDC_FV_DESC_DOUBLES * sizeof(double), "descriptor slot");
+
+// host: the caller's stream handle of the C ABI
+inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // host: validate `pr` (not null) for a mapping that takes grids up to max_n x max_n and fill the descriptor from it.
 // 0 or LDC_E_ARG; needs no device.

@@ -22,16 +22,17 @@
 // The post blocks reach the device through fv_post_stage_kernel: the structs travel as kernel arguments and one thread
 // per trial writes them behind the descriptor.  Stream-ordered, no host synchronisation, no library-owned staging.
 //
-// ldc_fv_wide.hip holds COPIES of the bodies of fv_post_vorticity, fv_post_gemm, fv_post_extrema and of the result block
-// of fv_post_kernel (fv_wide_post_*: the same chain for a chip or shared trial, one launch per phase): a change to one
-// goes into the other.
+// The arithmetic is NOT written here: one cell of omega, one GEMM tile, the candidates with their scan and merge and the
+// result block are the functions of ldc_fv_post_cells.inc, which ldc_fv_wide.hip calls too (fv_wide_post_*: the same
+// chain for a chip or shared trial, one launch per phase).  What this unit adds is the mapping: the post block and its
+// staging, the loops of a work-group of 512 threads over cells and tiles, and the barriers between the phases.
 
 #include <hip/hip_runtime.h>
-#include <limits.h>
 #include <stdint.h>
 
 #include "ldc_hip.h"
 #include "ldc_fv_common.inc"
+#include "ldc_fv_post_cells.inc"
 
 namespace {
 
@@ -67,52 +68,24 @@ struct FvPostLaunch {
   const FvDesc* d[LDC_FV_LAUNCH_MAX];
 };
 
-// C[r*ldc + c] = sum_k A(r, k) B(k, c) (M x N), A(r, k) = A[r*sar + k*sak], B(k, c) = B[k*sbk + c*sbc]: fv_gemm of
-// the solve kernel (one wave per 16 x 16 tile, round-robin; operands from L2, zero fill at the edges) with a leading
-// dimension for C and the Dirichlet epilogue.  SCALE: C[a][b] /= cx*lamx[b] + cy*lamy[a]; every mode is kept.
+// one GEMM of the fast diagonalisation: one wave per 16 x 16 tile, round-robin
 template <bool SCALE>
 __device__ void fv_post_gemm(const double* A, int sar, int sak, const double* B, int sbk, int sbc, double* Cm, int ldc,
                              int M, int N, int K, const double* lamx, const double* lamy, double cx, double cy) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int tn = (N + 15) >> 4, tiles = ((M + 15) >> 4) * tn;
-  for (int t = w; t < tiles; t += kFvWaves) {
-    const int r0 = (t / tn) * 16, c0 = (t % tn) * 16;
-    const int ar = r0 + (lane & 15), bc = c0 + (lane & 15), kq = lane >> 4;
-    v4d acc = {0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < K; k0 += 4) {
-      const int k = k0 + kq;
-      const double a = (ar < M && k < K) ? A[ar * sar + k * sak] : 0.0;
-      const double b = (bc < N && k < K) ? B[k * sbk + bc * sbc] : 0.0;
-      acc = MFMA_F64(a, b, acc);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int row = r0 + (lane >> 4) + 4 * q, col = c0 + (lane & 15);
-      if (row < M && col < N) {
-        double val = acc[q];
-        if (SCALE) val = val / (cx * lamx[col] + cy * lamy[row]);
-        Cm[row * ldc + col] = val;
-      }
-    }
-  }
+  const int w = threadIdx.x >> 6;
+  const int tiles = ((M + 15) >> 4) * ((N + 15) >> 4);
+  for (int t = w; t < tiles; t += kFvWaves)
+    fv_post_gemm_tile<SCALE>(t, A, sar, sak, B, sbk, sbc, Cm, ldc, M, N, K, lamx, lamy, cx, cy);
 }
 
-// ---- 1. omega with ghost cells (-f at the walls, 2 lid - u at the lid), psi = 0 on the boundary ring; true if this
-//         thread saw a value that is not finite
+// ---- 1. omega at every cell, psi = 0 on the boundary ring; true if this thread saw a value that is not finite
 __device__ __forceinline__ bool fv_post_vorticity(const FvDesc& d, const FvPost& P) {
   const int nx = d.nx, ny = d.ny, n = nx * ny;
   const double dx = d.dx, dy = d.dy, lid = d.lid;
   const double *u = d.u, *v = d.v;
   bool bad = false;
-  for (int c = threadIdx.x; c < n; c += kFvThreads) {
-    const int i = c % nx, j = c / nx;
-    const double vE = i < nx - 1 ? v[c + 1] : -v[c], vW = i > 0 ? v[c - 1] : -v[c];
-    const double uN = j < ny - 1 ? u[c + nx] : 2 * lid - u[c], uS = j > 0 ? u[c - nx] : -u[c];
-    const double wc = (vE - vW) / (2 * dx) - (uN - uS) / (2 * dy);
-    P.omega[c] = wc;
-    bad |= !(fabs(wc) <= 1.7976931348623157e308);
-    if (i == 0 || i == nx - 1 || j == 0 || j == ny - 1) P.psi[c] = 0.0;
-  }
+  for (int c = threadIdx.x; c < n; c += kFvThreads)
+    bad |= fv_post_cell_vorticity(c, nx, ny, dx, dy, lid, u, v, P.omega, P.psi);
   __syncthreads();
   return bad;
 }
@@ -133,54 +106,15 @@ __device__ __forceinline__ void fv_post_psi(const FvDesc& d, const FvPost& P) {
   __syncthreads();
 }
 
-// an extremum candidate: the largest key, among equal keys the lowest cell index
-struct FvBest {
-  double key;
-  int idx;
-  __device__ __forceinline__ void scan(double k, int c) { if (k > key) { key = k; idx = c; } }     // increasing c
-  __device__ __forceinline__ void merge(double k, int c) { if (k > key || (k == key && c < idx)) { key = k; idx = c; } }
-};
-constexpr int kFvPostBest = 5;               // -psi, |omega|, psi in BR, BL, TL
-enum { FVP_PSI_MIN, FVP_OMEGA_MAX, FVP_BR, FVP_BL, FVP_TL };
-
 // ---- 3. the five extrema over the work-group, in a fixed order; every thread gets the same winners
 __device__ __forceinline__ bool fv_post_extrema(const FvDesc& d, const FvPost& P, FvBest (&best)[kFvPostBest],
                                                 double (*lkey)[kFvPostBest], int (*lidx)[kFvPostBest]) {
   const int nx = d.nx, n = d.nx * d.ny;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   bool bad = false;
-#pragma unroll
-  for (int q = 0; q < kFvPostBest; ++q) { best[q].key = -HUGE_VAL; best[q].idx = INT_MAX; }
-  for (int c = threadIdx.x; c < n; c += kFvThreads) {
-    const int i = c % nx, j = c / nx;
-    const double ps = P.psi[c], om = P.omega[c];
-    bad |= !(fabs(ps) <= 1.7976931348623157e308);
-    best[FVP_PSI_MIN].scan(-ps, c);
-    best[FVP_OMEGA_MAX].scan(fabs(om), c);
-    const bool left = i < P.ix_lt, right = i >= P.ix_gt, low = j < P.jy_lt, high = j >= P.jy_gt;
-    if (right && low) best[FVP_BR].scan(ps, c);
-    if (left && low) best[FVP_BL].scan(ps, c);
-    if (left && high) best[FVP_TL].scan(ps, c);
-  }
-#pragma unroll
-  for (int q = 0; q < kFvPostBest; ++q) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const double k = __shfl_xor(best[q].key, off);
-      const int c = __shfl_xor(best[q].idx, off);
-      best[q].merge(k, c);
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < kFvPostBest; ++q) { lkey[w][q] = best[q].key; lidx[w][q] = best[q].idx; }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < kFvPostBest; ++q) {
-    best[q].key = lkey[0][q]; best[q].idx = lidx[0][q];
-    for (int v = 1; v < kFvWaves; ++v) best[q].merge(lkey[v][q], lidx[v][q]);
-  }
+  fv_post_best_clear(best);
+  for (int c = threadIdx.x; c < n; c += kFvThreads)
+    bad |= fv_post_cell_extrema(c, nx, P.psi, P.omega, P.ix_lt, P.ix_gt, P.jy_lt, P.jy_gt, best);
+  fv_post_best_merge<kFvWaves>(best, lkey, lidx);
   return bad;
 }
 
@@ -197,27 +131,8 @@ __global__ __launch_bounds__(kFvThreads) void fv_post_kernel(FvPostLaunch) {
   FvBest best[kFvPostBest];
   bad |= fv_post_extrema(d, P, best, lkey, lidx);
   const int any_bad = __syncthreads_or(bad ? 1 : 0);
-  if (threadIdx.x == 0) {
-    double* r = P.result;
-    const int cmin = best[FVP_PSI_MIN].idx, cmax = best[FVP_OMEGA_MAX].idx;
-    const int n = d.nx * d.ny;
-    const bool ok = cmin < n && cmax < n;      // (a NaN field leaves a candidate empty; the flag below says so)
-    r[LDC_FV_POST_PSI_MIN] = ok ? P.psi[cmin] : 0.0;
-    r[LDC_FV_POST_OMEGA_CENTER] = ok ? P.omega[cmin] : 0.0;
-    r[LDC_FV_POST_OMEGA_MAX] = ok ? P.omega[cmax] : 0.0;
-    r[LDC_FV_POST_PSI_MIN_CELL] = ok ? cmin : -1;
-    r[LDC_FV_POST_OMEGA_MAX_CELL] = ok ? cmax : -1;
-    for (int q = 0; q < 3; ++q) {              // BR, BL, TL; an empty region: value -inf, cell -1
-      const FvBest& b = best[FVP_BR + q];
-      r[LDC_FV_POST_PSI_BR + q] = b.key;
-      r[LDC_FV_POST_PSI_BR_CELL + q] = b.idx < n ? b.idx : -1;
-    }
-    r[LDC_FV_POST_NONFINITE] = (any_bad || !ok) ? 1.0 : 0.0;
-    for (int q = LDC_FV_POST_NONFINITE + 1; q < LDC_FV_POST_RESULT_LEN; ++q) r[q] = 0.0;
-  }
+  if (threadIdx.x == 0) fv_post_result(d.nx * d.ny, P.psi, P.omega, best, any_bad, P.result);
 }
-
-inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 }  // namespace
 

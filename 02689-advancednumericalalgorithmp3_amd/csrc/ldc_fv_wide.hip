@@ -48,6 +48,9 @@
 // Behind the solve, at the end of this file: the post-processing chain (ldc_fv_wide_post_enqueue: omega, psi and the vortex
 // extrema of one trial in seven launches) and the prolongation (ldc_fv_wide_prolong_enqueue: two launches per pair), by
 // the same rules for trials of up to 1024 x 1024 cells.  They have no gate and touch neither ctrl, rec nor `scratch`.
+// Their arithmetic, and that of the mixing, is not written here either: ldc_fv_post_cells.inc, ldc_fv_prolong_cells.inc
+// and ldc_fv_anderson_cells.inc hold it for this unit and for the one-CU units ldc_fv_post.hip, ldc_fv_prolong.hip and
+// ldc_fv_anderson.hip alike.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -61,6 +64,9 @@
 #include "ldc_hip.h"
 #include "ldc_fv_common.inc"
 #include "ldc_fv_cells.inc"
+#include "ldc_fv_anderson_cells.inc"
+#include "ldc_fv_post_cells.inc"
+// (ldc_fv_prolong_cells.inc: at the prolongation section, behind its FP_CONTRACT pragma)
 
 namespace {
 
@@ -539,11 +545,11 @@ __global__ __launch_bounds__(kWT) void fv_wide_record(FvWideArgs a) { WIDE_LDS; 
 __global__ __launch_bounds__(kWT) void fv_wide_b_record(FvWideTable t) { WIDE_LDS; WIDE_SINGLE; wide_record(a, lds); }
 
 __global__ __launch_bounds__(kWT) void fv_wide_mix_push(FvWideArgs a, FvWideMix x) {
-  __shared__ double part[kWW][kWMixSums];
+  __shared__ double part[kWW][kFvAaSums];
   wide_mix_push(a, x, blockIdx.x, part);
 }
 __global__ __launch_bounds__(kWT) void fv_wide_b_mix_push(FvWideTable t) {
-  __shared__ double part[kWW][kWMixSums];
+  __shared__ double part[kWW][kFvAaSums];
   WIDE_MAPPED(sweep);
   wide_mix_push(a, t.entries[m_ >> 16].m, g, part);
 }
@@ -561,8 +567,6 @@ __global__ __launch_bounds__(64) void fv_wide_b_mix_close(FvWideTable t) {
   WIDE_SINGLE;
   wide_mix_close(a, t.entries[blockIdx.x].m);
 }
-
-inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 std::mutex g_wide_mutex;
 hipStream_t g_wide_stream[64] = {};
@@ -953,15 +957,12 @@ int ldc_fv_wide_batch_launches(const ldc_fv_wide_batch* b, int lin_budget) {
 // tile of the (ny - 2) x (nx - 2) interior, four tiles per work-group; `result` is ONE work-group.  Every work-group of a
 // sweep leaves its not-finite flag and its five (key, cell) candidates in its own slot of the caller's scratch, and
 // `result` merges the slots by (larger key, then lower cell): the rule does not depend on the grouping, so the winners
-// are those of the one-CU kernel.  The bodies below are COPIES of fv_post_vorticity, fv_post_gemm, fv_post_extrema and
-// of the result block of fv_post_kernel (ldc_fv_post.hip names these copies too): a change to one goes into the other.
+// are those of the one-CU kernel.  The arithmetic is that kernel's too: both call the functions of ldc_fv_post_cells.inc.
 // Nothing here reads or writes ctrl, rec, the state or the scratch of the solve, and there is no gate.
 namespace {
 
 constexpr int kWPS = 12;                    // doubles of a post slot: 5 keys, 5 cells (as doubles), 2 not-finite flags
-constexpr int kWPBest = 5;                  // -psi, |omega|, psi in BR, BL, TL
-constexpr int kWPNone = 2147483647;         // the cell of an empty candidate (INT_MAX, as fv_post_extrema)
-enum { WP_PSI_MIN, WP_OMEGA_MAX, WP_BR, WP_BL, WP_TL, WP_CELL = kWPBest, WP_BAD_OMEGA = 2 * kWPBest, WP_BAD_PSI };
+enum { WP_CELL = kFvPostBest, WP_BAD_OMEGA = 2 * kFvPostBest, WP_BAD_PSI };     // (the keys: FVP_* at 0 .. 4)
 static_assert(LDC_FV_WIDE_POST_SCRATCH_LEN(8, 8) == kWPS * 1, "post scratch layout");
 static_assert(LDC_FV_WIDE_POST_SCRATCH_LEN(1024, 1024) == kWPS * kWMaxG, "post scratch layout");
 constexpr int kWidePostLaunches = 7;
@@ -980,57 +981,25 @@ struct FvWidePostGemm {
   int sar, sak, sbk, sbc, ldc, M, N, K;
 };
 
-// ---- 1. omega with ghost cells, psi = 0 on the ring (fv_post_vorticity); slot: this work-group saw a value that is
-//         not finite
+// ---- 1. omega with ghost cells, psi = 0 on the ring; slot: this work-group saw a value that is not finite
 __global__ __launch_bounds__(kWT) void fv_wide_post_omega(FvWidePost a) {
   const int g = blockIdx.x;
   const int nx = a.nx, ny = a.ny, n = nx * ny;
-  const double dx = a.dx, dy = a.dy, lid = a.lid;
-  const double *u = a.u, *v = a.v;
   bool bad = false;
-  for (int c = g * kWT + threadIdx.x; c < n; c += a.G * kWT) {
-    const int i = c % nx, j = c / nx;
-    const double vE = i < nx - 1 ? v[c + 1] : -v[c], vW = i > 0 ? v[c - 1] : -v[c];
-    const double uN = j < ny - 1 ? u[c + nx] : 2 * lid - u[c], uS = j > 0 ? u[c - nx] : -u[c];
-    const double wc = (vE - vW) / (2 * dx) - (uN - uS) / (2 * dy);
-    a.omega[c] = wc;
-    bad |= !(fabs(wc) <= 1.7976931348623157e308);
-    if (i == 0 || i == nx - 1 || j == 0 || j == ny - 1) a.psi[c] = 0.0;
-  }
+  for (int c = g * kWT + threadIdx.x; c < n; c += a.G * kWT)
+    bad |= fv_post_cell_vorticity(c, nx, ny, a.dx, a.dy, a.lid, a.u, a.v, a.omega, a.psi);
   const int any_bad = __syncthreads_or(bad ? 1 : 0);
   if (threadIdx.x == 0) a.slots[g * kWPS + WP_BAD_OMEGA] = any_bad ? 1.0 : 0.0;
 }
 
-// ---- 2. one GEMM of the sine fast diagonalisation, one tile per wave (the tile body of fv_post_gemm: operands from L2,
-//         zero fill at the edges, ONE accumulator over k in steps of 4, a leading dimension for C).  SCALE: the Dirichlet
-//         epilogue C[a][b] /= cx lamx[b] + cy lamy[a]; every mode is kept.
+// ---- 2. one GEMM of the sine fast diagonalisation, one tile per wave.  SCALE: the Dirichlet epilogue.
 template <bool SCALE>
 __global__ __launch_bounds__(kWT) void fv_wide_post_gemm(FvWidePostGemm g, const double* lamx, const double* lamy, double dx,
                                                          double dy) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int M = g.M, N = g.N, K = g.K;
-  const int tn = (N + 15) >> 4, tiles = ((M + 15) >> 4) * tn;
-  const int t = blockIdx.x * kWW + w;
-  if (t >= tiles) return;
+  const int t = blockIdx.x * kWW + (threadIdx.x >> 6);
+  if (t >= ((g.M + 15) >> 4) * ((g.N + 15) >> 4)) return;
   const double cx = 1.0 / (dx * dx), cy = 1.0 / (dy * dy);
-  const int r0 = (t / tn) * 16, c0 = (t % tn) * 16;
-  const int ar = r0 + (lane & 15), bc = c0 + (lane & 15), kq = lane >> 4;
-  v4d acc = {0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    const int k = k0 + kq;
-    const double av = (ar < M && k < K) ? g.A[ar * g.sar + k * g.sak] : 0.0;
-    const double bv = (bc < N && k < K) ? g.B[k * g.sbk + bc * g.sbc] : 0.0;
-    acc = MFMA_F64(av, bv, acc);
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int row = r0 + (lane >> 4) + 4 * q, col = c0 + (lane & 15);
-    if (row < M && col < N) {
-      double val = acc[q];
-      if (SCALE) val = val / (cx * lamx[col] + cy * lamy[row]);
-      g.C[row * g.ldc + col] = val;
-    }
-  }
+  fv_post_gemm_tile<SCALE>(t, g.A, g.sar, g.sak, g.B, g.sbk, g.sbc, g.C, g.ldc, g.M, g.N, g.K, lamx, lamy, cx, cy);
 }
 
 // the four GEMMs: W1 = Sy^T F, W2 = W1 Sx / Lambda, W1 = Sy W2, psi = W1 Sx^T (the operands and strides of fv_post_psi)
@@ -1045,110 +1014,43 @@ inline FvWidePostGemm wide_post_gemm_of(const FvDesc& d, const struct ldc_fv_pos
   return {W1, p.Sx, p.psi + nx + 1, mx, 1, 1, mx, nx, my, mx, mx};
 }
 
-// an extremum candidate: the largest key, among equal keys the lowest cell (FvBest of ldc_fv_post.hip)
-struct WideBest {
-  double key;
-  int idx;
-  __device__ __forceinline__ void scan(double k, int c) { if (k > key) { key = k; idx = c; } }     // increasing c
-  __device__ __forceinline__ void merge(double k, int c) { if (k > key || (k == key && c < idx)) { key = k; idx = c; } }
-};
+#define WIDE_POST_LDS __shared__ double lkey[kWW][kFvPostBest]; __shared__ int lidx[kWW][kFvPostBest]
 
-// the five candidates of all threads of the work-group merged in a fixed order; thread 0 holds the winners
-__device__ __forceinline__ void wide_best_merge(WideBest (&best)[kWPBest], double (*lkey)[kWPBest], int (*lidx)[kWPBest]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < kWPBest; ++q) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const double k = __shfl_xor(best[q].key, off);
-      const int c = __shfl_xor(best[q].idx, off);
-      best[q].merge(k, c);
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < kWPBest; ++q) { lkey[w][q] = best[q].key; lidx[w][q] = best[q].idx; }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < kWPBest; ++q) {
-    best[q].key = lkey[0][q]; best[q].idx = lidx[0][q];
-    for (int v = 1; v < kWW; ++v) best[q].merge(lkey[v][q], lidx[v][q]);
-  }
-}
-
-#define WIDE_POST_LDS __shared__ double lkey[kWW][kWPBest]; __shared__ int lidx[kWW][kWPBest]
-
-// ---- 3. the five extrema over this work-group's cells (fv_post_extrema): each thread scans its cells in increasing c
-//         with strict comparisons; slot: the winners and the not-finite flag of psi
+// ---- 3. the five extrema over this work-group's cells; slot: the winners and the not-finite flag of psi
 __global__ __launch_bounds__(kWT) void fv_wide_post_extrema(FvWidePost a) {
   WIDE_POST_LDS;
   const int g = blockIdx.x;
   const int nx = a.nx, n = a.nx * a.ny;
   bool bad = false;
-  WideBest best[kWPBest];
-#pragma unroll
-  for (int q = 0; q < kWPBest; ++q) { best[q].key = -HUGE_VAL; best[q].idx = kWPNone; }
-  for (int c = g * kWT + threadIdx.x; c < n; c += a.G * kWT) {
-    const int i = c % nx, j = c / nx;
-    const double ps = a.psi[c], om = a.omega[c];
-    bad |= !(fabs(ps) <= 1.7976931348623157e308);
-    best[WP_PSI_MIN].scan(-ps, c);
-    best[WP_OMEGA_MAX].scan(fabs(om), c);
-    const bool left = i < a.ix_lt, right = i >= a.ix_gt, low = j < a.jy_lt, high = j >= a.jy_gt;
-    if (right && low) best[WP_BR].scan(ps, c);
-    if (left && low) best[WP_BL].scan(ps, c);
-    if (left && high) best[WP_TL].scan(ps, c);
-  }
-  wide_best_merge(best, lkey, lidx);
+  FvBest best[kFvPostBest];
+  fv_post_best_clear(best);
+  for (int c = g * kWT + threadIdx.x; c < n; c += a.G * kWT)
+    bad |= fv_post_cell_extrema(c, nx, a.psi, a.omega, a.ix_lt, a.ix_gt, a.jy_lt, a.jy_gt, best);
+  fv_post_best_merge<kWW>(best, lkey, lidx);
   const int any_bad = __syncthreads_or(bad ? 1 : 0);
   if (threadIdx.x == 0) {
     double* s = a.slots + g * kWPS;
 #pragma unroll
-    for (int q = 0; q < kWPBest; ++q) { s[q] = best[q].key; s[WP_CELL + q] = (double)best[q].idx; }
+    for (int q = 0; q < kFvPostBest; ++q) { s[q] = best[q].key; s[WP_CELL + q] = (double)best[q].idx; }
     s[WP_BAD_PSI] = any_bad ? 1.0 : 0.0;
   }
 }
 
-// ---- 4. result (one work-group): thread t takes slot t, the same merge, then the result block of fv_post_kernel, the
-//         empty-candidate and not-finite cases included
+// ---- 4. result (one work-group): thread t takes slot t, the same merge, then the result block
 __global__ __launch_bounds__(kWT) void fv_wide_post_result(FvWidePost a) {
   WIDE_POST_LDS;
-  const int n = a.nx * a.ny;
   const bool mine = (int)threadIdx.x < a.G;
   const double* s = a.slots + threadIdx.x * kWPS;
-  WideBest best[kWPBest];
+  FvBest best[kFvPostBest];
 #pragma unroll
-  for (int q = 0; q < kWPBest; ++q) {
+  for (int q = 0; q < kFvPostBest; ++q) {
     best[q].key = mine ? s[q] : -HUGE_VAL;
-    best[q].idx = mine ? (int)s[WP_CELL + q] : kWPNone;
+    best[q].idx = mine ? (int)s[WP_CELL + q] : kFvPostNone;
   }
   const bool bad = mine && (s[WP_BAD_OMEGA] != 0.0 || s[WP_BAD_PSI] != 0.0);
-  wide_best_merge(best, lkey, lidx);
+  fv_post_best_merge<kWW>(best, lkey, lidx);
   const int any_bad = __syncthreads_or(bad ? 1 : 0);
-  if (threadIdx.x == 0) {
-    double* r = a.result;
-    const int cmin = best[WP_PSI_MIN].idx, cmax = best[WP_OMEGA_MAX].idx;
-    const bool ok = cmin < n && cmax < n;      // (a NaN field leaves a candidate empty; the flag below says so)
-    r[LDC_FV_POST_PSI_MIN] = ok ? a.psi[cmin] : 0.0;
-    r[LDC_FV_POST_OMEGA_CENTER] = ok ? a.omega[cmin] : 0.0;
-    r[LDC_FV_POST_OMEGA_MAX] = ok ? a.omega[cmax] : 0.0;
-    r[LDC_FV_POST_PSI_MIN_CELL] = ok ? cmin : -1;
-    r[LDC_FV_POST_OMEGA_MAX_CELL] = ok ? cmax : -1;
-    for (int q = 0; q < 3; ++q) {              // BR, BL, TL; an empty region: value -inf, cell -1
-      const WideBest& b = best[WP_BR + q];
-      r[LDC_FV_POST_PSI_BR + q] = b.key;
-      r[LDC_FV_POST_PSI_BR_CELL + q] = b.idx < n ? b.idx : -1;
-    }
-    r[LDC_FV_POST_NONFINITE] = (any_bad || !ok) ? 1.0 : 0.0;
-    for (int q = LDC_FV_POST_NONFINITE + 1; q < LDC_FV_POST_RESULT_LEN; ++q) r[q] = 0.0;
-  }
-}
-
-// one domain: nx dx and ny dy of both trials agree (fv_same_domain of ldc_fv_prolong.hip)
-inline bool wide_same_extent(double a, double b) { return fabs(a - b) <= 1e-12 * fmax(fabs(a), fabs(b)); }
-inline bool wide_same_domain(const FvDesc& c, const FvDesc& f) {
-  return wide_same_extent(c.nx * c.dx, f.nx * f.dx) && wide_same_extent(c.ny * c.dy, f.ny * f.dy);
+  if (threadIdx.x == 0) fv_post_result(a.nx * a.ny, a.psi, a.omega, best, any_bad, a.result);
 }
 
 }  // namespace
@@ -1193,11 +1095,14 @@ int ldc_fv_wide_post_launches(const ldc_fv_wide* h) {
 // Prolongation of ONE (coarse, fine) pair of chip or shared trials (ldc_fv_wide_prolong_enqueue): the work of
 // fv_prolong_kernel (ldc_fv_prolong.hip) as two launches of the FINE trial's G work-groups, grid-stride -- `cells` (u, v,
 // p; every thread recomputes the interpolated p at fine cell 0 for itself, so p[0] is exactly 0.0 and nothing is
-// broadcast) and, behind the launch boundary, `fluxes` (mdot from the new u and v, wall faces exactly 0.0).  FvAxis,
-// the node and interpolation functions and both loop bodies are COPIES of those in ldc_fv_prolong.hip, which names these
-// copies too: a change to one goes into the other.  Contraction is off from here to the end of the unit, as it is there:
-// the arithmetic has no multiply-add that the compiler could fuse, and the fine state is that kernel's, bit for bit.
+// broadcast) and, behind the launch boundary, `fluxes` (mdot from the new u and v, wall faces exactly 0.0).  The
+// arithmetic is that kernel's: both call the functions of ldc_fv_prolong_cells.inc.  Contraction is off from here to the
+// end of the unit, as it is there -- the arithmetic has no multiply-add that the compiler could fuse, and the fine state is
+// that kernel's, bit for bit -- so the include stands HERE, behind the pragma and behind the SIMPLE chain, whose
+// multiply-adds stay fused.
 #pragma STDC FP_CONTRACT OFF
+
+#include "ldc_fv_prolong_cells.inc"
 
 namespace {
 
@@ -1206,88 +1111,24 @@ struct FvWideProlong {
   int G;                                    // work-groups of a sweep over the FINE cells
 };
 
-// one axis of the extended coarse grid: nodes e_0 = 0, e_k = (k - 1/2) h (k = 1..n), e_{n+1} = n h
-struct WideAxis {
-  int n;
-  double h;
-  __device__ __forceinline__ double node(int k) const { return k == 0 ? 0.0 : (k == n + 1 ? n * h : (k - 0.5) * h); }
-  // the left node of x (the largest node <= x, at most n: the last interval) and the weight inside its interval
-  __device__ __forceinline__ void locate(double x, int& k, double& t) const {
-    k = (int)(x / h + 0.5);
-    k = k < 0 ? 0 : (k > n ? n : k);
-    while (k < n && node(k + 1) <= x) ++k;           // (the guess is off by one at most: rounding at a node)
-    while (k > 0 && node(k) > x) --k;
-    const double e0 = node(k), e1 = node(k + 1);
-    t = (x - e0) / (e1 - e0);
-  }
-};
-
-enum WideRing { WIDE_RING_U, WIDE_RING_V, WIDE_RING_P };
-
-// the extended coarse field at node (kx, ky), kx = 0..nx+1, ky = 0..ny+1
-template <WideRing R>
-__device__ __forceinline__ double wide_prolong_node(const FvDesc& c, const double* f, int kx, int ky) {
-  const int nx = c.nx, ny = c.ny;
-  if (R == WIDE_RING_P) {
-    const int i = kx < 1 ? 0 : (kx > nx ? nx - 1 : kx - 1), j = ky < 1 ? 0 : (ky > ny ? ny - 1 : ky - 1);
-    return f[j * nx + i];
-  }
-  const bool inx = kx >= 1 && kx <= nx, iny = ky >= 1 && ky <= ny;
-  if (inx && iny) return f[(ky - 1) * nx + (kx - 1)];
-  if (R == WIDE_RING_U && inx && ky == ny + 1) return c.ulid[kx - 1];
-  return 0.0;
-}
-
-template <WideRing R>
-__device__ __forceinline__ double wide_prolong_at(const FvDesc& c, const double* f, int kx, double tx, int ky, double ty) {
-  const double a = wide_prolong_node<R>(c, f, kx, ky), b = wide_prolong_node<R>(c, f, kx + 1, ky);
-  const double lo = a + tx * (b - a);
-  const double a1 = wide_prolong_node<R>(c, f, kx, ky + 1), b1 = wide_prolong_node<R>(c, f, kx + 1, ky + 1);
-  const double hi = a1 + tx * (b1 - a1);
-  return lo + ty * (hi - lo);
-}
-
-// ---- 1. u, v, p at the fine cell centres (fv_prolong_cells)
+// ---- 1. u, v, p at the fine cell centres
 __global__ __launch_bounds__(kWT) void fv_wide_prolong_cells(FvWideProlong a) {
   const FvDesc &c = a.c, &f = a.f;
   const int nx = f.nx, n = f.nx * f.ny;
-  const WideAxis ax = {c.nx, c.dx}, ay = {c.ny, c.dy};
-  int kx0, ky0;
-  double tx0, ty0;
-  ax.locate((0 + 0.5) * f.dx, kx0, tx0);
-  ay.locate((0 + 0.5) * f.dy, ky0, ty0);
-  const double p0 = wide_prolong_at<WIDE_RING_P>(c, c.p, kx0, tx0, ky0, ty0);
-  for (int cell = blockIdx.x * kWT + threadIdx.x; cell < n; cell += a.G * kWT) {
-    const int i = cell % nx, j = cell / nx;
-    int kx, ky;
-    double tx, ty;
-    ax.locate((i + 0.5) * f.dx, kx, tx);
-    ay.locate((j + 0.5) * f.dy, ky, ty);
-    f.u[cell] = wide_prolong_at<WIDE_RING_U>(c, c.u, kx, tx, ky, ty);
-    f.v[cell] = wide_prolong_at<WIDE_RING_V>(c, c.v, kx, tx, ky, ty);
-    f.p[cell] = wide_prolong_at<WIDE_RING_P>(c, c.p, kx, tx, ky, ty) - p0;
-  }
+  const FvAxis ax = {c.nx, c.dx}, ay = {c.ny, c.dy};
+  const double p0 = fv_prolong_p0(c, f, ax, ay);
+  for (int cell = blockIdx.x * kWT + threadIdx.x; cell < n; cell += a.G * kWT)
+    fv_prolong_cell(c, f, ax, ay, nx, p0, cell);
 }
 
-// ---- 2. mdot = [ fx | fy ] from the new u and v: rho (1/2 f_N + 1/2 f_P) |S| inside, 0.0 on the walls
-//         (fv_prolong_fluxes)
+// ---- 2. mdot = [ fx | fy ] from the new u and v
 __global__ __launch_bounds__(kWT) void fv_wide_prolong_fluxes(FvWideProlong a) {
   const FvDesc& f = a.f;
   const int nx = f.nx, ny = f.ny;
   const int nfx = ny * (nx + 1), nfy = (ny + 1) * nx;
   double *fx = f.mdot, *fy = f.mdot + nfx;
-  for (int q = blockIdx.x * kWT + threadIdx.x; q < nfx; q += a.G * kWT) {
-    const int i = q % (nx + 1), j = q / (nx + 1);
-    double m = 0.0;
-    if (i > 0 && i < nx) m = f.rho * (0.5 * f.u[j * nx + i] + (1.0 - 0.5) * f.u[j * nx + i - 1]) * f.dy;
-    fx[q] = m;
-  }
-  for (int q = blockIdx.x * kWT + threadIdx.x; q < nfy; q += a.G * kWT) {
-    const int i = q % nx, j = q / nx;
-    double m = 0.0;
-    if (j > 0 && j < ny) m = f.rho * (0.5 * f.v[j * nx + i] + (1.0 - 0.5) * f.v[(j - 1) * nx + i]) * f.dx;
-    fy[q] = m;
-  }
+  for (int q = blockIdx.x * kWT + threadIdx.x; q < nfx; q += a.G * kWT) fv_prolong_xface(f, nx, fx, q);
+  for (int q = blockIdx.x * kWT + threadIdx.x; q < nfy; q += a.G * kWT) fv_prolong_yface(f, nx, ny, fy, q);
 }
 
 }  // namespace
@@ -1296,7 +1137,7 @@ extern "C" {
 
 int ldc_fv_wide_prolong_enqueue(ldc_fv_wide* coarse, ldc_fv_wide* fine, void* stream) {
   if (!coarse || !fine) return LDC_E_STATE;
-  if (coarse == fine || !wide_same_domain(coarse->a.d, fine->a.d)) return LDC_E_ARG;
+  if (coarse == fine || !fv_same_domain(coarse->a.d, fine->a.d)) return LDC_E_ARG;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
   if (coarse->device != dev || fine->device != dev) return LDC_E_STATE;

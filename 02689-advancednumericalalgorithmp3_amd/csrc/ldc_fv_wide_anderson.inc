@@ -6,7 +6,9 @@
 // x -> g = SIMPLE(x) on [u | v | p | mdot], hist = [ x | g_prev | f_prev | dG[depth] | dF[depth] ], A = dF^T dF and
 // b = dF^T f over the first 3n entries with the columns in slot order, lambda = 1e-12 trace(A) / m, Cholesky by one thread,
 // x_next = g - sum_i gamma_i dG_i over all L entries with p[0] written as 0.0, the same fallback and the same four astate
-// words.  The mapping is the chip mapping's: three launches behind `record`,
+// words.  Its arithmetic is NOT written here: the constants, the view of hist, push and mix for one entry, the row block
+// of the Gram sums and the solve are the functions of ldc_fv_anderson_cells.inc, which ldc_fv_wide.hip includes ahead of
+// this file and fv_anderson_kernel calls too.  The mapping is the chip mapping's: three launches behind `record`,
 //   push  (G work-groups)  f, the new columns dG and dF, g_prev, f_prev for its entries (x = g at once where the
 //                          iteration is not mixed); then its partial sums of b and of the lower triangle of A into its
 //                          own slot of the mixing scratch
@@ -30,13 +32,8 @@
 
 constexpr int kWMixWords = 8;
 enum { MW_FELL };
-constexpr int kWMixDepth = LDC_FV_ANDERSON_MAX_DEPTH;
-constexpr int kWMixRows = 4;                                  // rows of A per pass of push over its columns
-constexpr int kWMixSums = kWMixRows * (kWMixDepth + 1);       // per pass: 4 x (16 entries of A, 1 of b)
-constexpr int kWMixNeed = kWMixDepth * (kWMixDepth + 3) / 2;  // most doubles of a slot
-constexpr double kWMixLambda = 1e-12;
+constexpr int kWMixNeed = kFvAaDepth * (kFvAaDepth + 3) / 2;  // most doubles of a slot
 constexpr int kWideMixLaunches = LDC_FV_WIDE_ANDERSON_LAUNCHES;
-static_assert(kWMixDepth % kWMixRows == 0, "row blocks");
 static_assert(LDC_FV_WIDE_ANDERSON_SCRATCH_LEN(8, 8, 16) == kWMixWords + kWMixNeed * 1, "mixing scratch layout");
 static_assert(LDC_FV_WIDE_ANDERSON_SCRATCH_LEN(1024, 1024, 5) == kWMixWords + 20 * kWMaxG, "mixing scratch layout");
 static_assert(kWideMixLaunches == 3, "push | mix | close");
@@ -71,82 +68,35 @@ __device__ __forceinline__ WideMixPlan wide_mix_plan(const FvWideArgs& a, const 
   return p;
 }
 
-// the trial's vectors of L = 3n + faces doubles inside hist
-struct WideMixHist {
-  long long L;
-  double *x, *gp, *fp, *dG, *dF;
-  __device__ __forceinline__ WideMixHist(double* h, long long L_, int depth)
-      : L(L_), x(h), gp(h + L_), fp(h + 2 * L_), dG(h + 3 * L_), dF(h + (3 + depth) * L_) {}
-};
-
-// entry e of [u | v | p | mdot]
-__device__ __forceinline__ double* wide_state_at(const FvDesc& d, int n, int e) {
-  return e < n ? d.u + e : (e < 2 * n ? d.v + (e - n) : (e < 3 * n ? d.p + (e - 2 * n) : d.mdot + (e - 3 * n)));
-}
-
-// ---- push: f = g - x; the new columns into ring slot `slot`; g_prev = g, f_prev = f; without mixing x = g at once.  Then
-//      A[i][k] = dF_i . dF_k (k <= i) and b[i] = dF_i . f over this work-group's share of the first 3n entries, rows
-//      i0 .. i0 + 3 per pass, into its slot.  `part`: kWW x kWMixSums doubles of LDS.
-__device__ __forceinline__ void wide_mix_push(const FvWideArgs& a, const FvWideMix& x, int g, double (*part)[kWMixSums]) {
+// ---- push: every entry of this work-group through fv_anderson_push_entry.  Then A[i][k] = dF_i . dF_k (k <= i) and
+//      b[i] = dF_i . f over this work-group's share of the first 3n entries, rows i0 .. i0 + 3 per pass, into its slot.
+//      `part`: kWW x kFvAaSums doubles of LDS.
+__device__ __forceinline__ void wide_mix_push(const FvWideArgs& a, const FvWideMix& x, int g, double (*part)[kFvAaSums]) {
   const WideMixPlan p = wide_mix_plan(a, x);
   if (!p.go || p.count_only) return;
   const FvDesc& d = a.d;
   const int n = d.nx * d.ny, depth = x.depth, m = p.m;
-  const WideMixHist H(x.hist, 3LL * n + LDC_FV_FACES(d.nx, d.ny), depth);
+  const FvAaHist H(x.hist, 3LL * n + LDC_FV_FACES(d.nx, d.ny), depth);
   const int L = (int)H.L, stride = a.G * kWT;
   double *dGs = H.dG + p.slot * H.L, *dFs = H.dF + p.slot * H.L;
-  for (int e = g * kWT + threadIdx.x; e < L; e += stride) {
-    const double gv = *wide_state_at(d, n, e);
-    if (p.has_f) {
-      const double f = gv - H.x[e];
-      if (p.push) {
-        dGs[e] = gv - H.gp[e];
-        dFs[e] = f - H.fp[e];
-      }
-      H.gp[e] = gv;
-      H.fp[e] = f;
-    }
-    if (!p.mix) H.x[e] = gv;
-  }
+  for (int e = g * kWT + threadIdx.x; e < L; e += stride)
+    fv_anderson_push_entry(d, H, n, e, p.has_f, p.push, dGs, dFs, !p.mix);
   if (!p.mix) return;
   // (every entry read below was written above by this same thread, or by an earlier launch)
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n3 = 3 * n;
+  const int n3 = 3 * n;
   double* slot = x.mscr + kWMixWords + (long long)g * wide_mix_slot_len(depth);
-  for (int i0 = 0; i0 < m; i0 += kWMixRows) {
-    double acc[kWMixRows][kWMixDepth + 1];
-#pragma unroll
-    for (int r = 0; r < kWMixRows; ++r)
-#pragma unroll
-      for (int k = 0; k <= kWMixDepth; ++k) acc[r][k] = 0.0;
-    for (int e = g * kWT + threadIdx.x; e < n3; e += stride) {
-      double c[kWMixDepth + 1];
-#pragma unroll
-      for (int k = 0; k < kWMixDepth; ++k) c[k] = k < m ? H.dF[k * H.L + e] : 0.0;
-      c[kWMixDepth] = H.fp[e];
-#pragma unroll
-      for (int r = 0; r < kWMixRows; ++r) {
-        const double rv = i0 + r < m ? H.dF[(i0 + r) * H.L + e] : 0.0;
-#pragma unroll
-        for (int k = 0; k <= kWMixDepth; ++k) acc[r][k] = fma(rv, c[k], acc[r][k]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < kWMixRows; ++r) {
-#pragma unroll
-      for (int k = 0; k <= kWMixDepth; ++k) {
-        double s = acc[r][k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) part[w][r * (kWMixDepth + 1) + k] = s;
-      }
-    }
+  for (int i0 = 0; i0 < m; i0 += kFvAaRows) {
+    double acc[kFvAaRows][kFvAaDepth + 1];
+    fv_anderson_acc_clear(acc);
+    for (int e = g * kWT + threadIdx.x; e < n3; e += stride) fv_anderson_acc_entry(H, m, i0, e, acc);
+    fv_anderson_acc_wave(acc, part);
     __syncthreads();
-    if (threadIdx.x < kWMixSums) {
+    if (threadIdx.x < kFvAaSums) {
       double s = part[0][threadIdx.x];
       for (int v = 1; v < kWW; ++v) s += part[v][threadIdx.x];
-      const int i = i0 + (int)threadIdx.x / (kWMixDepth + 1), k = (int)threadIdx.x % (kWMixDepth + 1);
+      const int i = i0 + (int)threadIdx.x / (kFvAaDepth + 1), k = (int)threadIdx.x % (kFvAaDepth + 1);
       if (i < m) {
-        if (k == kWMixDepth) slot[i] = s;
+        if (k == kFvAaDepth) slot[i] = s;
         else if (k <= i) slot[depth + i * (i + 1) / 2 + k] = s;
       }
     }
@@ -154,53 +104,17 @@ __device__ __forceinline__ void wide_mix_push(const FvWideArgs& a, const FvWideM
   }
 }
 
-// (A + lambda I) gamma = b by Cholesky, one thread; false: a pivot that is not > 0 or a gamma that is not finite.  A copy
-// of fv_anderson_solve (ldc_fv_anderson.hip names this copy too), whose unit shares no device function with this one: a
-// change to one goes into the other.
-__device__ __forceinline__ bool wide_mix_solve(int m, double (*A)[kWMixDepth + 1], const double* b, double* gamma) {
-  double tr = 0.0;
-  for (int i = 0; i < m; ++i) tr += A[i][i];
-  const double lam = kWMixLambda * tr / m;
-  for (int i = 0; i < m; ++i) A[i][i] += lam;
-  for (int i = 0; i < m; ++i) {                            // the lower triangle becomes R^T
-    for (int k = 0; k <= i; ++k) {
-      double s = A[i][k];
-      for (int q = 0; q < k; ++q) s -= A[i][q] * A[k][q];
-      if (k == i) {
-        if (!(s > 0.0)) return false;
-        A[i][i] = sqrt(s);
-      } else {
-        A[i][k] = s / A[k][k];
-      }
-    }
-  }
-  for (int i = 0; i < m; ++i) {
-    double s = b[i];
-    for (int q = 0; q < i; ++q) s -= A[i][q] * gamma[q];
-    gamma[i] = s / A[i][i];
-  }
-  for (int i = m - 1; i >= 0; --i) {
-    double s = gamma[i];
-    for (int q = i + 1; q < m; ++q) s -= A[q][i] * gamma[q];
-    gamma[i] = s / A[i][i];
-  }
-  for (int i = 0; i < m; ++i)
-    if (!(fabs(gamma[i]) <= 1.7976931348623157e308)) return false;
-  return true;
-}
-
 // the LDS of the mix launch
 struct WideMixLds {
   double sum[kWW * kWS];
   double tot[kWMixNeed];
-  double A[kWMixDepth][kWMixDepth + 1];
-  double b[kWMixDepth], gamma[kWMixDepth];
+  double A[kFvAaDepth][kFvAaDepth + 1];
+  double b[kFvAaDepth], gamma[kFvAaDepth];
   int fell;
 };
 
-// ---- mix: the totals of the slots, the small solve, then x_next = g - sum_i gamma_i dG_i (slot order) into the state and
-//      x for this work-group's entries; the pinned cell's p is written as 0.0.  The fallback leaves the state (it is g)
-//      and keeps g as x.
+// ---- mix: the totals of the slots, the small solve (fv_anderson_solve), then every entry of this work-group through
+//      fv_anderson_mix_entry.
 __device__ __forceinline__ void wide_mix_mix(const FvWideArgs& a, const FvWideMix& x, int g, WideMixLds& s) {
   const WideMixPlan p = wide_mix_plan(a, x);
   if (!p.go || p.count_only || !p.mix) return;
@@ -229,23 +143,15 @@ __device__ __forceinline__ void wide_mix_mix(const FvWideArgs& a, const FvWideMi
       s.b[i] = s.tot[i];
       for (int k = 0; k <= i; ++k) s.A[i][k] = s.tot[m + i * (i + 1) / 2 + k];
     }
-    const int fell = wide_mix_solve(m, s.A, s.b, s.gamma) ? 0 : 1;
+    const int fell = fv_anderson_solve(m, s.A, s.b, s.gamma) ? 0 : 1;
     s.fell = fell;
     if (g == 0) reinterpret_cast<long long*>(x.mscr)[MW_FELL] = fell;
   }
   __syncthreads();
   const bool fell = s.fell != 0;
-  const WideMixHist H(x.hist, 3LL * n + LDC_FV_FACES(d.nx, d.ny), depth);
+  const FvAaHist H(x.hist, 3LL * n + LDC_FV_FACES(d.nx, d.ny), depth);
   const int L = (int)H.L, stride = a.G * kWT;
-  for (int e = g * kWT + threadIdx.x; e < L; e += stride) {
-    double xn = H.gp[e];
-    if (!fell) {
-      for (int k = 0; k < m; ++k) xn -= s.gamma[k] * H.dG[k * H.L + e];
-      if (e == 2 * n) xn = 0.0;
-      *wide_state_at(d, n, e) = xn;
-    }
-    H.x[e] = xn;
-  }
+  for (int e = g * kWT + threadIdx.x; e < L; e += stride) fv_anderson_mix_entry(d, H, n, e, m, fell, s.gamma);
 }
 
 // ---- close (one work-group): astate, once per iteration

@@ -1761,8 +1761,6 @@ namespace {
     if (_e != hipSuccess) return (int)_e;     \
   } while (0)
 
-inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 // write-through stores (st_out); ldc_debug_ablate bits 128 / 256 force plain / write-through for A/B timing
 // (tiles = work-groups of 16 x 16 nodes in the launch, all trials of a batch together: the `tiles` of make_stage_args and
 //  make_post_args)
