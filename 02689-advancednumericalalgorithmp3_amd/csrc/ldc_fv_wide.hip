@@ -15,6 +15,10 @@
 //   sums | record
 // and, for a trial with Anderson mixing attached (ldc_fv_wide_set_anderson; ldc_fv_wide_anderson.inc), behind it
 //   push | mix | close
+// A trial with the consistent pressure equation (ldc_fv_wide_set_pressure; ldc_fv_wide_pressure.inc) replaces
+// `faces | gemm x 4` and `fluxvort` by
+//   faces | init | min(pressure budget, pressure_max_iters) x (gemm x 4 | rz | ap | xr) | pfinish    and    fluxvort
+// of its own: conjugate gradients on the a_P-weighted operator, preconditioned by the same four GEMMs.
 // Rules every kernel keeps:
 //  - the grid is a function of (nx, ny) alone;
 //  - a work-group writes its partial sums to its own slot; the NEXT launch lets every work-group add all slots in one
@@ -29,7 +33,7 @@
 // word in `linfinish`, BEFORE u, v, p or mdot have been touched (assemble and BiCGSTAB write work vectors only), and
 // the host repeats the rest of the chunk with twice the budget: the result does not depend on the budget.
 //
-// scratch (LDC_FV_WIDE_SCRATCH_LEN doubles): 16 int64 words (overflow, record row, pending give-ups, pending BiCGSTAB
+// scratch (LDC_FV_WIDE_SCRATCH_LEN doubles): 16 int64 words (overflow: 1 from linfinish, 2 from pfinish; record row, pending give-ups, pending BiCGSTAB
 // iterations, the enqueue's quota of iterations), 2 x 32 doubles of BiCGSTAB scalars, 2 x G x 10 slot sums, G x 10 sums
 // of the record row.
 //
@@ -84,6 +88,8 @@ struct FvWideArgs {
   FvDesc d;
   double* scr;
   int G;                                    // work-groups of a sweep
+  int pmax;                                 // pressure_max_iters of a trial with the consistent pressure equation; 0: the
+                                            // reference's (in what was padding: the struct keeps its 208 bytes)
 };
 
 // The per-trial Anderson mixing block (ldc_fv_wide_set_anderson; ldc_fv_wide_anderson.inc): in the handle, by value in the
@@ -99,10 +105,18 @@ static_assert(sizeof(FvWideMix) == 32, "the mixing block");
 // The table of a batch in the caller's device buffer (LDC_FV_WIDE_BATCH_TABLE_LEN bytes): n entries, then the block map
 // of the cell sweeps (sum of G_q words) and that of the GEMMs (sum of LDC_FV_WIDE_GEMM_GROUPS words), one word
 // q << 16 | g per work-group, trial after trial.
+// The per-trial block of the consistent pressure equation (ldc_fv_wide_set_pressure; ldc_fv_wide_pressure.inc), behind the
+// mixing block in the table entry: with it the entry's 256 bytes are full.
+struct FvWidePcg {
+  double tol;
+  long long* stats;                         // LDC_FV_WIDE_PRESSURE_SCRATCH_LEN words: iterations, solves, cap hits, last count
+};
+static_assert(sizeof(FvWidePcg) == 16, "the pressure block");
+
 struct FvWideEntry {
   FvWideArgs a;
   FvWideMix m;
-  char pad[LDC_FV_WIDE_BATCH_ENTRY_BYTES - sizeof(FvWideArgs) - sizeof(FvWideMix)];
+  FvWidePcg x;
 };
 static_assert(sizeof(FvWideEntry) == LDC_FV_WIDE_BATCH_ENTRY_BYTES && sizeof(FvWideArgs) == 208, "table entry");
 static_assert(LDC_FV_WIDE_BATCH_MAX <= 1 << 15 && LDC_FV_WIDE_GEMM_GROUPS(LDC_FV_WIDE_MAX_N, LDC_FV_WIDE_MAX_N) <= 1 << 16,
@@ -493,6 +507,9 @@ __device__ __forceinline__ void wide_record(const FvWideArgs& a, double* lds) {
 // ---- 8. Anderson mixing behind `record`, for a trial that has it attached: push | mix | close
 #include "ldc_fv_wide_anderson.inc"
 
+// ---- 9. the consistent pressure equation: the launches that replace faces | gemm x 4 and fluxvort
+#include "ldc_fv_wide_pressure.inc"
+
 // ---- the kernels: every phase for a lone trial (arguments by value, g = blockIdx.x) and for a batch (the table)
 #define WIDE_LDS __shared__ double lds[kWW * kWS]
 // the trial and the work-group of this block of a batch launch, from a block map / for one work-group per trial
@@ -568,6 +585,57 @@ __global__ __launch_bounds__(64) void fv_wide_b_mix_close(FvWideTable t) {
   wide_mix_close(a, t.entries[blockIdx.x].m);
 }
 
+// the consistent pressure equation.  Lone: the handle's block by value.  Batch: the block of the entry; `faces` and
+// `fluxvort` take the reference's body for a reference trial, whose four GEMMs of the exact solve skip the other kind.
+#define WIDE_PCG const FvWidePcg& x = t.entries[m_ >> 16].x
+__global__ __launch_bounds__(kWT) void fv_wide_pcg_faces(FvWideArgs a, int par) { WIDE_LDS; wide_pcg_faces(a, blockIdx.x, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_pcg_faces(FvWideTable t, int par) {
+  WIDE_LDS;
+  WIDE_MAPPED(sweep);
+  if (a.pmax) wide_pcg_faces(a, g, par, lds);
+  else wide_faces(a, g, par, lds);
+}
+template <bool FIRST, bool SCALE>
+__global__ __launch_bounds__(kWT) void fv_wide_b_pcg_refgemm(FvWideTable t, int which, int par) {
+  WIDE_LDS;
+  WIDE_MAPPED(gemm);
+  if (a.pmax) return;
+  wide_gemm<FIRST, SCALE>(a, g, wide_gemm_of(a.d, which), par, lds);
+}
+__global__ __launch_bounds__(kWT) void fv_wide_pcg_init(FvWideArgs a, int par) { WIDE_LDS; wide_pcg_init(a, blockIdx.x, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_pcg_init(FvWideTable t, int par) { WIDE_LDS; WIDE_MAPPED(sweep); wide_pcg_init(a, g, par, lds); }
+template <bool HEAD, bool SCALE>
+__global__ __launch_bounds__(kWT) void fv_wide_pcg_gemm(FvWideArgs a, FvWidePcg x, FvWideGemm gd, int it, int par) {
+  WIDE_LDS;
+  wide_pcg_gemm<HEAD, SCALE>(a, x, blockIdx.x, gd, it, par, lds);
+}
+template <bool HEAD, bool SCALE>
+__global__ __launch_bounds__(kWT) void fv_wide_b_pcg_gemm(FvWideTable t, int which, int it, int par) {
+  WIDE_LDS;
+  WIDE_MAPPED(gemm);
+  WIDE_PCG;
+  wide_pcg_gemm<HEAD, SCALE>(a, x, g, wide_pcg_gemm_of(a.d, which), it, par, lds);
+}
+__global__ __launch_bounds__(kWT) void fv_wide_pcg_rz(FvWideArgs a, int par) { WIDE_LDS; wide_pcg_rz(a, blockIdx.x, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_pcg_rz(FvWideTable t, int par) { WIDE_LDS; WIDE_MAPPED(sweep); wide_pcg_rz(a, g, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_pcg_ap(FvWideArgs a, int it, int par) { WIDE_LDS; wide_pcg_ap(a, blockIdx.x, it, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_pcg_ap(FvWideTable t, int it, int par) { WIDE_LDS; WIDE_MAPPED(sweep); wide_pcg_ap(a, g, it, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_pcg_xr(FvWideArgs a, int it, int par) { WIDE_LDS; wide_pcg_xr(a, blockIdx.x, it, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_pcg_xr(FvWideTable t, int it, int par) { WIDE_LDS; WIDE_MAPPED(sweep); wide_pcg_xr(a, g, it, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_pcg_finish(FvWideArgs a, FvWidePcg x, int nb, int par) { WIDE_LDS; wide_pcg_finish(a, x, nb, par, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_pcg_finish(FvWideTable t, int nb, int par) {
+  WIDE_LDS;
+  WIDE_SINGLE;
+  wide_pcg_finish(a, t.entries[blockIdx.x].x, nb, par, lds);
+}
+__global__ __launch_bounds__(kWT) void fv_wide_pcg_fluxvort(FvWideArgs a) { WIDE_LDS; wide_pcg_fluxvort(a, blockIdx.x, lds); }
+__global__ __launch_bounds__(kWT) void fv_wide_b_pcg_fluxvort(FvWideTable t) {
+  WIDE_LDS;
+  WIDE_MAPPED(sweep);
+  if (a.pmax) wide_pcg_fluxvort(a, g, lds);
+  else wide_fluxvort(a, g, lds);
+}
+
 std::mutex g_wide_mutex;
 hipStream_t g_wide_stream[64] = {};
 
@@ -596,7 +664,8 @@ hipError_t wide_copy_now(void* dst, const void* src, size_t bytes, hipMemcpyKind
   return e != hipSuccess ? e : w;
 }
 
-// the captured iterations of a handle, lone or batch: (BiCGSTAB iterations, the iteration's graph), kept until destroy
+// the captured iterations of a handle, lone or batch: (BiCGSTAB iterations | CG iterations << 16, the iteration's graph),
+// kept until destroy
 struct WideGraphs {
   std::vector<std::pair<int, hipGraphExec_t>> graphs;
   hipEvent_t done = nullptr;                 // behind the last graph launch: no graph is destroyed in flight
@@ -612,6 +681,8 @@ struct ldc_fv_wide {
                                              // ldc_fv_wide_launches reads nothing behind these first 216 bytes
   FvWideMix m;                               // ldc_fv_wide_set_anderson; all zero: no mixing
   WideGraphs gs;
+  FvWidePcg x;                               // ldc_fv_wide_set_pressure (a.pmax > 0: in use).  Behind gs: nothing in front
+  int pbudget;                               // of it moves, and only a handle with a.pmax > 0 is read this far
 };
 static_assert(sizeof(FvWideArgs) + sizeof(int) + 2 * sizeof(short) == 216, "the head of a handle");
 
@@ -620,8 +691,10 @@ struct ldc_fv_wide_batch {
   int rec_cap[LDC_FV_WIDE_BATCH_MAX];
   int sweep_groups, gemm_groups;             // work-groups of a cell sweep and of a GEMM launch
   int mixing;                                // some trial has mixing attached: every chain ends on the mixing launches
+  int pressure;                              // some trial has the consistent pressure equation: the chain carries both kinds
   FvWideTable t;                             // (pointers into the caller's device buffer)
   WideGraphs gs;
+  int pmax, pbudget;                         // pressure_max_iters of those trials (one value), the CG launches of an enqueue
 };
 
 namespace {
@@ -633,8 +706,9 @@ namespace {
     if (e_ != hipSuccess) return (int)e_;                                            \
   } while (0)
 
-// the launches of ONE iteration with `nb` BiCGSTAB iterations; `par` alternates launch by launch
-int wide_iteration(const ldc_fv_wide* h, int nb, hipStream_t st) {
+// the launches of ONE iteration with `nb` BiCGSTAB iterations and, for a trial with the consistent pressure equation, `np`
+// CG iterations; `par` alternates launch by launch
+int wide_iteration(const ldc_fv_wide* h, int nb, int np, hipStream_t st) {
   const FvWideArgs& a = h->a;
   const FvDesc& d = a.d;
   const int G = a.G, gg = (int)LDC_FV_WIDE_GEMM_GROUPS(d.nx, d.ny);
@@ -648,13 +722,31 @@ int wide_iteration(const ldc_fv_wide* h, int nb, hipStream_t st) {
     WIDE_LAUNCH(fv_wide_bicg_x, G, kWT, a, it, par); par ^= 1;
   }
   WIDE_LAUNCH(fv_wide_linfinish, 1, kWT, a, nb, par); par ^= 1;
-  WIDE_LAUNCH(fv_wide_faces, G, kWT, a, par); par ^= 1;
-  WIDE_LAUNCH((fv_wide_gemm<true, false>), gg, kWT, a, wide_gemm_of(d, 0), par);
-  WIDE_LAUNCH((fv_wide_gemm<false, true>), gg, kWT, a, wide_gemm_of(d, 1), par);
-  WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, wide_gemm_of(d, 2), par);
-  WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, wide_gemm_of(d, 3), par);
-  WIDE_LAUNCH(fv_wide_correct, G, kWT, a);
-  WIDE_LAUNCH(fv_wide_fluxvort, G, kWT, a);
+  if (a.pmax == 0) {
+    WIDE_LAUNCH(fv_wide_faces, G, kWT, a, par); par ^= 1;
+    WIDE_LAUNCH((fv_wide_gemm<true, false>), gg, kWT, a, wide_gemm_of(d, 0), par);
+    WIDE_LAUNCH((fv_wide_gemm<false, true>), gg, kWT, a, wide_gemm_of(d, 1), par);
+    WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, wide_gemm_of(d, 2), par);
+    WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, wide_gemm_of(d, 3), par);
+    WIDE_LAUNCH(fv_wide_correct, G, kWT, a);
+    WIDE_LAUNCH(fv_wide_fluxvort, G, kWT, a);
+  } else {
+    const FvWidePcg& x = h->x;
+    WIDE_LAUNCH(fv_wide_pcg_faces, G, kWT, a, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_pcg_init, G, kWT, a, par); par ^= 1;
+    for (int it = 0; it < np; ++it) {
+      WIDE_LAUNCH((fv_wide_pcg_gemm<true, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 0), it, par); par ^= 1;
+      WIDE_LAUNCH((fv_wide_pcg_gemm<false, true>), gg, kWT, a, x, wide_pcg_gemm_of(d, 1), it, par);
+      WIDE_LAUNCH((fv_wide_pcg_gemm<false, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 2), it, par);
+      WIDE_LAUNCH((fv_wide_pcg_gemm<false, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 3), it, par);
+      WIDE_LAUNCH(fv_wide_pcg_rz, G, kWT, a, par); par ^= 1;
+      WIDE_LAUNCH(fv_wide_pcg_ap, G, kWT, a, it, par); par ^= 1;
+      WIDE_LAUNCH(fv_wide_pcg_xr, G, kWT, a, it, par); par ^= 1;
+    }
+    WIDE_LAUNCH(fv_wide_pcg_finish, 1, kWT, a, x, np, par);
+    WIDE_LAUNCH(fv_wide_correct, G, kWT, a);
+    WIDE_LAUNCH(fv_wide_pcg_fluxvort, G, kWT, a);
+  }
   WIDE_LAUNCH(fv_wide_sums, G, kWT, a);
   WIDE_LAUNCH(fv_wide_record, 1, kWT, a);
   if (h->mixing) {
@@ -665,8 +757,9 @@ int wide_iteration(const ldc_fv_wide* h, int nb, hipStream_t st) {
   return 0;
 }
 
-// the same chain for all trials of a batch: every launch carries the work-groups of all of them
-int wide_iteration(const ldc_fv_wide_batch* b, int nb, hipStream_t st) {
+// the same chain for all trials of a batch: every launch carries the work-groups of all of them.  With a trial of either
+// kind of pressure equation in it the chain has the launches of both, and a trial returns from those of the other kind.
+int wide_iteration(const ldc_fv_wide_batch* b, int nb, int np, hipStream_t st) {
   const FvWideTable& t = b->t;
   const int G = b->sweep_groups, gg = b->gemm_groups, n = b->n;
   int par = 0;
@@ -679,13 +772,34 @@ int wide_iteration(const ldc_fv_wide_batch* b, int nb, hipStream_t st) {
     WIDE_LAUNCH(fv_wide_b_bicg_x, G, kWT, t, it, par); par ^= 1;
   }
   WIDE_LAUNCH(fv_wide_b_linfinish, n, kWT, t, nb, par); par ^= 1;
-  WIDE_LAUNCH(fv_wide_b_faces, G, kWT, t, par); par ^= 1;
-  WIDE_LAUNCH((fv_wide_b_gemm<true, false>), gg, kWT, t, 0, par);
-  WIDE_LAUNCH((fv_wide_b_gemm<false, true>), gg, kWT, t, 1, par);
-  WIDE_LAUNCH((fv_wide_b_gemm<false, false>), gg, kWT, t, 2, par);
-  WIDE_LAUNCH((fv_wide_b_gemm<false, false>), gg, kWT, t, 3, par);
-  WIDE_LAUNCH(fv_wide_b_correct, G, kWT, t);
-  WIDE_LAUNCH(fv_wide_b_fluxvort, G, kWT, t);
+  if (!b->pressure) {
+    WIDE_LAUNCH(fv_wide_b_faces, G, kWT, t, par); par ^= 1;
+    WIDE_LAUNCH((fv_wide_b_gemm<true, false>), gg, kWT, t, 0, par);
+    WIDE_LAUNCH((fv_wide_b_gemm<false, true>), gg, kWT, t, 1, par);
+    WIDE_LAUNCH((fv_wide_b_gemm<false, false>), gg, kWT, t, 2, par);
+    WIDE_LAUNCH((fv_wide_b_gemm<false, false>), gg, kWT, t, 3, par);
+    WIDE_LAUNCH(fv_wide_b_correct, G, kWT, t);
+    WIDE_LAUNCH(fv_wide_b_fluxvort, G, kWT, t);
+  } else {
+    WIDE_LAUNCH(fv_wide_b_pcg_faces, G, kWT, t, par); par ^= 1;
+    WIDE_LAUNCH((fv_wide_b_pcg_refgemm<true, false>), gg, kWT, t, 0, par);
+    WIDE_LAUNCH((fv_wide_b_pcg_refgemm<false, true>), gg, kWT, t, 1, par);
+    WIDE_LAUNCH((fv_wide_b_pcg_refgemm<false, false>), gg, kWT, t, 2, par);
+    WIDE_LAUNCH((fv_wide_b_pcg_refgemm<false, false>), gg, kWT, t, 3, par);
+    WIDE_LAUNCH(fv_wide_b_pcg_init, G, kWT, t, par); par ^= 1;
+    for (int it = 0; it < np; ++it) {
+      WIDE_LAUNCH((fv_wide_b_pcg_gemm<true, false>), gg, kWT, t, 0, it, par); par ^= 1;
+      WIDE_LAUNCH((fv_wide_b_pcg_gemm<false, true>), gg, kWT, t, 1, it, par);
+      WIDE_LAUNCH((fv_wide_b_pcg_gemm<false, false>), gg, kWT, t, 2, it, par);
+      WIDE_LAUNCH((fv_wide_b_pcg_gemm<false, false>), gg, kWT, t, 3, it, par);
+      WIDE_LAUNCH(fv_wide_b_pcg_rz, G, kWT, t, par); par ^= 1;
+      WIDE_LAUNCH(fv_wide_b_pcg_ap, G, kWT, t, it, par); par ^= 1;
+      WIDE_LAUNCH(fv_wide_b_pcg_xr, G, kWT, t, it, par); par ^= 1;
+    }
+    WIDE_LAUNCH(fv_wide_b_pcg_finish, n, kWT, t, np, par);
+    WIDE_LAUNCH(fv_wide_b_correct, G, kWT, t);
+    WIDE_LAUNCH(fv_wide_b_pcg_fluxvort, G, kWT, t);
+  }
   WIDE_LAUNCH(fv_wide_b_sums, G, kWT, t);
   WIDE_LAUNCH(fv_wide_b_record, n, kWT, t);
   if (b->mixing) {
@@ -696,23 +810,25 @@ int wide_iteration(const ldc_fv_wide_batch* b, int nb, hipStream_t st) {
   return 0;
 }
 
-// Budgets above this are launched one by one: the graph of an iteration has 11 + 5 nb nodes (and the mixing chain's)
+// Budgets above this are launched one by one: the graph of an iteration has 11 + 5 nb nodes (and the mixing chain's, and
+// 7 np of the consistent pressure equation, whose budget has the same bound)
 constexpr int kWideGraphMaxNb = 64;
 
 // The graph of ONE iteration of `h` (a lone handle or a batch) with nb BiCGSTAB iterations: a linear chain captured on
 // this unit's private stream (relaxed mode: kernel launches only, no call elsewhere needs to be prohibited meanwhile),
 // instantiated once and kept.
 template <class Handle>
-int wide_graph(Handle* h, int nb, hipGraphExec_t* out) {
+int wide_graph(Handle* h, int nb, int np, hipGraphExec_t* out) {
+  const int key = nb | np << 16;
   for (const auto& g : h->gs.graphs)
-    if (g.first == nb) { *out = g.second; return 0; }
+    if (g.first == key) { *out = g.second; return 0; }
   std::lock_guard<std::mutex> lock(g_wide_mutex);
   hipStream_t cs = nullptr;
   hipError_t e = wide_stream(&cs);
   if (e != hipSuccess) return (int)e;
   e = hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed);
   if (e != hipSuccess) return (int)e;
-  const int rc = wide_iteration(h, nb, cs);
+  const int rc = wide_iteration(h, nb, np, cs);
   hipGraph_t g = nullptr;
   const hipError_t ce = hipStreamEndCapture(cs, &g);
   if (rc != 0 || ce != hipSuccess) {
@@ -723,18 +839,18 @@ int wide_graph(Handle* h, int nb, hipGraphExec_t* out) {
   const hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
   (void)hipGraphDestroy(g);
   if (ie != hipSuccess) return (int)ie;
-  h->gs.graphs.emplace_back(nb, exec);
+  h->gs.graphs.emplace_back(key, exec);
   *out = exec;
   return 0;
 }
 
-// `chains` iterations of `h` at nb BiCGSTAB iterations each on `st`, behind the `begin` launch the caller has made: the
-// handle's graph replayed, or every kernel on its own
+// `chains` iterations of `h` at nb BiCGSTAB iterations (and np CG iterations) each on `st`, behind the `begin` launch the
+// caller has made: the handle's graph replayed, or every kernel on its own
 template <class Handle>
-int wide_chains(Handle* h, int chains, int nb, hipStream_t st) {
+int wide_chains(Handle* h, int chains, int nb, int np, hipStream_t st) {
   hipGraphExec_t exec = nullptr;
-  if (h->graph && nb <= kWideGraphMaxNb) {
-    const int rc = wide_graph(h, nb, &exec);
+  if (h->graph && nb <= kWideGraphMaxNb && np <= kWideGraphMaxNb) {
+    const int rc = wide_graph(h, nb, np, &exec);
     if (rc != 0) return rc;
     if (!h->gs.done) {
       const hipError_t e = hipEventCreateWithFlags(&h->gs.done, hipEventDisableTiming);
@@ -746,7 +862,7 @@ int wide_chains(Handle* h, int chains, int nb, hipStream_t st) {
       const hipError_t e = hipGraphLaunch(exec, st);
       if (e != hipSuccess) return (int)e;
     } else {
-      const int rc = wide_iteration(h, nb, st);
+      const int rc = wide_iteration(h, nb, np, st);
       if (rc != 0) return rc;
     }
   }
@@ -769,6 +885,11 @@ void wide_graphs_free(WideGraphs& gs) {
   gs.graphs.clear();
 }
 
+// the CG iterations an enqueue of `h` carries per SIMPLE iteration (0: no trial with the consistent pressure equation)
+inline int wide_np(const ldc_fv_wide* h) { return h->a.pmax == 0 ? 0 : (h->pbudget < h->a.pmax ? h->pbudget : h->a.pmax); }
+inline int wide_np(const ldc_fv_wide_batch* b) { return !b->pressure ? 0 : (b->pbudget < b->pmax ? b->pbudget : b->pmax); }
+inline int wide_lin(int lin_budget, int maxit) { return lin_budget < maxit ? lin_budget : maxit; }
+
 }  // namespace
 
 extern "C" {
@@ -788,6 +909,9 @@ int ldc_fv_wide_create(const struct ldc_fv_problem* pr, double* scratch, int64_t
   s->a.d = h;
   s->a.scr = scratch;
   s->a.G = (int)LDC_FV_WIDE_GROUPS(pr->nx, pr->ny);
+  s->a.pmax = 0;
+  s->x = FvWidePcg{};
+  s->pbudget = LDC_FV_WIDE_PRESSURE_BUDGET_DEFAULT;
   s->device = dev;
   s->graph = LDC_FV_WIDE_GRAPH_DEFAULT;
   s->mixing = 0;
@@ -832,6 +956,31 @@ int ldc_fv_wide_set_anderson(ldc_fv_wide* h, const struct ldc_fv_anderson* acc, 
   return 0;
 }
 
+int ldc_fv_wide_set_pressure(ldc_fv_wide* h, const struct ldc_fv_pressure* cfg, double* scratch, int64_t scratch_len) {
+  if (!h) return LDC_E_STATE;
+  int pmax = 0;
+  FvWidePcg x = {};
+  if (cfg && cfg->mode != LDC_FV_PRESSURE_REFERENCE) {
+    if (cfg->mode != LDC_FV_PRESSURE_CONSISTENT || cfg->max_iters < 1 || !(cfg->tol > 0 && cfg->tol < 1)) return LDC_E_ARG;
+    if (!scratch || scratch_len < LDC_FV_WIDE_PRESSURE_SCRATCH_LEN) return LDC_E_ARG;
+    pmax = cfg->max_iters;
+    x.tol = cfg->tol;
+    x.stats = reinterpret_cast<long long*>(scratch);
+  }
+  if (h->a.pmax == 0 && pmax == 0) return 0;                // (a plain handle stays as it is, and as short as it is)
+  wide_graphs_free(h->gs);
+  h->a.pmax = pmax;
+  h->x = x;
+  return 0;
+}
+
+int ldc_fv_wide_set_pressure_budget(ldc_fv_wide* h, int budget) {
+  if (!h) return LDC_E_STATE;
+  if (budget < 1 || h->a.pmax == 0) return LDC_E_ARG;
+  h->pbudget = budget;
+  return 0;
+}
+
 int ldc_fv_wide_enqueue(ldc_fv_wide* h, int n_iters, int lin_budget, void* stream) {
   if (!h) return LDC_E_STATE;
   if (n_iters < 1 || n_iters > h->a.d.rec_cap || lin_budget < 1) return LDC_E_ARG;
@@ -840,12 +989,13 @@ int ldc_fv_wide_enqueue(ldc_fv_wide* h, int n_iters, int lin_budget, void* strea
   if (dev != h->device) return LDC_E_STATE;
   hipStream_t st = as_stream(stream);
   WIDE_LAUNCH(fv_wide_begin, 1, 64, h->a, n_iters);
-  return wide_chains(h, n_iters, lin_budget < h->a.d.maxit ? lin_budget : h->a.d.maxit, st);
+  return wide_chains(h, n_iters, wide_lin(lin_budget, h->a.d.maxit), wide_np(h), st);
 }
 
 int ldc_fv_wide_launches(const ldc_fv_wide* h, int lin_budget) {
   if (!h || lin_budget < 1) return LDC_E_ARG;
-  return 11 + 5 * (lin_budget < h->a.d.maxit ? lin_budget : h->a.d.maxit) + (h->mixing ? kWideMixLaunches : 0);
+  return 11 + 5 * wide_lin(lin_budget, h->a.d.maxit) + (h->mixing ? kWideMixLaunches : 0)
+         + (h->a.pmax ? 2 - 4 + kWidePcgLaunches * wide_np(h) : 0);      // init and pfinish come, the exact solve's GEMMs go
 }
 
 int ldc_fv_wide_status(ldc_fv_wide* h) {
@@ -865,10 +1015,15 @@ int ldc_fv_wide_batch_create(ldc_fv_wide* const* hs, int n, void* table, int64_t
   for (int q = 0; q < n; ++q)
     if (!hs[q]) return LDC_E_STATE;
   int64_t sweep = 0, gemm = 0;
+  int pmax = 0;                               // pressure_max_iters of the trials with the consistent equation: one value
   for (int q = 0; q < n; ++q) {
     for (int r = 0; r < q; ++r)
       if (hs[r] == hs[q]) return LDC_E_ARG;
     if (hs[q]->a.d.maxit != hs[0]->a.d.maxit) return LDC_E_ARG;
+    if (hs[q]->a.pmax) {
+      if (pmax && hs[q]->a.pmax != pmax) return LDC_E_ARG;
+      pmax = hs[q]->a.pmax;
+    }
     sweep += hs[q]->a.G;
     gemm += LDC_FV_WIDE_GEMM_GROUPS(hs[q]->a.d.nx, hs[q]->a.d.ny);
   }
@@ -882,6 +1037,7 @@ int ldc_fv_wide_batch_create(ldc_fv_wide* const* hs, int n, void* table, int64_t
   if (!b) return LDC_E_STATE;
   b->n = n; b->maxit = hs[0]->a.d.maxit; b->device = dev; b->graph = LDC_FV_WIDE_GRAPH_DEFAULT;
   b->sweep_groups = (int)sweep; b->gemm_groups = (int)gemm; b->mixing = 0;
+  b->pressure = 0; b->pmax = pmax; b->pbudget = LDC_FV_WIDE_PRESSURE_BUDGET_DEFAULT;
   // the image of the table: entries, the block map of the sweeps, that of the GEMMs
   std::vector<char> image((size_t)LDC_FV_WIDE_BATCH_TABLE_LEN(n, sweep, gemm), 0);
   FvWideEntry* entries = reinterpret_cast<FvWideEntry*>(image.data());
@@ -891,6 +1047,7 @@ int ldc_fv_wide_batch_create(ldc_fv_wide* const* hs, int n, void* table, int64_t
     entries[q].a = hs[q]->a;
     entries[q].m = hs[q]->m;
     if (hs[q]->mixing) b->mixing = 1;
+    if (hs[q]->a.pmax) { entries[q].x = hs[q]->x; b->pressure = 1; }
     b->rec_cap[q] = hs[q]->a.d.rec_cap;
     const int gq = (int)LDC_FV_WIDE_GEMM_GROUPS(hs[q]->a.d.nx, hs[q]->a.d.ny);
     for (int g = 0; g < hs[q]->a.G; ++g) *smap++ = (uint32_t)q << 16 | (uint32_t)g;
@@ -939,12 +1096,20 @@ int ldc_fv_wide_batch_enqueue(ldc_fv_wide_batch* b, const int32_t* n_iters, int 
   if (dev != b->device) return LDC_E_STATE;
   hipStream_t st = as_stream(stream);
   WIDE_LAUNCH(fv_wide_b_begin, b->n, 64, b->t, quotas);
-  return wide_chains(b, chains, lin_budget < b->maxit ? lin_budget : b->maxit, st);
+  return wide_chains(b, chains, wide_lin(lin_budget, b->maxit), wide_np(b), st);
+}
+
+int ldc_fv_wide_batch_set_pressure_budget(ldc_fv_wide_batch* b, int budget) {
+  if (!b) return LDC_E_STATE;
+  if (budget < 1) return LDC_E_ARG;
+  b->pbudget = budget;
+  return 0;
 }
 
 int ldc_fv_wide_batch_launches(const ldc_fv_wide_batch* b, int lin_budget) {
   if (!b || lin_budget < 1) return LDC_E_ARG;
-  return 11 + 5 * (lin_budget < b->maxit ? lin_budget : b->maxit) + (b->mixing ? kWideMixLaunches : 0);
+  return 11 + 5 * wide_lin(lin_budget, b->maxit) + (b->mixing ? kWideMixLaunches : 0)
+         + (b->pressure ? 2 + kWidePcgLaunches * wide_np(b) : 0);        // (the chain keeps the exact solve's four GEMMs)
 }
 
 }  // extern "C"

@@ -22,6 +22,12 @@ WIDE_MAX_N = 1024
 WIDE_BATCH_MAX, WIDE_BATCH_ENTRY_BYTES = 256, 256        # LDC_FV_WIDE_BATCH_MAX, LDC_FV_WIDE_BATCH_ENTRY_BYTES
 WIDE_ANDERSON_LAUNCHES = 3     # LDC_FV_WIDE_ANDERSON_LAUNCHES: push | mix | close behind every iteration
 E_BUDGET = -6                  # ldc_fv_wide_status: the last enqueue ran out of BiCGSTAB launches (LDC_FV_WIDE_E_BUDGET)
+# the consistent pressure equation of a chip or shared trial (ldc_fv_wide_set_pressure): modes, launches of one CG iteration,
+# the default budget, the statistics words, and the values of the overflow word (which budget was too small)
+PRESSURE_MODES = {"reference": 0, "consistent": 1}
+WIDE_PRESSURE_LAUNCHES, WIDE_PRESSURE_BUDGET_DEFAULT, WIDE_PRESSURE_SCRATCH_LEN = 7, 12, 4
+PSTAT_ITERS, PSTAT_SOLVES, PSTAT_CAPS, PSTAT_LAST = range(4)
+OVERFLOW_LINEAR, OVERFLOW_PRESSURE = 1, 2
 CTRL_DONE, CTRL_ITER, CTRL_NAN, CTRL_GIVEUP, CTRL_LIN_ITERS, CTRL_SOLVES = range(6)
 # slots of a result block of ldc_fv_post_enqueue (LDC_FV_POST_*)
 (POST_PSI_MIN, POST_OMEGA_CENTER, POST_OMEGA_MAX, POST_PSI_BR, POST_PSI_BL, POST_PSI_TL, POST_PSI_MIN_CELL,
@@ -55,6 +61,11 @@ class Anderson(C.Structure):
     _fields_ = [("depth", C.c_int32), ("start", C.c_int32), ("hist", _dp), ("hist_len", C.c_int64), ("astate", _dp)]
 
 
+class Pressure(C.Structure):
+    """Mirror of ``struct ldc_fv_pressure`` -- keep field order in sync with the header."""
+    _fields_ = [("mode", C.c_int32), ("max_iters", C.c_int32), ("tol", C.c_double)]
+
+
 # every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
            "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
@@ -62,7 +73,8 @@ EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue"
            "ldc_fv_wide_launches", "ldc_fv_wide_status", "ldc_fv_wide_set_graph", "ldc_fv_wide_batch_create",
            "ldc_fv_wide_batch_destroy", "ldc_fv_wide_batch_enqueue", "ldc_fv_wide_batch_set_graph",
            "ldc_fv_wide_batch_launches", "ldc_fv_wide_post_enqueue", "ldc_fv_wide_post_launches",
-           "ldc_fv_wide_prolong_enqueue", "ldc_fv_wide_set_anderson")
+           "ldc_fv_wide_prolong_enqueue", "ldc_fv_wide_set_anderson", "ldc_fv_wide_set_pressure",
+           "ldc_fv_wide_set_pressure_budget", "ldc_fv_wide_batch_set_pressure_budget")
 
 _bound = None
 
@@ -146,6 +158,9 @@ def lib() -> C.CDLL:
         L.ldc_fv_wide_post_launches.argtypes = [_dp]
         L.ldc_fv_wide_prolong_enqueue.argtypes = [_dp, _dp, _dp]
         L.ldc_fv_wide_set_anderson.argtypes = [_dp, C.POINTER(Anderson), _dp, C.c_int64]
+        L.ldc_fv_wide_set_pressure.argtypes = [_dp, C.POINTER(Pressure), _dp, C.c_int64]
+        L.ldc_fv_wide_set_pressure_budget.argtypes = [_dp, C.c_int]
+        L.ldc_fv_wide_batch_set_pressure_budget.argtypes = [_dp, C.c_int]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -223,3 +238,12 @@ def wide_set_anderson(wide, block, scratch_ptr: int = None, scratch_len: int = 0
     scratch) or detach it (``None`` or depth 0).  A batch copies the block when it is created: attach first."""
     check(lib().ldc_fv_wide_set_anderson(wide, C.byref(block) if block is not None else None, _dp(scratch_ptr),
                                          int(scratch_len)), "ldc_fv_wide_set_anderson")
+
+
+def wide_set_pressure(wide, mode: str, tol: float, max_iters: int, stats_ptr: int = None,
+                      stats_len: int = WIDE_PRESSURE_SCRATCH_LEN) -> None:
+    """The pressure equation of an ``ldc_fv_wide`` handle: ``"reference"`` or ``"consistent"`` (CG to ``tol``, at most
+    ``max_iters`` iterations, statistics in the caller's ``stats_len`` int64 words).  A batch copies the block when it is
+    created: set it first."""
+    cfg = Pressure(mode=PRESSURE_MODES[mode], max_iters=int(max_iters), tol=float(tol))
+    check(lib().ldc_fv_wide_set_pressure(wide, C.byref(cfg), _dp(stats_ptr), int(stats_len)), "ldc_fv_wide_set_pressure")

@@ -323,6 +323,94 @@ def advance_batch_with_budget(step, starts, ks, budgets, max_lin_iters):
             for b, (latch, nan), total, budget, r in zip(blocks, flags, totals, budgets, retries)]
 
 
+def advance_with_budgets(step, start, k, budgets, caps):
+    """``advance_with_budget`` for a trial with the consistent pressure equation, whose iterations carry two fixed numbers
+    of launches: ``budgets`` = (BiCGSTAB iterations, CG iterations of the pressure solve) per SIMPLE iteration, ``caps`` =
+    (max_lin_iters, pressure_max_iters).
+
+    ``step(m, linear_budget, pressure_budget)`` enqueues up to ``m`` iterations, waits, and returns (rows of the iterations
+    it completed, latch, nan, iteration count, overflow): overflow ``OVERFLOW_LINEAR`` (1) when a momentum solve of the next
+    iteration needs more than its budget, ``OVERFLOW_PRESSURE`` (2) when its pressure solve does; either way that iteration
+    has changed nothing, and the rest is enqueued again with twice THAT budget, at most its cap.  Returns (rows, latch, nan,
+    iteration count, budgets now, retries per budget)."""
+    import numpy as np
+    budgets, retries = [int(b) for b in budgets], [0, 0]
+    blocks, total = [], int(start)
+    latch = nan = 0
+    while total - start < k:
+        rows, latch, nan, new_total, overflow = step(k - (total - start), budgets[0], budgets[1])
+        if len(rows) != new_total - total:
+            raise RuntimeError(f"{len(rows)} record rows for iterations {total} ... {new_total}")
+        blocks.append(rows)
+        total = int(new_total)
+        if latch or nan:
+            break
+        if overflow:
+            if overflow not in (F.OVERFLOW_LINEAR, F.OVERFLOW_PRESSURE):
+                raise RuntimeError(f"overflow word {overflow}")
+            which = overflow - 1
+            if budgets[which] >= caps[which]:
+                raise RuntimeError(f"{('linear', 'pressure')[which]} budget {budgets[which]} >= its cap {caps[which]} "
+                                   f"reported an overflow")
+            budgets[which] = min(2 * budgets[which], int(caps[which]))
+            retries[which] += 1
+        elif total - start < k:
+            raise RuntimeError("device loop made no progress")
+    rows = np.concatenate(blocks, axis=0) if blocks else np.zeros((0, F.REC_LEN))
+    return rows, int(latch), int(nan), total, tuple(budgets), tuple(retries)
+
+
+def advance_batch_with_budgets(step, starts, ks, budgets, caps):
+    """``advance_batch_with_budget`` with the two budgets of ``advance_with_budgets``: ``budgets[q]`` = (BiCGSTAB, CG) of trial
+    q, ``caps`` = (max_lin_iters, pressure_max_iters).  ``step(quotas, linear_budget, pressure_budget)`` returns per trial
+    (rows, latch, nan, iteration count, overflow code).  A call carries the largest budget of either kind among its trials; a
+    trial that overflowed takes twice the CALL's budget of the kind it ran out of and is enqueued again beside the others
+    that overflowed, quota 0 for everyone else.  Returns per trial (rows, latch, nan, iteration count, budgets now, retries
+    per budget)."""
+    import numpy as np
+    n = len(starts)
+    starts = [int(x) for x in starts]
+    totals, budgets, retries = list(starts), [[int(b) for b in bq] for bq in budgets], [[0, 0] for _ in range(n)]
+    blocks, flags = [[] for _ in range(n)], [(0, 0)] * n
+    todo = [q for q in range(n) if ks[q] > 0]
+    while todo:
+        quotas = [0] * n
+        for q in todo:
+            quotas[q] = int(ks[q]) - (totals[q] - starts[q])
+        call = [max(budgets[q][w] for q in todo) for w in range(2)]
+        out = step(list(quotas), call[0], call[1])
+        if len(out) != n:
+            raise RuntimeError("one result per trial expected")
+        again = []
+        for q, (rows, latch, nan, new_total, overflow) in enumerate(out):
+            if len(rows) != new_total - totals[q]:
+                raise RuntimeError(f"trial {q}: {len(rows)} record rows for iterations {totals[q]} ... {new_total}")
+            if quotas[q] == 0:
+                if new_total != totals[q]:
+                    raise RuntimeError(f"trial {q} had quota 0 and went from iteration {totals[q]} to {new_total}")
+                continue
+            blocks[q].append(rows)
+            totals[q] = int(new_total)
+            flags[q] = (int(latch), int(nan))
+            if latch or nan:
+                continue
+            if overflow:
+                if overflow not in (F.OVERFLOW_LINEAR, F.OVERFLOW_PRESSURE):
+                    raise RuntimeError(f"trial {q}: overflow word {overflow}")
+                which = overflow - 1
+                if call[which] >= caps[which]:
+                    raise RuntimeError(f"trial {q}: {('linear', 'pressure')[which]} budget {call[which]} >= its cap "
+                                       f"{caps[which]} reported an overflow")
+                budgets[q][which] = min(2 * call[which], int(caps[which]))
+                retries[q][which] += 1
+                again.append(q)
+            elif totals[q] - starts[q] < ks[q]:
+                raise RuntimeError(f"trial {q}: device loop made no progress")
+        todo = again
+    return [(np.concatenate(b, axis=0) if b else np.zeros((0, F.REC_LEN)), latch, nan, total, tuple(bq), tuple(r))
+            for b, (latch, nan), total, bq, r in zip(blocks, flags, totals, budgets, retries)]
+
+
 class SharedBatch:
     """``solvers`` (FVSolvers with ``mapping="shared"`` on one device, at most ``WIDE_BATCH_MAX``) as ONE batch object of
     the library (``ldc_fv_wide_batch_*``): every phase launch carries the work-groups of all of them, and an enqueue gives
@@ -353,15 +441,18 @@ class SharedBatch:
             F.lib().ldc_fv_wide_batch_destroy(self.handle)
             self.handle = None
 
-    def _step(self, quotas, budget):
+    def _step(self, quotas, budget, pressure_budget=None):
         """ONE enqueue and ONE wait, then one copy each of the control words, the overflow words and the new record rows
-        (``advance_batch_with_budget``'s step)."""
+        (``advance_batch_with_budget``'s step; with a ``pressure_budget``, ``advance_batch_with_budgets``'s)."""
         import torch
         from solvers.spectral import ldc_lib
         from solvers.spectral.chunks import _words
         dev, ss = self.device, self.solvers
         index = torch.cuda.current_device() if dev.index is None else dev.index
         with torch.cuda.device(dev):
+            if pressure_budget is not None:
+                F.check(F.lib().ldc_fv_wide_batch_set_pressure_budget(self.handle, int(pressure_budget)),
+                        "ldc_fv_wide_batch_set_pressure_budget")
             with ldc_lib.resident_lock(index):
                 F.wide_batch_enqueue(self.handle, quotas, budget, torch.cuda.current_stream(dev).cuda_stream)
                 ctrl = _words([s.t["ctrl"] for s in ss])          # (synchronises the stream)
@@ -388,6 +479,16 @@ class SharedBatch:
             raise RuntimeError("a trial of a shared batch has a new device handle: the batch's table is out of date")
         with torch.cuda.device(self.device):
             self._totals = [int(t) for t in _words([s.t["ctrl"] for s in ss])[:, F.CTRL_ITER]]
+        consistent = [s for s in ss if s.consistent]
+        if consistent:      # (ldc_fv_wide_batch_create has seen to it that they share pressure_max_iters)
+            out = advance_batch_with_budgets(self._step, list(self._totals), [int(k) for k in ks],
+                                             [(s.linear_budget, s.pressure_budget) for s in ss],
+                                             (LINEAR_MAX_ITERATIONS, int(consistent[0].params.pressure_max_iters)))
+            for s, (_, _, _, _, budgets, retries) in zip(ss, out):
+                s.linear_budget, s.pressure_budget = budgets
+                s.linear_budget_retries += retries[0]
+                s.pressure_budget_retries += retries[1]
+            return [(rows, latch, nan, total) for rows, latch, nan, total, _, _ in out]
         out = advance_batch_with_budget(self._step, list(self._totals), [int(k) for k in ks],
                                         [s.linear_budget for s in ss], LINEAR_MAX_ITERATIONS)
         for s, (_, _, _, _, budget, retries) in zip(ss, out):
@@ -427,6 +528,18 @@ class FVSolver(LidDrivenCavitySolver):
             raise ValueError(f"mapping={p.mapping!r}: 'cu', 'chip' or 'shared'")
         if int(p.linear_budget) < 1:
             raise ValueError(f"linear_budget={p.linear_budget}: BiCGSTAB iterations per SIMPLE iteration, at least 1")
+        if p.pressure_equation not in F.PRESSURE_MODES:
+            raise ValueError(f"pressure_equation={p.pressure_equation!r}: 'reference' or 'consistent'")
+        self.consistent = p.pressure_equation == "consistent"
+        if self.consistent and p.mapping == "cu":
+            raise ValueError("pressure_equation='consistent' with mapping='cu': the consistent pressure equation is solved "
+                             "by launches over the whole chip, give the trial mapping=chip (or mapping=shared)")
+        if not 0.0 < float(p.pressure_tol) < 1.0:
+            raise ValueError(f"pressure_tol={p.pressure_tol}: a relative residual, between 0 and 1")
+        if int(p.pressure_max_iters) < 1:
+            raise ValueError(f"pressure_max_iters={p.pressure_max_iters}: CG iterations per pressure solve, at least 1")
+        if int(p.pressure_budget) < 1:
+            raise ValueError(f"pressure_budget={p.pressure_budget}: CG iterations per SIMPLE iteration, at least 1")
         self.shared = p.mapping == "shared"       # the phase kernels of csrc/ldc_fv_wide.hip: a launch of its own per
         self.chip = p.mapping == "chip" or self.shared        # phase ("chip") or one for all trials of a batch ("shared")
         nx, ny = int(p.nx), int(p.ny)
@@ -488,8 +601,12 @@ class FVSolver(LidDrivenCavitySolver):
             self.t["mix_scratch"] = torch.zeros(F.wide_anderson_scratch_len(nx, ny, int(p.anderson_depth)), **f64)
         if self.chip:
             self.t["scratch"] = torch.zeros(F.wide_scratch_len(nx, ny), **f64)
+        if self.consistent:                       # CG iterations, solves, cap hits, the last solve's count (pfinish)
+            self.t["pstats"] = torch.zeros(F.WIDE_PRESSURE_SCRATCH_LEN, dtype=torch.int64, device=self.device)
         self.linear_budget = int(p.linear_budget)        # grows when a solve overflows it (advance_with_budget)
         self.linear_budget_retries = 0
+        self.pressure_budget = int(p.pressure_budget)    # likewise (advance_with_budgets)
+        self.pressure_budget_retries = 0
         self._handle = None
         self._wide = None
         self._batch1 = None                      # a "shared" trial alone: the batch object of one it is advanced through
@@ -527,6 +644,10 @@ class FVSolver(LidDrivenCavitySolver):
                 self._wide = h
                 if self.wide_graph is not None:
                     F.check(F.lib().ldc_fv_wide_set_graph(h, int(self.wide_graph)), "ldc_fv_wide_set_graph")
+                if self.consistent:               # (likewise before the batch of one)
+                    F.wide_set_pressure(h, "consistent", float(self.params.pressure_tol),
+                                        int(self.params.pressure_max_iters), self.t["pstats"].data_ptr(),
+                                        self.t["pstats"].numel())
                 if self.mixed_chip:               # (before the batch of one below: a batch copies the block)
                     F.wide_set_anderson(h, self._anderson_block(), self.t["mix_scratch"].data_ptr(),
                                         self.t["mix_scratch"].numel())
@@ -603,8 +724,16 @@ class FVSolver(LidDrivenCavitySolver):
             self.t[name].copy_(torch.as_tensor(np.asarray(val, dtype=np.float64).ravel()))
         self.t["ctrl"].zero_()
         self.t["astate"].zero_()
-        self.linear_budget, self.linear_budget_retries = int(self.params.linear_budget), 0
+        self._reset_budgets()
         self._post = None
+
+    def _reset_budgets(self):
+        """The budgets of a new solve, and the statistics words of its pressure solves at zero."""
+        p = self.params
+        self.linear_budget, self.linear_budget_retries = int(p.linear_budget), 0
+        self.pressure_budget, self.pressure_budget_retries = int(p.pressure_budget), 0
+        if self.consistent:
+            self.t["pstats"].zero_()
 
     def state(self) -> dict:
         return {k: self.t[k].cpu().numpy().copy() for k in ("u", "v", "p", "mdot")}
@@ -612,10 +741,16 @@ class FVSolver(LidDrivenCavitySolver):
     def counters(self) -> dict:
         c = self.t["ctrl"].cpu().numpy()
         a = self.t["astate"].cpu().numpy()
-        return dict(done=int(c[F.CTRL_DONE]), iterations=int(c[F.CTRL_ITER]), nan=int(c[F.CTRL_NAN]),
-                    linear_giveups=int(c[F.CTRL_GIVEUP]), linear_iterations=int(c[F.CTRL_LIN_ITERS]),
-                    momentum_solves=int(c[F.CTRL_SOLVES]), anderson_fallbacks=int(a[F.ASTATE_FALLBACKS]),
-                    linear_budget_retries=int(self.linear_budget_retries))
+        out = dict(done=int(c[F.CTRL_DONE]), iterations=int(c[F.CTRL_ITER]), nan=int(c[F.CTRL_NAN]),
+                   linear_giveups=int(c[F.CTRL_GIVEUP]), linear_iterations=int(c[F.CTRL_LIN_ITERS]),
+                   momentum_solves=int(c[F.CTRL_SOLVES]), anderson_fallbacks=int(a[F.ASTATE_FALLBACKS]),
+                   linear_budget_retries=int(self.linear_budget_retries))
+        if self.consistent:
+            ps = self.t["pstats"].cpu().numpy()
+            out.update(pressure_iterations=int(ps[F.PSTAT_ITERS]), pressure_solves=int(ps[F.PSTAT_SOLVES]),
+                       pressure_caps=int(ps[F.PSTAT_CAPS]), pressure_last=int(ps[F.PSTAT_LAST]),
+                       pressure_budget_retries=int(self.pressure_budget_retries))
+        return out
 
     def step_debug(self, which=F.DBG) -> dict:
         """One iteration through ldc_fv_step_debug; returns the named intermediates (include/ldc_fv.h)."""
@@ -638,16 +773,20 @@ class FVSolver(LidDrivenCavitySolver):
         self._make_handle(tolerance)
         self.t["ctrl"].zero_()
         self.t["astate"].zero_()                 # (the mixing history starts over with the count: include/ldc_fv.h)
-        self.linear_budget, self.linear_budget_retries = int(self.params.linear_budget), 0
+        self._reset_budgets()
         self._post = None
 
-    def _wide_step(self, m: int, budget: int):
-        """One wide enqueue of up to ``m`` iterations at ``budget`` and ONE wait (``advance_with_budget``'s step)."""
+    def _wide_step(self, m: int, budget: int, pressure_budget: int = None):
+        """One wide enqueue of up to ``m`` iterations at ``budget`` and ONE wait (``advance_with_budget``'s step; with a
+        ``pressure_budget``, ``advance_with_budgets``'s: the overflow word then tells which budget was too small)."""
         import torch
         from solvers.spectral import ldc_lib
         index = torch.cuda.current_device() if self.device.index is None else self.device.index
         with torch.cuda.device(self.device):
             start = int(self.t["ctrl"][F.CTRL_ITER].item())
+            if pressure_budget is not None:
+                F.check(F.lib().ldc_fv_wide_set_pressure_budget(self._wide, int(pressure_budget)),
+                        "ldc_fv_wide_set_pressure_budget")
             with ldc_lib.resident_lock(index):
                 F.check(F.lib().ldc_fv_wide_enqueue(self._wide, int(m), int(budget), C.c_void_p(self._stream())),
                         "ldc_fv_wide_enqueue")
@@ -666,8 +805,16 @@ class FVSolver(LidDrivenCavitySolver):
             return rows, done, total
         if self.chip:
             start = int(self.t["ctrl"][F.CTRL_ITER].item())
-            rows, done, nan, total, self.linear_budget, retries = advance_with_budget(
-                self._wide_step, start, n_iters, self.linear_budget, LINEAR_MAX_ITERATIONS)
+            if self.consistent:
+                rows, done, nan, total, budgets, both = advance_with_budgets(
+                    self._wide_step, start, n_iters, (self.linear_budget, self.pressure_budget),
+                    (LINEAR_MAX_ITERATIONS, int(self.params.pressure_max_iters)))
+                self.linear_budget, self.pressure_budget = budgets
+                retries, more = both
+                self.pressure_budget_retries += more
+            else:
+                rows, done, nan, total, self.linear_budget, retries = advance_with_budget(
+                    self._wide_step, start, n_iters, self.linear_budget, LINEAR_MAX_ITERATIONS)
             self.linear_budget_retries += retries
             if nan:
                 F.check(F.lib().ldc_fv_wide_status(self._wide), f"FV trial at iteration {total}")

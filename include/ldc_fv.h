@@ -1,5 +1,6 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
- * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc).
+ * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc and
+ * csrc/ldc_fv_wide_pressure.inc).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -136,6 +137,39 @@
  *  thread), so lone runs, batches, graphs and repeats agree bit for bit, whatever the budget and the enqueues' lengths.
  *  The order differs from the one-CU mixing kernel's: the two agree to rounding.
  *
+ * The consistent pressure equation of such a trial (ldc_fv_wide_set_pressure; csrc/ldc_fv_wide_pressure.inc, part of the
+ * same unit).  The reference corrects the pressure with the constant-coefficient Laplacian rho |S| / d and the velocities
+ * with u' = -D grad p', D = V / a_P: two operators, so the corrected face fluxes never conserve mass.  A handle in mode
+ * LDC_FV_PRESSURE_CONSISTENT solves, per SIMPLE iteration,
+ *    (A x)_P = sum over the inner faces f of P of w_f (x_P - x_N) = b,  w_f = rho (D_P / 2 + D_N / 2) |S_f| / d_f,
+ * D_c = V / (a_P + 1e-14) from the unrelaxed diagonal, |S| / d = dy / dx on x faces and dx / dy on y faces, b = rhs_p with
+ * entry 0 replaced by minus the sum of the others, by conjugate gradients from x = 0 with the preconditioner z = L+ r (the
+ * four GEMMs of the fast diagonalisation, zero mode dropped, no entry-0 insertion, no shift).  It stops at
+ * |r|_2 <= tol |b|_2; after max_iters iterations the iterate is accepted and the cap hit counted; |b| = 0 gives x = 0 without
+ * an iteration.  p' = x - x_0, u' = -D grad p' and p += alpha_p p' as before; the inner faces take
+ * mdot = mdot* - w_f (p'_N - p'_P) and the wall faces stay exactly 0.0 (DESIGN.md FV-Q4 does not apply in this mode).
+ *  - the chain: faces | init | np x (gemm x 4 | rz | ap | xr) | pfinish stand where faces | gemm x 4 stood, and a fluxvort
+ *    of the mode where fluxvort stood: 9 + 5 nb + 7 np launches per iteration (ldc_fv_wide_launches), np = min(pressure
+ *    budget, max_iters), by the chip mapping's rules -- grids of (nx, ny) alone, partial sums through the slots of the solve's
+ *    scratch in the one fixed order, the CG scalars in two copies that alternate by launch (where the BiCGSTAB scalars
+ *    lived), the search direction in two alternating copies because its update is fused with the matrix-vector product,
+ *    no waits, no atomics.  The CG vectors and mdot* live in BiCGSTAB's work vectors 9 .. 16, dead after linfinish; x is
+ *    vector 26, where p' + const stands in the reference mode too;
+ *  - the budget (ldc_fv_wide_set_pressure_budget, LDC_FV_WIDE_PRESSURE_BUDGET_DEFAULT) follows the protocol of lin_budget: a
+ *    solve still active after np < max_iters iterations sets the overflow word -- to 2, where BiCGSTAB's overflow writes 1 --
+ *    before u, v, p or mdot are touched (mdot* waits in work vectors), ctrl stays, ldc_fv_wide_status returns
+ *    LDC_FV_WIDE_E_BUDGET and the caller enqueues again with a larger budget.  Results do not depend on either budget; the
+ *    captured graphs are keyed on both;
+ *  - statistics: LDC_FV_WIDE_PRESSURE_SCRATCH_LEN int64 words of the caller's, written by pfinish for every completed
+ *    iteration: [0] CG iterations in all, [1] solves, [2] cap hits, [3] the last solve's count.  Zero them with ctrl;
+ *  - in a batch the block (tolerance, statistics pointer: 16 bytes) travels in the trial's table entry behind the mixing
+ *    block -- FvWideArgs 208 bytes with max_iters in its last four, the mixing block 32, this one 16: the entry's 256 bytes
+ *    are full -- so ldc_fv_wide_set_pressure comes before ldc_fv_wide_batch_create.  A batch may mix both modes (one
+ *    max_iters among the consistent trials): its chain then carries the launches of both, 13 + 5 nb + 7 np, a reference
+ *    trial returns from the new ones before it reads anything and is bit-identical to its plain run, and a consistent trial
+ *    returns from the exact solve's GEMMs.  A batch without a consistent trial runs the plain chain, launch for launch.
+ *  The mixing chain of ldc_fv_wide_set_anderson follows `record` as before.
+ *
  * Post-processing and prolongation of such a trial (ldc_fv_wide_post_enqueue, ldc_fv_wide_prolong_enqueue; the same
  * unit): what ldc_fv_post_enqueue and ldc_fv_prolong_enqueue do for a trial of up to LDC_FV_MAX_N cells per axis, by the
  * chip mapping's rules for LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N: one launch per phase, a grid that depends on (nx, ny) alone,
@@ -197,6 +231,14 @@ extern "C" {
 /* caller's mixing scratch in doubles: 8 words, then per work-group of a sweep b[depth] and the lower triangle of A        */
 #define LDC_FV_WIDE_ANDERSON_LAUNCHES 3
 #define LDC_FV_WIDE_ANDERSON_SCRATCH_LEN(nx, ny, depth) (8 + LDC_FV_WIDE_GROUPS(nx, ny) * ((int64_t)(depth) * ((depth) + 3) / 2))
+
+/* The consistent pressure equation of a chip or shared trial (ldc_fv_wide_set_pressure): the modes, the launches of one   */
+/* CG iteration, the CG iterations a new handle's enqueue carries per SIMPLE iteration, the caller's statistics words       */
+#define LDC_FV_PRESSURE_REFERENCE 0
+#define LDC_FV_PRESSURE_CONSISTENT 1
+#define LDC_FV_WIDE_PRESSURE_LAUNCHES 7
+#define LDC_FV_WIDE_PRESSURE_BUDGET_DEFAULT 12
+#define LDC_FV_WIDE_PRESSURE_SCRATCH_LEN 4
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
 #define LDC_FV_DBG_GRAD_P 0        /* 2n: d/dx p, then d/dy p                                    */
@@ -265,6 +307,13 @@ struct ldc_fv_anderson {
                                   /* count seen last, fallbacks taken.  Zero it exactly when ctrl is zeroed. */
 };
 
+struct ldc_fv_pressure {
+  int32_t mode;                   /* LDC_FV_PRESSURE_REFERENCE (the exact solve of the constant-coefficient Laplacian) or */
+                                  /* LDC_FV_PRESSURE_CONSISTENT (CG on the a_P-weighted operator)                          */
+  int32_t max_iters;              /* CG iterations per solve (>= 1); the iterate is accepted after that many              */
+  double tol;                     /* CG stops at |r|_2 <= tol |b|_2 (0 < tol < 1)                                          */
+};
+
 typedef struct ldc_fv ldc_fv;
 typedef struct ldc_fv_wide ldc_fv_wide;
 typedef struct ldc_fv_wide_batch ldc_fv_wide_batch;
@@ -329,6 +378,18 @@ int ldc_fv_wide_launches(const ldc_fv_wide *h, int lin_budget);
 /* astate, and with depth > 0 a null hist, a hist_len below LDC_FV_ANDERSON_HIST_LEN, a null or short scratch.  A batch      */
 /* copies the block at ldc_fv_wide_batch_create: attach before creating it.                                                  */
 int ldc_fv_wide_set_anderson(ldc_fv_wide *h, const struct ldc_fv_anderson *acc, double *scratch, int64_t scratch_len);
+/* The pressure equation of the handle: cfg == NULL or mode LDC_FV_PRESSURE_REFERENCE is the chain of a new handle; mode    */
+/* LDC_FV_PRESSURE_CONSISTENT the one described above, with `scratch` a device buffer of scratch_len >=                       */
+/* LDC_FV_WIDE_PRESSURE_SCRATCH_LEN int64 words owned by the caller (the statistics).  Call it between solves, with nothing   */
+/* of the handle in flight, and before ldc_fv_wide_batch_create; the handle's captured iterations are freed.  Validation      */
+/* needs no device: LDC_E_STATE for a null handle; LDC_E_ARG for another mode, max_iters < 1, tol outside (0, 1), a null or   */
+/* short scratch.                                                                                                             */
+int ldc_fv_wide_set_pressure(ldc_fv_wide *h, const struct ldc_fv_pressure *cfg, double *scratch, int64_t scratch_len);
+/* The CG iterations the next enqueues carry per SIMPLE iteration (>= 1; min(budget, max_iters) x 7 launches).  LDC_E_ARG for */
+/* a handle in the reference mode.  Graphs are kept: they are keyed on both budgets.                                          */
+int ldc_fv_wide_set_pressure_budget(ldc_fv_wide *h, int budget);
+/* The same for a batch (it has no effect on a batch without a consistent trial). */
+int ldc_fv_wide_batch_set_pressure_budget(ldc_fv_wide_batch *b, int budget);
 /* 0, LDC_FV_E_NAN, or LDC_FV_WIDE_E_BUDGET when the last enqueue overflowed (wait for its stream first). */
 int ldc_fv_wide_status(ldc_fv_wide *h);
 /* n (1 .. LDC_FV_WIDE_BATCH_MAX) trials of any sizes and parameters, one device, advanced by the same launches.  `table` */
