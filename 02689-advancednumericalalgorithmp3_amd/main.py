@@ -65,6 +65,8 @@ def make_record(cfg: dict, solver, out_dir: Path, t0: float) -> dict:
                validation_table=solver.validation_table(), total_seconds=time.perf_counter() - t0)
     if hasattr(solver, "kernel_mode"):          # which of the library's kernels advanced this trial (include/ldc_hip.h: 0, 3, 4, 5)
         rec["kernel_mode"] = int(solver.kernel_mode)
+    if getattr(solver, "initial_guess_info", None):     # a spectral solve with initial_guess="fv": the seed's cells, iterations, seconds
+        rec["initial_guess"] = dict(solver.initial_guess_info)
     if hasattr(solver, "level_iterations"):     # a sequenced finite-volume solve: the iterations of every level, coarse -> fine
         rec["level_iterations"] = [int(k) for k in solver.level_iterations]
     if hasattr(solver, "counters"):             # a finite-volume solve: the device's counters (linear solves, Anderson fallbacks)

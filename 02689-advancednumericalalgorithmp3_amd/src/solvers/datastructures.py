@@ -75,6 +75,17 @@ class SpectralParameters(Parameters):
     # where the reported vortices sit: "none" (the collocation node of the grid extremum, as the reference) or "newton"
     # (the stationary point of the interpolant of psi, ldc_vortex_refine).  Changes reported metrics: it goes to MLflow
     vortex_refine: str = "none"
+    # where a solve() starts: "rest" (the fluid at rest under the lid, as the reference) or "fv" (a finite-volume solve of
+    # the same cavity first -- mapping "chip", a batch's seeds together as mapping "shared"; TVD, the consistent pressure
+    # equation -- sampled at the collocation nodes by ldc_fv_sample_nodes; solvers.spectral.warm_start).  The seed has
+    # initial_guess_cells cells per axis (0: max(16, N), each axis by its own order), runs to initial_guess_tolerance
+    # with the relaxation initial_guess_alpha_uv / _alpha_p, and a seed that fails leaves the trial at rest.  The stop
+    # rule then ends another path to the same fixed point: all five change results and go to MLflow
+    initial_guess: str = "rest"
+    initial_guess_cells: int = 0
+    initial_guess_tolerance: float = 1e-4
+    initial_guess_alpha_uv: float = 0.7
+    initial_guess_alpha_p: float = 0.3
 
     def to_mlflow(self) -> dict:
         skip = {"device", "check_every", "graph_iters", "nan_guard", "diagnostics", "persistent"}

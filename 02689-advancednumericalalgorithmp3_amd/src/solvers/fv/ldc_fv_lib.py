@@ -15,6 +15,7 @@ REC_LEN, CTRL_LEN = 8, 8
 NWORK, DESC_DOUBLES = 32, 64
 LAUNCH_MAX = 256
 PROLONG_LAUNCH_MAX = 128
+SAMPLE_LAUNCH_MAX = 32         # LDC_FV_SAMPLE_LAUNCH_MAX: jobs per launch of ldc_fv_sample_nodes
 ANDERSON_LAUNCH_MAX, ANDERSON_MAX_DEPTH, ANDERSON_STATE_LEN = 96, 16, 4
 ASTATE_COLUMNS, ASTATE_POSITION, ASTATE_SEEN, ASTATE_FALLBACKS = range(4)
 E_NAN = -5
@@ -66,6 +67,17 @@ class Pressure(C.Structure):
     _fields_ = [("mode", C.c_int32), ("max_iters", C.c_int32), ("tol", C.c_double)]
 
 
+class SampleJob(C.Structure):
+    """Mirror of ``struct ldc_fv_sample_job`` -- keep field order in sync with the header."""
+    _fields_ = (
+        [(n, _dp) for n in ("u", "v", "p", "ulid")]
+        + [("nx", C.c_int32), ("ny", C.c_int32), ("dx", C.c_double), ("dy", C.c_double)]
+        + [(n, _dp) for n in ("x", "y", "ulid_nodes")]
+        + [("Mx", C.c_int32), ("My", C.c_int32)]
+        + [(n, _dp) for n in ("U", "V", "P")]
+    )
+
+
 # every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
            "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
@@ -74,7 +86,7 @@ EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue"
            "ldc_fv_wide_batch_destroy", "ldc_fv_wide_batch_enqueue", "ldc_fv_wide_batch_set_graph",
            "ldc_fv_wide_batch_launches", "ldc_fv_wide_post_enqueue", "ldc_fv_wide_post_launches",
            "ldc_fv_wide_prolong_enqueue", "ldc_fv_wide_set_anderson", "ldc_fv_wide_set_pressure",
-           "ldc_fv_wide_set_pressure_budget", "ldc_fv_wide_batch_set_pressure_budget")
+           "ldc_fv_wide_set_pressure_budget", "ldc_fv_wide_batch_set_pressure_budget", "ldc_fv_sample_nodes")
 
 _bound = None
 
@@ -161,6 +173,7 @@ def lib() -> C.CDLL:
         L.ldc_fv_wide_set_pressure.argtypes = [_dp, C.POINTER(Pressure), _dp, C.c_int64]
         L.ldc_fv_wide_set_pressure_budget.argtypes = [_dp, C.c_int]
         L.ldc_fv_wide_batch_set_pressure_budget.argtypes = [_dp, C.c_int]
+        L.ldc_fv_sample_nodes.argtypes = [C.POINTER(SampleJob), C.c_int, _dp]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -247,3 +260,10 @@ def wide_set_pressure(wide, mode: str, tol: float, max_iters: int, stats_ptr: in
     created: set it first."""
     cfg = Pressure(mode=PRESSURE_MODES[mode], max_iters=int(max_iters), tol=float(tol))
     check(lib().ldc_fv_wide_set_pressure(wide, C.byref(cfg), _dp(stats_ptr), int(stats_len)), "ldc_fv_wide_set_pressure")
+
+
+def sample_nodes(jobs, stream) -> None:
+    """U, V, P of every ``SampleJob`` from its FV state (include/ldc_fv.h): ONE call for all jobs, which the library
+    checks first and launches SAMPLE_LAUNCH_MAX at a time; nothing synchronises."""
+    arr = (SampleJob * len(jobs))(*jobs)
+    check(lib().ldc_fv_sample_nodes(arr, len(jobs), _dp(stream)), "ldc_fv_sample_nodes")

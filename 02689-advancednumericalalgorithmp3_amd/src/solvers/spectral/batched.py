@@ -24,7 +24,7 @@ import time
 
 import numpy as np
 
-from . import chunks, ldc_lib as L
+from . import chunks, ldc_lib as L, warm_start
 from .sg import SGSolver, refine_vortices_together
 from ..base import WARMUP_ITERATIONS
 
@@ -148,7 +148,10 @@ class BatchedSGSolver:
         The trials share every launch, so only the batch has a wall time of its own (``self.batch_seconds``).
         A trial's ``metrics.wall_time_seconds`` is its SHARE of it, in proportion to its iteration count (the
         shares add up to the batch's wall time), so ``iterations / wall_time_seconds`` of any trial is the
-        batch's aggregate rate in trial-iterations per second, not B times too low."""
+        batch's aggregate rate in trial-iterations per second, not B times too low.
+
+        The trials with ``initial_guess="fv"`` are seeded first: ONE batch of ``mapping="shared"`` finite-volume trials
+        and ONE transfer call (``warm_start.seed_together``); the seeds' time is part of the batch's wall time."""
         ps = [s.params for s in self.solvers]
         if len({bool(p.diagnostics) for p in ps}) != 1:
             raise ValueError("trials of one batch must agree on `diagnostics` (it selects the kernels of the "
@@ -156,6 +159,7 @@ class BatchedSGSolver:
         caps = [p.max_iterations for p in ps] if max_iter is None else [max_iter] * len(ps)
         diag = bool(ps[0].diagnostics)
         t0 = time.perf_counter()
+        warm_start.seed_together(self.solvers)
         out = self.run_to_tolerance([p.tolerance for p in ps], caps, diag)
         wall = time.perf_counter() - t0
         self.batch_seconds, self.batch_size = wall, len(self.solvers)

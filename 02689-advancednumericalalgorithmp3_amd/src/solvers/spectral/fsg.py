@@ -40,6 +40,9 @@ def hierarchy_orders(n_fine: int, n_levels: int, coarsest_n: int = COARSEST_N) -
 class FSGSolver(SGSolver):
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
+        if self.params.initial_guess != "rest":      # (with multigrid="fsg" in the parameters SGSolver has refused already)
+            raise ValueError(f"initial_guess={self.params.initial_guess!r} with multigrid='fsg' (FSGSolver): the sequence "
+                             f"starts on its coarsest level, which takes no finite-volume seed yet")
         if self.params.nx != self.params.ny:
             # the reference builds its level hierarchy from ONE order (multigrid/fsg.py:490-530, n_fine = nx) and squares
             # every level; with nx != ny it has no defined behaviour to reproduce

@@ -17,7 +17,7 @@ import numpy as np
 
 from ..base import LidDrivenCavitySolver
 from ..datastructures import SpectralParameters
-from . import chunks, ldc_lib as L
+from . import chunks, ldc_lib as L, warm_start
 from .basis.spectral import ChebyshevLobattoBasis, LegendreLobattoBasis, inner_to_full_interpolation
 from .operators.corner import create_corner_treatment
 
@@ -155,6 +155,8 @@ class SGSolver(LidDrivenCavitySolver):
         p = self.params
         if p.vortex_refine not in VORTEX_REFINE:
             raise ValueError(f"Unknown vortex_refine: {p.vortex_refine!r}. Use one of {VORTEX_REFINE}")
+        warm_start.validate(p)               # initial_guess and its keys; initial_guess="fv" with multigrid="fsg" is refused
+        self.initial_guess_info = None       # after a solve() with initial_guess="fv": what the seed took (warm_start)
         self.vortex_refine_status = None     # per (primary, BR, BL, TL) after a refined compute_vortex_metrics()
         self._refined = None                 # (result block, extrema values, indices) left by refine_vortices_together
         self._refine_w = None
@@ -352,6 +354,23 @@ class SGSolver(LidDrivenCavitySolver):
         self.d["P"][1: Mx - 1, 1: My - 1] = p_inner
         self._edge_off = {}          # (the FSG prolongation: the east wall holds the lid speed on purpose, quirk Q2)
         self.set_state()
+
+    def start_from(self, fv):
+        """This trial's state from the finite-volume trial ``fv`` (an FVSolver of any mapping and size on the same device
+        and the same domain Lx, Ly): ``warm_start.start_from_fv``, the FV fields sampled at the collocation nodes on the
+        device, this trial's own boundary values on the boundary."""
+        warm_start.start_from_fv([(fv, self)])
+
+    def solve(self, tolerance: float = None, max_iter: int = None):
+        """``LidDrivenCavitySolver.solve`` from the state the trial holds; with ``initial_guess="fv"`` that state is
+        first taken from a finite-volume solve of the same cavity (``warm_start.seed_alone``; from rest when the seed
+        fails).  ``metrics.iterations`` is the spectral count, ``metrics.wall_time_seconds`` includes the seed, and
+        ``initial_guess_info`` holds the seed's cells, iterations and wall time."""
+        if self.params.initial_guess != "fv":
+            return super().solve(tolerance, max_iter)
+        warm_start.seed_alone(self)
+        super().solve(tolerance, max_iter)
+        self.metrics.wall_time_seconds += self.initial_guess_info["wall_time_seconds"]
 
     def reset_state(self):
         """Fluid at rest with the regularised lid (reference sg.py:76-98)."""

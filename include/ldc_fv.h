@@ -1,6 +1,6 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
  * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc and
- * csrc/ldc_fv_wide_pressure.inc).
+ * csrc/ldc_fv_wide_pressure.inc, csrc/ldc_fv_sample.hip).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -185,6 +185,20 @@
  *  - prolong: a launch for u, v, p at the fine cells (every thread recomputes the interpolated p at fine cell 0, so
  *    p[0] is exactly 0.0) and one for mdot, LDC_FV_WIDE_GROUPS of the fine trial each; the arithmetic of
  *    ldc_fv_prolong_enqueue with no multiply-add contracted, so the fine u, v, p, mdot are its bits.
+ *
+ * Sampling at the nodes of a tensor grid (csrc/ldc_fv_sample.hip, ldc_fv_sample_nodes): the initial guess of a spectral
+ * trial from a finite-volume state of the same cavity.  A job holds raw device pointers only, no handle, so a trial of any
+ * mapping can be the source, LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N cells per axis; nothing of the source is written.
+ *  - interior nodes (0 < ix < Mx - 1 and 0 < iy < My - 1) take the bilinear interpolant of the ring-extended field of the
+ *    prolongation above at (x[ix], y[iy]): the same nodes e_k, the same left node and weight, x first, no multiply-add
+ *    contracted.  U and V take the ring of walls and lid (the SOURCE's ulid above the cells), P the zero-gradient ring,
+ *    and P is not shifted: only grad p enters the spectral residual;
+ *  - boundary nodes take the TARGET's own values, bit for bit: U = V = 0.0 on ix = 0, ix = Mx - 1 and iy = 0; V = 0.0 and
+ *    U = ulid_nodes[ix] on iy = My - 1, the two top corners included;
+ *  - U and V are dense Mx x My, element (ix, iy) at ix My + iy; P is dense (Mx - 2) x (My - 2) over the inner nodes,
+ *    element (ix, iy) at (ix - 1)(My - 2) + (iy - 1);
+ *  - blockIdx.y is the job and the work-groups of a job stride over its nodes: no waits, no atomics, no LDS, so a job's
+ *    result does not depend on what else is in the call, bit for bit.
  */
 #ifndef LDC_FV_H
 #define LDC_FV_H
@@ -206,6 +220,7 @@ extern "C" {
 #define LDC_FV_FACES(nx, ny) ((int64_t)(ny) * ((nx) + 1) + (int64_t)((ny) + 1) * (nx))
 #define LDC_FV_LAUNCH_MAX 256      /* trials per launch of ldc_fv_batch_enqueue (more: several launches) */
 #define LDC_FV_PROLONG_LAUNCH_MAX 128 /* pairs per launch of ldc_fv_prolong_enqueue: two descriptors per pair in the arguments */
+#define LDC_FV_SAMPLE_LAUNCH_MAX 32  /* jobs per launch of ldc_fv_sample_nodes: 112 bytes per job in the arguments */
 #define LDC_FV_ANDERSON_LAUNCH_MAX 96 /* trials per launch of the mixing kernel: 32 bytes per trial in the arguments */
 #define LDC_FV_ANDERSON_MAX_DEPTH 16
 #define LDC_FV_ANDERSON_STATE_LEN 4
@@ -312,6 +327,18 @@ struct ldc_fv_pressure {
                                   /* LDC_FV_PRESSURE_CONSISTENT (CG on the a_P-weighted operator)                          */
   int32_t max_iters;              /* CG iterations per solve (>= 1); the iterate is accepted after that many              */
   double tol;                     /* CG stops at |r|_2 <= tol |b|_2 (0 < tol < 1)                                          */
+};
+
+struct ldc_fv_sample_job {
+  const double *u, *v, *p;        /* source: the FV state at the cells c = j*nx + i (n each) */
+  const double *ulid;             /* source: the FV lid profile (nx) */
+  int32_t nx, ny;                 /* LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N each */
+  double dx, dy;                  /* > 0 */
+  const double *x, *y;            /* target: node coordinates, ascending, Mx inside [0, nx dx] and My inside [0, ny dy] */
+  const double *ulid_nodes;       /* target: its own u on the lid (Mx) */
+  int32_t Mx, My;                 /* >= 3 each */
+  double *U, *V;                  /* out: Mx * My each, element (ix, iy) at ix * My + iy */
+  double *P;                      /* out: (Mx - 2) * (My - 2), the inner nodes */
 };
 
 typedef struct ldc_fv ldc_fv;
@@ -427,6 +454,13 @@ int ldc_fv_wide_post_launches(const ldc_fv_wide *h);
 /* and needs no device: LDC_E_STATE for a null handle; LDC_E_ARG for coarse == fine and for two domains (nx dx or ny dy      */
 /* differ beyond 1e-12 relative); then LDC_E_NODEVICE, or LDC_E_STATE for a handle of another device.                        */
 int ldc_fv_wide_prolong_enqueue(ldc_fv_wide *coarse, ldc_fv_wide *fine, void *stream);
+/* n jobs (a host array; every pointer inside a job is a device pointer, nothing of it in flight elsewhere): U, V, P of   */
+/* every job from its u, v, p as described above, LDC_FV_SAMPLE_LAUNCH_MAX jobs per launch, nothing synchronises.         */
+/* Validation comes before any launch and needs no device: LDC_E_ARG for a null list or n < 1, for a null pointer in a    */
+/* job, for nx or ny outside LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N, for Mx or My < 3 and for dx or dy <= 0; then               */
+/* LDC_E_NODEVICE.  That x and y lie inside the source's domain is the caller's to see to (a node outside is              */
+/* extrapolated from the last interval; no read leaves the source arrays).                                                */
+int ldc_fv_sample_nodes(const struct ldc_fv_sample_job *jobs, int n, void *stream);
 
 #ifdef __cplusplus
 }
