@@ -1,7 +1,8 @@
 // ldc_fv_common.inc -- what all translation units of the finite-volume solver share (include/ldc_fv.h):
 // ldc_kernels.hip (through ldc_fv_kernel.inc, the SIMPLE iteration with one trial per CU), ldc_fv_wide.hip (the same
 // iteration by the whole chip), ldc_fv_post.hip (streamfunction and vortex metrics), ldc_fv_prolong.hip (coarse-to-fine
-// transfer of the state) and ldc_fv_anderson.hip (Anderson mixing).
+// transfer of the state), ldc_fv_anderson.hip (Anderson mixing) and ldc_fv_cu_pressure.hip (the one-CU iteration with the
+// consistent pressure equation).
 // Types, constants and host-side helpers (the fill of a descriptor, as_stream) only, no device function: each unit's
 // code object holds what that unit needs and depends on no other's.  The device functions that two mappings share are
 // in ldc_fv_cells.inc (the SIMPLE iteration), ldc_fv_post_cells.inc, ldc_fv_prolong_cells.inc and
@@ -41,6 +42,24 @@ struct FvDesc {
 };
 static_assert(sizeof(FvDesc) <= LDC_FV_DESC_DOUBLES * sizeof(double), "descriptor slot");
 
+// The descriptor slot (LDC_FV_DESC_DOUBLES doubles = 512 bytes in the tail of `work`), byte by byte:
+//     0 .. 255  FvDesc (ldc_fv_create; it travels by value in the 256-byte table entry of a shared batch: it must not grow)
+//   256 .. 327  the post block (ldc_fv_post.hip, kFvPostOffset)
+//   384 .. 407  the pressure block of a one-CU trial (FvCuPcg below; ldc_fv_set_pressure)
+//   448 .. 511  the mixing kernel's kept record row (ldc_fv_anderson.hip, kFvAaKeepOffset)
+// The consistent pressure equation of a one-CU trial (ldc_fv_cu_pressure.hip): tolerance, cap, mode and the caller's four
+// statistics words, written by ldc_fv_set_pressure with the synchronous copy of ldc_fv_create.
+struct FvCuPcg {
+  double tol;
+  int max_iters, mode;
+  long long* stats;
+};
+constexpr int kFvCuPcgOffset = 384;
+static_assert(sizeof(FvDesc) <= 256, "the pressure block is clear of the descriptor");
+static_assert(kFvCuPcgOffset >= 256 + 72, "the pressure block is clear of the post block (ldc_fv_post.hip: 72 bytes at 256)");
+static_assert(kFvCuPcgOffset + sizeof(FvCuPcg) <= (LDC_FV_DESC_DOUBLES - LDC_FV_REC_LEN) * sizeof(double),
+              "the pressure block is clear of the mixing kernel's kept row");
+
 // host: the caller's stream handle of the C ABI
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -75,6 +94,11 @@ struct ldc_fv {
   int device;
   int nx, ny;               // (host-side copies for validation: ldc_fv_prolong_enqueue)
   double dx, dy;
+  int pressure_mode;        // LDC_FV_PRESSURE_*: the kernel that advances the trial (ldc_fv_set_pressure)
 };
+
+// host: consistent handles (pressure_mode LDC_FV_PRESSURE_CONSISTENT) of the CURRENT device go to fv_cu_pressure_kernel,
+// LDC_FV_LAUNCH_MAX per launch (ldc_fv_cu_pressure.hip; called by ldc_fv_enqueue and ldc_fv_batch_enqueue only)
+__attribute__((visibility("hidden"))) int ldc_fv_cu_pressure_launch(ldc_fv* const* hs, int n, int n_iters, void* stream);
 
 #endif  // LDC_FV_COMMON_INC

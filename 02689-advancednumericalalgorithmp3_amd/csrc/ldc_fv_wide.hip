@@ -68,6 +68,7 @@
 #include "ldc_hip.h"
 #include "ldc_fv_common.inc"
 #include "ldc_fv_cells.inc"
+#include "ldc_fv_pressure_cells.inc"
 #include "ldc_fv_anderson_cells.inc"
 #include "ldc_fv_post_cells.inc"
 // (ldc_fv_prolong_cells.inc: at the prolongation section, behind its FP_CONTRACT pragma)

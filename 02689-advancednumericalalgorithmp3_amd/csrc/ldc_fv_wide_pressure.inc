@@ -37,11 +37,8 @@
 constexpr int kWidePcgLaunches = LDC_FV_WIDE_PRESSURE_LAUNCHES;         // of one CG iteration
 static_assert(kWidePcgLaunches == 7, "gemm x 4 | rz | ap | xr");
 
-// work vectors of the solve (all dead after linfinish): mdot* (3 n >= faces), r, z, the two copies of p, q; x is FV_Y
-constexpr FvVec PCG_MS = FV_RU, PCG_R = FV_RTV, PCG_Z = FV_PU, PCG_P = FV_PV, PCG_Q = FV_VV;
-static_assert(PCG_R == PCG_MS + 3 && PCG_Z == PCG_R + 1 && PCG_P == PCG_Z + 1 && PCG_Q == PCG_P + 2 && PCG_Q < FV_C,
-              "the vectors of the pressure solve");
-static_assert(3 * LDC_FV_MIN_N * LDC_FV_MIN_N >= LDC_FV_FACES(LDC_FV_MIN_N, LDC_FV_MIN_N), "mdot* in three work vectors");
+// (the work vectors of the solve PCG_MS, PCG_R, PCG_Z, PCG_P, PCG_Q, wide_pcg_D, wide_pcg_w, wide_pcg_row and
+// wide_pcg_cell_fluxvort: ldc_fv_pressure_cells.inc, shared with ldc_fv_cu_pressure.hip)
 
 struct WidePcgScalars {
   double bb, rr, rz, alpha, beta;
@@ -62,13 +59,6 @@ __device__ __forceinline__ void wide_pcg_store(double* k, int g, const WidePcgSc
 __device__ __forceinline__ bool wide_pcg_gate(const FvWideArgs& a) { return a.pmax == 0 || wide_gate(a); }
 
 __device__ __forceinline__ bool wide_pcg_done(const WidePcgScalars& s, double tol) { return sqrt(s.rr) <= tol * sqrt(s.bb); }
-
-__device__ __forceinline__ double wide_pcg_D(const FvCtx& x, int c) { return x.V / (x.w[FV_AP * x.n + c] + 1e-14); }
-
-// the weight of an inner face between owner P (west / south) and neighbour N
-__device__ __forceinline__ double wide_pcg_w(const FvCtx& x, double DP, double DN, bool xdir) {
-  return (x.rho * (0.5 * DP + 0.5 * DN)) * (xdir ? x.dy / x.dx : x.dx / x.dy);
-}
 
 // ---- faces: wide_faces with mdot* left in the work vectors PCG_MS
 __device__ __forceinline__ void wide_pcg_faces(const FvWideArgs& a, int g, int par, double* lds) {
@@ -177,7 +167,7 @@ __device__ __forceinline__ void wide_pcg_ap(const FvWideArgs& a, int g, int it, 
   }
   wide_pcg_store(wide_kry(a, par ^ 1), g, s);
   if (!s.act) return;
-  const int nx = x.nx, ny = x.ny;
+  const int nx = x.nx;
   const double beta = s.beta;
   const double *z = x.vec(PCG_Z), *pold = x.vec(PCG_P, (it & 1) ^ 1);
   double *pnew = x.vec(PCG_P, it & 1), *q = x.vec(PCG_Q);
@@ -186,12 +176,8 @@ __device__ __forceinline__ void wide_pcg_ap(const FvWideArgs& a, int g, int it, 
     const int i = c % nx, j = c / nx;
     // (the same expression for the cell and for its neighbours: every thread gets the p its neighbour writes)
 #define PCG_PV(k) (it > 0 ? fma(beta, pold[k], z[k]) : z[k])
-    const double pc = PCG_PV(c), Dc = wide_pcg_D(x, c);
-    double y = 0.0;
-    if (i > 0) y += wide_pcg_w(x, wide_pcg_D(x, c - 1), Dc, true) * (pc - PCG_PV(c - 1));
-    if (i < nx - 1) y += wide_pcg_w(x, Dc, wide_pcg_D(x, c + 1), true) * (pc - PCG_PV(c + 1));
-    if (j > 0) y += wide_pcg_w(x, wide_pcg_D(x, c - nx), Dc, false) * (pc - PCG_PV(c - nx));
-    if (j < ny - 1) y += wide_pcg_w(x, Dc, wide_pcg_D(x, c + nx), false) * (pc - PCG_PV(c + nx));
+    const double pc = PCG_PV(c);
+    const double y = wide_pcg_row(x, c, i, j, pc, [&](int k) { return PCG_PV(k); });
 #undef PCG_PV
     pnew[c] = pc; q[c] = y;
     pq[0] += pc * y;
@@ -246,31 +232,11 @@ __device__ __forceinline__ void wide_pcg_finish(const FvWideArgs& a, const FvWid
 }
 
 // ---- mdot = mdot* - w_f (p'_N - p'_P) on the inner faces, 0.0 on the walls; the vorticity with ghost cells; record sum 8.
-//      (The vorticity is a copy of the second half of fv_cell_flux_vorticity, ldc_fv_cells.inc, 6.: a change to one goes
-//      into the other.)
 __device__ __forceinline__ void wide_pcg_fluxvort(const FvWideArgs& a, int g, double* lds) {
   if (wide_pcg_gate(a)) return;
   const FvCtx x(a.d);
-  const FvDesc& d = x.d;
-  const int nx = x.nx, ny = x.ny, ldx = x.ldx;
-  const double dx = x.dx, dy = x.dy;
-  const double *pp = x.vec(FV_Y), *sx = x.vec(PCG_MS), *sy = x.vec(PCG_MS) + ny * ldx;
-  double *fx = x.fx, *fy = x.fy;
+  const double *pp = x.vec(FV_Y), *sx = x.vec(PCG_MS), *sy = x.vec(PCG_MS) + x.ny * x.ldx;
   double part[1] = {0.0};
-  for (int c = g * kWT + threadIdx.x; c < x.n; c += a.G * kWT) {
-    const int i = c % nx, j = c / nx;
-    const double Dc = wide_pcg_D(x, c);
-    if (i == 0) fx[j * ldx] = 0.0;
-    fx[j * ldx + i + 1] =
-        i < nx - 1 ? sx[j * ldx + i + 1] - wide_pcg_w(x, Dc, wide_pcg_D(x, c + 1), true) * (pp[c + 1] - pp[c]) : 0.0;
-    if (j == 0) fy[i] = 0.0;
-    fy[(j + 1) * nx + i] =
-        j < ny - 1 ? sy[(j + 1) * nx + i] - wide_pcg_w(x, Dc, wide_pcg_D(x, c + nx), false) * (pp[c + nx] - pp[c]) : 0.0;
-    const double vE = i < nx - 1 ? d.v[c + 1] : -d.v[c], vW = i > 0 ? d.v[c - 1] : -d.v[c];
-    const double uN = j < ny - 1 ? d.u[c + nx] : 2 * d.lid - d.u[c], uS = j > 0 ? d.u[c - nx] : -d.u[c];
-    const double wc = (vE - vW) / (2 * dx) - (uN - uS) / (2 * dy);
-    x.vec(FV_OMEGA)[c] = wc;
-    part[0] += wc * wc;
-  }
+  for (int c = g * kWT + threadIdx.x; c < x.n; c += a.G * kWT) wide_pcg_cell_fluxvort(x, c, pp, sx, sy, part[0]);
   wide_slot_put(wide_rec_slots(a), g, 8, part, lds);
 }

@@ -130,8 +130,10 @@ class FVParameters(Parameters):
     # the pressure-correction equation: "reference" (the constant-coefficient Laplacian rho |S| / d, solved exactly: the
     # reference's, whose corrected face fluxes do not conserve mass) or "consistent" (the operator that also corrects the
     # fluxes, w_f = rho D_f |S| / d with D = V / a_P, by preconditioned CG to pressure_tol, at most pressure_max_iters
-    # iterations per solve; mapping "chip" or "shared" only).  They change results: they go to MLflow.  pressure_budget is
-    # the CG iterations the first chunk carries per SIMPLE iteration (doubled when a solve needs more); it changes nothing
+    # iterations per solve; mapping "chip" or "shared" only) or "consistent_cu" (the same equation inside the work-group of a
+    # mapping "cu" trial).  They change results: they go to MLflow.  pressure_budget is the CG iterations the first chunk of
+    # a chip or shared trial carries per SIMPLE iteration (doubled when a solve needs more; "consistent_cu" has no budget);
+    # it changes nothing
     pressure_equation: str = "reference"
     pressure_tol: float = 1e-8
     pressure_max_iters: int = 200

@@ -28,6 +28,7 @@ E_BUDGET = -6                  # ldc_fv_wide_status: the last enqueue ran out of
 PRESSURE_MODES = {"reference": 0, "consistent": 1}
 WIDE_PRESSURE_LAUNCHES, WIDE_PRESSURE_BUDGET_DEFAULT, WIDE_PRESSURE_SCRATCH_LEN = 7, 12, 4
 PSTAT_ITERS, PSTAT_SOLVES, PSTAT_CAPS, PSTAT_LAST = range(4)
+PRESSURE_STATS_LEN = 4         # LDC_FV_PRESSURE_STATS_LEN: the same four words for a one-CU trial (ldc_fv_set_pressure)
 OVERFLOW_LINEAR, OVERFLOW_PRESSURE = 1, 2
 CTRL_DONE, CTRL_ITER, CTRL_NAN, CTRL_GIVEUP, CTRL_LIN_ITERS, CTRL_SOLVES = range(6)
 # slots of a result block of ldc_fv_post_enqueue (LDC_FV_POST_*)
@@ -80,7 +81,7 @@ class SampleJob(C.Structure):
 
 # every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
-           "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
+           "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_set_pressure", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
            "ldc_fv_anderson_enqueue", "ldc_fv_wide_create", "ldc_fv_wide_destroy", "ldc_fv_wide_enqueue",
            "ldc_fv_wide_launches", "ldc_fv_wide_status", "ldc_fv_wide_set_graph", "ldc_fv_wide_batch_create",
            "ldc_fv_wide_batch_destroy", "ldc_fv_wide_batch_enqueue", "ldc_fv_wide_batch_set_graph",
@@ -152,6 +153,7 @@ def lib() -> C.CDLL:
         L.ldc_fv_batch_enqueue.argtypes = [C.POINTER(_dp), C.c_int, C.c_int, _dp]
         L.ldc_fv_status.argtypes = [_dp]
         L.ldc_fv_step_debug.argtypes = [_dp, C.c_int, C.POINTER(_dp), _dp]
+        L.ldc_fv_set_pressure.argtypes = [_dp, C.POINTER(Pressure), _dp, C.c_int64]
         L.ldc_fv_post_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(Post), C.c_int, _dp]
         L.ldc_fv_prolong_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(_dp), C.c_int, _dp]
         L.ldc_fv_anderson_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(Anderson), C.c_int, C.c_int, _dp]
@@ -190,6 +192,15 @@ def batch_enqueue(handles, n_iters: int, stream) -> None:
     """One launch (per LAUNCH_MAX trials) advancing every handle by up to n_iters iterations."""
     arr = (_dp * len(handles))(*[h.value if isinstance(h, _dp) else h for h in handles])
     check(lib().ldc_fv_batch_enqueue(arr, len(handles), int(n_iters), _dp(stream)), "ldc_fv_batch_enqueue")
+
+
+def set_pressure(handle, mode: str, tol: float, max_iters: int, stats_ptr: int = None,
+                 stats_len: int = PRESSURE_STATS_LEN) -> None:
+    """The pressure equation of an ``ldc_fv`` handle (a one-CU trial): ``"reference"`` or ``"consistent"`` (CG inside the
+    trial's work-group to ``tol``, at most ``max_iters`` iterations, statistics in the caller's ``stats_len`` int64
+    words).  One synchronous copy into the tail of the trial's work buffer: nothing of the handle may be in flight."""
+    cfg = Pressure(mode=PRESSURE_MODES[mode], max_iters=int(max_iters), tol=float(tol))
+    check(lib().ldc_fv_set_pressure(handle, C.byref(cfg), _dp(stats_ptr), int(stats_len)), "ldc_fv_set_pressure")
 
 
 def post_enqueue(handles, posts, stream) -> None:

@@ -30,6 +30,9 @@ SCHEMES = {"Upwind": 0, "TVD": 1}
 VORTEX_METRICS = ("host", "device", "chip")
 ACCELERATIONS = ("none", "anderson", "anderson_chip")
 MAPPINGS = ("cu", "chip", "shared")
+# "consistent": the chain of launches over the whole chip (mapping "chip" / "shared"); "consistent_cu": the same equation
+# inside the work-group of a one-CU trial (mapping "cu"); both are LDC_FV_PRESSURE_CONSISTENT to the library
+PRESSURE_EQUATIONS = ("reference", "consistent", "consistent_cu")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
 
 
@@ -528,9 +531,14 @@ class FVSolver(LidDrivenCavitySolver):
             raise ValueError(f"mapping={p.mapping!r}: 'cu', 'chip' or 'shared'")
         if int(p.linear_budget) < 1:
             raise ValueError(f"linear_budget={p.linear_budget}: BiCGSTAB iterations per SIMPLE iteration, at least 1")
-        if p.pressure_equation not in F.PRESSURE_MODES:
-            raise ValueError(f"pressure_equation={p.pressure_equation!r}: 'reference' or 'consistent'")
-        self.consistent = p.pressure_equation == "consistent"
+        if p.pressure_equation not in PRESSURE_EQUATIONS:
+            raise ValueError(f"pressure_equation={p.pressure_equation!r}: 'reference', 'consistent' or 'consistent_cu'")
+        self.consistent = p.pressure_equation == "consistent"          # the chip chain, with its budget protocol
+        self.consistent_cu = p.pressure_equation == "consistent_cu"    # the one-CU kernel: no budget, no retries
+        if self.consistent_cu and p.mapping != "cu":
+            raise ValueError(f"pressure_equation='consistent_cu' with mapping={p.mapping!r}: the one-CU kernel of the "
+                             f"consistent pressure equation takes mapping='cu' trials (a chip or shared trial takes "
+                             f"pressure_equation='consistent')")
         if self.consistent and p.mapping == "cu":
             raise ValueError("pressure_equation='consistent' with mapping='cu': the consistent pressure equation is solved "
                              "by launches over the whole chip, give the trial mapping=chip (or mapping=shared)")
@@ -603,6 +611,8 @@ class FVSolver(LidDrivenCavitySolver):
             self.t["scratch"] = torch.zeros(F.wide_scratch_len(nx, ny), **f64)
         if self.consistent:                       # CG iterations, solves, cap hits, the last solve's count (pfinish)
             self.t["pstats"] = torch.zeros(F.WIDE_PRESSURE_SCRATCH_LEN, dtype=torch.int64, device=self.device)
+        if self.consistent_cu:                    # the same four words, added to by the one-CU kernel with ctrl
+            self.t["pstats"] = torch.zeros(F.PRESSURE_STATS_LEN, dtype=torch.int64, device=self.device)
         self.linear_budget = int(p.linear_budget)        # grows when a solve overflows it (advance_with_budget)
         self.linear_budget_retries = 0
         self.pressure_budget = int(p.pressure_budget)    # likewise (advance_with_budgets)
@@ -637,6 +647,9 @@ class FVSolver(LidDrivenCavitySolver):
                 h = C.c_void_p()
                 F.check(F.lib().ldc_fv_create(C.byref(pr), C.byref(h)), "ldc_fv_create")
                 self._handle = h
+                if self.consistent_cu:
+                    F.set_pressure(h, "consistent", float(self.params.pressure_tol), int(self.params.pressure_max_iters),
+                                   self.t["pstats"].data_ptr(), self.t["pstats"].numel())
             if self.chip:
                 h = C.c_void_p()
                 F.check(F.lib().ldc_fv_wide_create(C.byref(pr), self.t["scratch"].data_ptr(),
@@ -732,7 +745,7 @@ class FVSolver(LidDrivenCavitySolver):
         p = self.params
         self.linear_budget, self.linear_budget_retries = int(p.linear_budget), 0
         self.pressure_budget, self.pressure_budget_retries = int(p.pressure_budget), 0
-        if self.consistent:
+        if self.consistent or self.consistent_cu:
             self.t["pstats"].zero_()
 
     def state(self) -> dict:
@@ -750,6 +763,10 @@ class FVSolver(LidDrivenCavitySolver):
             out.update(pressure_iterations=int(ps[F.PSTAT_ITERS]), pressure_solves=int(ps[F.PSTAT_SOLVES]),
                        pressure_caps=int(ps[F.PSTAT_CAPS]), pressure_last=int(ps[F.PSTAT_LAST]),
                        pressure_budget_retries=int(self.pressure_budget_retries))
+        if self.consistent_cu:                    # (no budget on this mapping: no retries to report)
+            ps = self.t["pstats"].cpu().numpy()
+            out.update(pressure_iterations=int(ps[F.PSTAT_ITERS]), pressure_solves=int(ps[F.PSTAT_SOLVES]),
+                       pressure_caps=int(ps[F.PSTAT_CAPS]), pressure_last=int(ps[F.PSTAT_LAST]))
         return out
 
     def step_debug(self, which=F.DBG) -> dict:

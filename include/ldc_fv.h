@@ -1,6 +1,6 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
  * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc and
- * csrc/ldc_fv_wide_pressure.inc, csrc/ldc_fv_sample.hip).
+ * csrc/ldc_fv_wide_pressure.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -170,6 +170,30 @@
  *    returns from the exact solve's GEMMs.  A batch without a consistent trial runs the plain chain, launch for launch.
  *  The mixing chain of ldc_fv_wide_set_anderson follows `record` as before.
  *
+ * The consistent pressure equation of a one-CU trial (ldc_fv_set_pressure; csrc/ldc_fv_cu_pressure.hip, a unit of its own so
+ * that the code object of the reference kernel stays what it was).  The same equation, operator, right-hand side,
+ * preconditioner, stop rule, cap, p' = x - x_0 and face correction as above, for an ldc_fv handle: one work-group of 512
+ * threads advances the trial for the whole chunk, as the reference kernel does, and ldc_fv_enqueue / ldc_fv_batch_enqueue
+ * send each handle to the kernel of its mode (a list of both modes is two launch groups; ldc_fv_anderson_enqueue reaches the
+ * solve through ldc_fv_batch_enqueue, so the mixing kernel follows either).
+ *  - the CG loop runs inside the work-group, between barriers where the chip chain has launch boundaries: b and |b|^2; per
+ *    iteration the stop test, the four GEMMs of z = L+ r, r.z, p = z + beta p (one copy of p: the barrier does what the two
+ *    alternating copies do), q = A p and p.q, x += alpha p, r -= alpha q and |r|^2.  There is no budget and no overflow: the
+ *    loop ends inside the kernel, as BiCGSTAB does on this mapping;
+ *  - every stop decision is taken from totals that every thread holds identically, every loop is bounded (a NaN runs to
+ *    max_iters and the record's NaN then stops the trial, ctrl[2]), and the sums run in one fixed order (per thread in
+ *    increasing cell, wave shuffles, the waves in order from LDS; no atomics): lone runs, batches and repeats agree bit
+ *    for bit, whatever the chunks.  The order differs from the chip chain's: the two agree to rounding;
+ *  - the work vectors are the chip chain's (mdot* in 9 .. 11, r 12, z 13, p 14, q 16, x 26): after one iteration `work`
+ *    reads as after a chip iteration, rhs_p at 23 with entry 0 = 0 and x at 26;
+ *  - statistics: LDC_FV_PRESSURE_STATS_LEN int64 words of the caller's, to which thread 0 adds the launch's increments
+ *    when it writes ctrl back: [0] CG iterations in all, [1] solves, [2] cap hits, [3] the last solve's count.  Zero them
+ *    with ctrl;
+ *  - the block (tolerance, cap, mode, statistics pointer: 24 bytes) lives at byte 384 of the descriptor slot in the tail of
+ *    `work`, clear of the descriptor (< 256), the post block (256 .. 327) and the mixing kernel's kept row (448 .. 511);
+ *  - ldc_fv_step_debug on such a handle returns LDC_E_ARG: the debug kernel is the reference iteration.  The work vectors
+ *    hold the intermediates.  ldc_fv_post_enqueue and ldc_fv_prolong_enqueue take the handle as any other.
+ *
  * Post-processing and prolongation of such a trial (ldc_fv_wide_post_enqueue, ldc_fv_wide_prolong_enqueue; the same
  * unit): what ldc_fv_post_enqueue and ldc_fv_prolong_enqueue do for a trial of up to LDC_FV_MAX_N cells per axis, by the
  * chip mapping's rules for LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N: one launch per phase, a grid that depends on (nx, ny) alone,
@@ -254,6 +278,7 @@ extern "C" {
 #define LDC_FV_WIDE_PRESSURE_LAUNCHES 7
 #define LDC_FV_WIDE_PRESSURE_BUDGET_DEFAULT 12
 #define LDC_FV_WIDE_PRESSURE_SCRATCH_LEN 4
+#define LDC_FV_PRESSURE_STATS_LEN 4 /* the statistics words of ldc_fv_set_pressure (a one-CU trial) */
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
 #define LDC_FV_DBG_GRAD_P 0        /* 2n: d/dx p, then d/dy p                                    */
@@ -357,8 +382,16 @@ int ldc_fv_batch_enqueue(ldc_fv *const *hs, int n, int n_iters, void *stream);
 /* 0, or LDC_FV_E_NAN when the trial stopped on a NaN (reads ctrl through the library's own stream: wait for the */
 /* stream of the trial's launches first). */
 int ldc_fv_status(ldc_fv *h);
-/* One iteration, copying the intermediates selected by `which` into out[k] (device pointers). */
+/* One iteration, copying the intermediates selected by `which` into out[k] (device pointers).  LDC_E_ARG for a handle in */
+/* mode LDC_FV_PRESSURE_CONSISTENT (its work vectors hold the intermediates).                                              */
 int ldc_fv_step_debug(ldc_fv *h, int which, double *const *out, void *stream);
+/* The pressure equation of a one-CU trial: cfg == NULL or mode LDC_FV_PRESSURE_REFERENCE is the kernel of a new handle;     */
+/* mode LDC_FV_PRESSURE_CONSISTENT the one described above, with `stats` a device buffer of stats_len >=                      */
+/* LDC_FV_PRESSURE_STATS_LEN int64 words owned by the caller.  Call it between solves, with nothing of the handle in flight   */
+/* (one synchronous copy into the tail of `work` on the library's own stream).  Validation comes first and needs no device:   */
+/* LDC_E_STATE for a null handle; LDC_E_ARG for another mode, max_iters < 1, tol outside (0, 1) or NaN, a null or short       */
+/* stats.  A refused call leaves the handle as it was.                                                                        */
+int ldc_fv_set_pressure(ldc_fv *h, const struct ldc_fv_pressure *cfg, int64_t *stats, int64_t stats_len);
 /* omega, psi and the result block of n trials (any sizes, one device), one work-group each; trial q takes posts[q]. */
 /* Validation comes first and needs no device.  The trials must not be in flight on another stream.                  */
 int ldc_fv_post_enqueue(ldc_fv *const *hs, const struct ldc_fv_post *posts, int n, void *stream);
