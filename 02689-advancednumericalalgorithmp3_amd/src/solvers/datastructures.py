@@ -138,6 +138,13 @@ class FVParameters(Parameters):
     pressure_tol: float = 1e-8
     pressure_max_iters: int = 200
     pressure_budget: int = 12
+    # how the vortices are read off the result.  streamfunction: "reference" (psi = 0 at the centres of the boundary ring
+    # of cells, the reference's rule, by whichever vortex_metrics route) or "wall" (psi = 0 on the wall faces and the lid
+    # profile in omega's ghost row: second order; ldc_fv_wall_post_enqueue, always on the device, any mapping and size).
+    # vortex_refine: "none" (every centre is a cell centre) or "quadratic" (the extremum of the quadratic through the
+    # 3 x 3 cells around it; "wall" only).  Both change the reported metrics: they go to MLflow
+    streamfunction: str = "reference"
+    vortex_refine: str = "none"
 
     def to_mlflow(self) -> dict:
         skip = {"device", "check_every", "vortex_metrics", "mapping", "linear_budget"}

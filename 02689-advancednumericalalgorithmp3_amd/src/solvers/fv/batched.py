@@ -190,10 +190,10 @@ class BatchedFVSolver:
         work = [0 if q in self.errors else total * s.nx * s.ny + (extra_work[q] if extra_work else 0)
                 for q, (s, (_, _, total, _)) in enumerate(zip(self.solvers, out))]
         work_all = max(1, sum(work))
-        # the device paths of the vortex metrics ("device" and "chip"): every finished trial that asks for one in one go (_store_results below
+        # the device paths of the vortex metrics ("device", "chip" and streamfunction="wall"): every finished trial that asks for one in one go (_store_results below
         # finds its result block); a trial in `errors` is left alone
         postprocess([s for q, s in enumerate(self.solvers)
-                     if q not in self.errors and s.params.vortex_metrics in ("device", "chip")])
+                     if q not in self.errors and (s.params.vortex_metrics in ("device", "chip") or s.params.streamfunction == "wall")])
         for q, (s, (done, _, total, hist)) in enumerate(zip(self.solvers, out)):
             if q in self.errors:
                 continue

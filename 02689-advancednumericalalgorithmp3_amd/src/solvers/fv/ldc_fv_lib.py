@@ -35,6 +35,13 @@ CTRL_DONE, CTRL_ITER, CTRL_NAN, CTRL_GIVEUP, CTRL_LIN_ITERS, CTRL_SOLVES = range
 (POST_PSI_MIN, POST_OMEGA_CENTER, POST_OMEGA_MAX, POST_PSI_BR, POST_PSI_BL, POST_PSI_TL, POST_PSI_MIN_CELL,
  POST_OMEGA_MAX_CELL, POST_PSI_BR_CELL, POST_PSI_BL_CELL, POST_PSI_TL_CELL, POST_NONFINITE) = range(12)
 POST_RESULT_LEN = 16
+# ldc_fv_wall_post_enqueue: jobs per launch, the result block (the POST_* slots, then four groups of WALL_GROUP_LEN doubles:
+# the primary minimum, BR, BL, TL), the slots of a group and its status codes (LDC_FV_WALL_*)
+WALL_LAUNCH_MAX = 24
+WALL_GROUP_LEN, WALL_RESULT_LEN = 8, 48
+WALL_X, WALL_Y, WALL_PSI, WALL_OMEGA, WALL_STATUS, WALL_SX, WALL_SY = range(7)
+WALL_NOT_ASKED, WALL_REFINED, WALL_NO_CANDIDATE, WALL_INDEFINITE, WALL_REJECTED = -1, 0, 1, 2, 3
+WALL_POST_LAUNCHES = 7         # omega | gemm x 4 | extrema | result, per group of WALL_LAUNCH_MAX jobs
 DBG = ("grad_p", "diag", "b", "u_star", "v_star", "mdot_star", "rhs_p", "p_prime", "u_prime", "v_prime", "mdot")
 
 _dp = C.c_void_p
@@ -79,6 +86,15 @@ class SampleJob(C.Structure):
     )
 
 
+class WallJob(C.Structure):
+    """Mirror of ``struct ldc_fv_wall_job`` -- keep field order in sync with the header."""
+    _fields_ = (
+        [(n, _dp) for n in ("u", "v", "ulid", "Cx", "lamx", "Cy", "lamy", "psi", "omega", "scratch", "result")]
+        + [("dx", C.c_double), ("dy", C.c_double)]
+        + [(n, C.c_int32) for n in ("nx", "ny", "ix_lt", "ix_gt", "jy_lt", "jy_gt", "refine", "pad")]
+    )
+
+
 # every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
            "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_set_pressure", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
@@ -87,7 +103,8 @@ EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue"
            "ldc_fv_wide_batch_destroy", "ldc_fv_wide_batch_enqueue", "ldc_fv_wide_batch_set_graph",
            "ldc_fv_wide_batch_launches", "ldc_fv_wide_post_enqueue", "ldc_fv_wide_post_launches",
            "ldc_fv_wide_prolong_enqueue", "ldc_fv_wide_set_anderson", "ldc_fv_wide_set_pressure",
-           "ldc_fv_wide_set_pressure_budget", "ldc_fv_wide_batch_set_pressure_budget", "ldc_fv_sample_nodes")
+           "ldc_fv_wide_set_pressure_budget", "ldc_fv_wide_batch_set_pressure_budget", "ldc_fv_sample_nodes",
+           "ldc_fv_wall_post_enqueue", "ldc_fv_wall_post_launches")
 
 _bound = None
 
@@ -119,6 +136,11 @@ def wide_post_scratch_len(nx: int, ny: int) -> int:
     """LDC_FV_WIDE_POST_SCRATCH_LEN: one slot of 12 doubles per work-group of a cell sweep (five keys, five cells, two
     not-finite flags)."""
     return 12 * wide_groups(nx, ny)
+
+
+def wall_scratch_len(nx: int, ny: int) -> int:
+    """LDC_FV_WALL_SCRATCH_LEN: two fields of n doubles, then one slot of 12 doubles per work-group of a cell sweep."""
+    return 2 * nx * ny + 12 * wide_groups(nx, ny)
 
 
 def wide_anderson_scratch_len(nx: int, ny: int, depth: int) -> int:
@@ -176,6 +198,8 @@ def lib() -> C.CDLL:
         L.ldc_fv_wide_set_pressure_budget.argtypes = [_dp, C.c_int]
         L.ldc_fv_wide_batch_set_pressure_budget.argtypes = [_dp, C.c_int]
         L.ldc_fv_sample_nodes.argtypes = [C.POINTER(SampleJob), C.c_int, _dp]
+        L.ldc_fv_wall_post_enqueue.argtypes = [C.POINTER(WallJob), C.c_int, _dp]
+        L.ldc_fv_wall_post_launches.argtypes = [C.c_int]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -278,3 +302,10 @@ def sample_nodes(jobs, stream) -> None:
     checks first and launches SAMPLE_LAUNCH_MAX at a time; nothing synchronises."""
     arr = (SampleJob * len(jobs))(*jobs)
     check(lib().ldc_fv_sample_nodes(arr, len(jobs), _dp(stream)), "ldc_fv_sample_nodes")
+
+
+def wall_post_enqueue(jobs, stream) -> None:
+    """omega, the wall-anchored psi and the result block of every ``WallJob`` (include/ldc_fv.h): ONE call for all jobs,
+    which the library checks first and launches WALL_LAUNCH_MAX at a time, seven launches each; nothing synchronises."""
+    arr = (WallJob * len(jobs))(*jobs)
+    check(lib().ldc_fv_wall_post_enqueue(arr, len(jobs), _dp(stream)), "ldc_fv_wall_post_enqueue")

@@ -11,6 +11,9 @@ kernel's exact pressure-correction solve uses, and, once per solve, the vortex m
 solve (``vortex_metrics="host"``, the default) or on the device (``"device"``: ``ldc_fv_post_enqueue``, one work-group
 per trial, the same quantities by the same rules; ``"chip"``: ``ldc_fv_wide_post_enqueue``, the whole chip per trial, for
 ``mapping="chip"`` and ``"shared"`` trials of up to 1024 cells per axis, the same bits as ``"device"`` where both exist).
+``streamfunction="wall"`` reads the vortices by a second-order rule instead of the reference's (psi = 0 on the wall faces,
+the lid profile in omega's ghost row; ``vortex_refine="quadratic"``: sub-cell centres), always on the device and for every
+mapping and size (``ldc_fv_wall_post_enqueue``: the wall trials of a call share seven launches per 24 of them).
 """
 from __future__ import annotations
 
@@ -33,6 +36,8 @@ MAPPINGS = ("cu", "chip", "shared")
 # "consistent": the chain of launches over the whole chip (mapping "chip" / "shared"); "consistent_cu": the same equation
 # inside the work-group of a one-CU trial (mapping "cu"); both are LDC_FV_PRESSURE_CONSISTENT to the library
 PRESSURE_EQUATIONS = ("reference", "consistent", "consistent_cu")
+STREAMFUNCTIONS = ("reference", "wall")
+VORTEX_REFINES = ("none", "quadratic")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
 
 
@@ -89,6 +94,34 @@ def sine_eig(m: int, device=None):
     return _sine_cache[key]
 
 
+_wall_cache = {}
+
+
+def wall_eig_host(n: int):
+    """(eigenvalues ascending, eigenvectors as columns) of the n x n second difference tridiag(-1, 2, -1) with 3 in both
+    corners (the ghost cell is minus its neighbour: zero on the wall FACE), analytic: C[j, k] = sqrt(2 / n)
+    sin(pi (k + 1)(j + 1/2) / n), the last column divided by sqrt(2); lam[k] = 2 - 2 cos(pi (k + 1) / n).  Not symmetric."""
+    k = np.arange(1, n + 1, dtype=np.float64)
+    j = np.arange(n, dtype=np.float64) + 0.5
+    Cm = np.sqrt(2.0 / n) * np.sin(np.pi * np.outer(j, k) / n)
+    Cm[:, -1] /= np.sqrt(2.0)
+    return 2.0 - 2.0 * np.cos(np.pi * k / n), Cm
+
+
+def wall_eig(n: int, device=None):
+    """``wall_eig_host(n)``; with a ``device`` as float64 tensors there, cached per (n, device), as ``sine_eig``."""
+    if device is None:
+        return wall_eig_host(n)
+    import torch
+    device = torch.device(device)
+    key = (int(n), device.type, torch.cuda.current_device() if device.index is None else device.index)
+    if key not in _wall_cache:
+        lam, Cm = wall_eig_host(n)
+        _wall_cache[key] = (torch.tensor(lam, dtype=torch.float64, device=device),
+                            torch.tensor(Cm, dtype=torch.float64, device=device).contiguous())
+    return _wall_cache[key]
+
+
 def mask_bounds(xs, ys):
     """The corner regions of ``compute_vortex_metrics`` as index bounds on the sorted cell-centre coordinates:
     xs < 0.5 is i < ix_lt, xs > 0.5 is i >= ix_gt, likewise ys (absolute coordinates, as the reference's masks)."""
@@ -96,10 +129,14 @@ def mask_bounds(xs, ys):
             int(np.count_nonzero(ys < 0.5)), int(ys.size - np.count_nonzero(ys > 0.5)))
 
 
-def post_route(vortex_metrics: str, has_cu_handle: bool) -> str:
-    """The entry that post-processes a trial: ``"chip"`` (``ldc_fv_wide_post_enqueue``, a chain of launches over the
+def post_route(vortex_metrics: str, has_cu_handle: bool, streamfunction: str = "reference") -> str:
+    """The entry that post-processes a trial: ``"wall"`` (``ldc_fv_wall_post_enqueue``, launches shared by the wall trials
+    of the call) for a ``streamfunction="wall"`` trial, whatever ``vortex_metrics`` says and for every mapping and size;
+    else ``"chip"`` (``ldc_fv_wide_post_enqueue``, a chain of launches over the
     whole chip for this trial alone) when the trial asks for it or has no one-CU handle, else ``"cu"``
     (``ldc_fv_post_enqueue``, one work-group, beside the other such trials of the call)."""
+    if streamfunction == "wall":
+        return "wall"
     return "chip" if vortex_metrics == "chip" or not has_cu_handle else "cu"
 
 
@@ -117,28 +154,34 @@ def prolong_route(coarse_has_cu: bool, fine_has_cu: bool, coarse_chip: bool, fin
 
 def postprocess(trials):
     """omega, psi and the vortex extrema of ``trials`` (FVSolvers on one device, none in flight) on the device: one
-    launch per 256 trials of the one-CU route and one chain of launches per trial of the chip route (``post_route``),
-    then ONE copy of all result blocks.  ``psi`` and ``omega`` stay on the device as ``t["psi"]``, ``t["omega"]``; every
+    launch per 256 trials of the one-CU route, one chain of launches per trial of the chip route and one chain per 24
+    trials of the wall route (``post_route``), then ONE copy of all result blocks (rows of ``WALL_RESULT_LEN`` doubles when
+    the call has a wall trial: the ``POST_*`` slots come first either way).  ``psi`` and ``omega`` stay on the device as ``t["psi"]``, ``t["omega"]``; every
     trial keeps its row of the result blocks for ``compute_vortex_metrics``."""
     import torch
     from solvers.spectral import ldc_lib
     if not trials:
         return
-    routes = [post_route(s.params.vortex_metrics, s._has_cu_handle) for s in trials]
+    routes = [post_route(s.params.vortex_metrics, s._has_cu_handle, s.params.streamfunction) for s in trials]
     for s, route in zip(trials, routes):
         if route == "cu":
             s._require_cu_handle("postprocess")
-        elif s._wide is None:
+        elif route == "chip" and s._wide is None:
             raise ValueError(f"postprocess: a trial of {s.nx} x {s.ny} cells with mapping={s.params.mapping!r} has no "
                              f"whole-chip handle")
     dev = trials[0].device
     index = torch.cuda.current_device() if dev.index is None else dev.index
     with torch.cuda.device(dev):
-        results = torch.zeros((len(trials), F.POST_RESULT_LEN), dtype=torch.float64, device=dev)
-        posts = []
+        width = F.WALL_RESULT_LEN if "wall" in routes else F.POST_RESULT_LEN
+        results = torch.zeros((len(trials), width), dtype=torch.float64, device=dev)
+        posts, jobs = [], []
         for q, s in enumerate(trials):
             if (torch.cuda.current_device() if s.device.index is None else s.device.index) != index:
                 raise ValueError("postprocess: all trials must be on one device")
+            if routes[q] == "wall":
+                posts.append(None)
+                jobs.append(s._wall_job(results[q].data_ptr()))
+                continue
             lamx, Sx = sine_eig(s.nx - 2, dev)
             lamy, Sy = sine_eig(s.ny - 2, dev)
             for name in ("psi", "omega"):
@@ -162,6 +205,8 @@ def postprocess(trials):
             for q in chip:
                 scratch = trials[q].t["post_scratch"]
                 F.wide_post_enqueue(trials[q]._wide, posts[q], scratch.data_ptr(), scratch.numel(), stream)
+            if jobs:
+                F.wall_post_enqueue(jobs, stream)
             rows = results.cpu().numpy()          # (synchronises the stream)
     for s, row in zip(trials, rows):
         s._post = row.copy()
@@ -519,6 +564,14 @@ class FVSolver(LidDrivenCavitySolver):
             raise ValueError(f"limiter={p.limiter!r}: the TVD scheme of the reference is MUSCL")
         if p.vortex_metrics not in VORTEX_METRICS:
             raise ValueError(f"vortex_metrics={p.vortex_metrics!r}: 'host', 'device' or 'chip'")
+        if p.streamfunction not in STREAMFUNCTIONS:
+            raise ValueError(f"streamfunction={p.streamfunction!r}: 'reference' or 'wall'")
+        if p.vortex_refine not in VORTEX_REFINES:
+            raise ValueError(f"vortex_refine={p.vortex_refine!r}: 'none' or 'quadratic'")
+        if p.vortex_refine == "quadratic" and p.streamfunction != "wall":
+            raise ValueError("vortex_refine='quadratic' with streamfunction='reference': the ring rule's O(h) error in psi "
+                             "makes sub-cell centres moot, give the trial streamfunction='wall'")
+        self.vortex_refine_status = None         # per (primary, BR, BL, TL) after a refined compute_vortex_metrics()
         if p.acceleration not in ACCELERATIONS:
             raise ValueError(f"acceleration={p.acceleration!r}: 'none', 'anderson' or 'anderson_chip'")
         if not 1 <= int(p.anderson_depth) <= F.ANDERSON_MAX_DEPTH:
@@ -882,6 +935,9 @@ class FVSolver(LidDrivenCavitySolver):
         return psi
 
     def compute_vortex_metrics(self) -> dict:
+        # (getattr: tests/fv_post_numpy.py calls this method on a bare namespace that has only the host branch's parameters)
+        if getattr(self.params, "streamfunction", "reference") == "wall":
+            return self._wall_vortex_metrics()
         if self.params.vortex_metrics in ("device", "chip"):
             return self._device_vortex_metrics()
         omega = self._vorticity()
@@ -925,6 +981,51 @@ class FVSolver(LidDrivenCavitySolver):
                 out.update({f"psi_{name}": val, f"psi_{name}_x": x, f"psi_{name}_y": y})
             else:
                 out.update({f"psi_{name}": 0.0, f"psi_{name}_x": 0.0, f"psi_{name}_y": 0.0})
+        return out
+
+    # ---- the wall rule (ldc_fv_wall_post_enqueue) ---------------------------------------------------------------
+    def _wall_job(self, result_ptr: int) -> F.WallJob:
+        """This trial's job of a ``wall_post_enqueue`` call: the state, the tables of its sizes (shared per device), its own
+        psi, omega and scratch, and the row of the call's result tensor."""
+        import torch
+        dev, t = self.device, self.t
+        lamx, Cx = wall_eig(self.nx, dev)
+        lamy, Cy = wall_eig(self.ny, dev)
+        for name, size in (("psi", self.n_cells), ("omega", self.n_cells),
+                           ("wall_scratch", F.wall_scratch_len(self.nx, self.ny))):
+            if name not in t:
+                t[name] = torch.zeros(size, dtype=torch.float64, device=dev)
+        ix_lt, ix_gt, jy_lt, jy_gt = self._mask_bounds
+        return F.WallJob(u=t["u"].data_ptr(), v=t["v"].data_ptr(), ulid=t["ulid"].data_ptr(), Cx=Cx.data_ptr(),
+                         lamx=lamx.data_ptr(), Cy=Cy.data_ptr(), lamy=lamy.data_ptr(), psi=t["psi"].data_ptr(),
+                         omega=t["omega"].data_ptr(), scratch=t["wall_scratch"].data_ptr(), result=result_ptr,
+                         dx=self.dx_min, dy=self.dy_min, nx=self.nx, ny=self.ny, ix_lt=ix_lt, ix_gt=ix_gt, jy_lt=jy_lt,
+                         jy_gt=jy_gt, refine=int(self.params.vortex_refine == "quadratic"), pad=0)
+
+    def _wall_vortex_metrics(self) -> dict:
+        """The metrics dict of a wall trial from its result block: the primary minimum and the corners from the groups
+        (refined, or the cell's own values), under the existing rule that a corner counts when its grid value is > 0;
+        ``omega_max`` stays on the grid.  ``omega_BR`` / ``omega_BL`` / ``omega_TL`` are filled."""
+        if self._post is None or len(self._post) < F.WALL_RESULT_LEN:
+            postprocess([self])
+        r, self._post = self._post, None
+        if r[F.POST_NONFINITE] != 0:
+            raise FloatingPointError("vortex metrics: omega or psi is not finite")
+        groups = r[F.POST_RESULT_LEN: F.WALL_RESULT_LEN].reshape(4, F.WALL_GROUP_LEN)
+        refined = self.params.vortex_refine == "quadratic"
+        self.vortex_refine_status = tuple(int(g[F.WALL_STATUS]) for g in groups) if refined else None
+        cmax = int(r[F.POST_OMEGA_MAX_CELL])
+        xs, ys = np.sort(np.unique(self.fields.x)), np.sort(np.unique(self.fields.y))      # (as the other two routes)
+        g = groups[0]
+        out = dict(psi_min=float(g[F.WALL_PSI]), psi_min_x=float(g[F.WALL_X]), psi_min_y=float(g[F.WALL_Y]),
+                   omega_center=float(g[F.WALL_OMEGA]), omega_max=float(r[F.POST_OMEGA_MAX]),
+                   omega_max_x=float(xs[cmax % self.nx]), omega_max_y=float(ys[cmax // self.nx]))
+        for q, name in enumerate(("BR", "BL", "TL")):
+            g = groups[1 + q]
+            keep = float(r[F.POST_PSI_BR + q]) > 0
+            vals = (g[F.WALL_PSI], g[F.WALL_OMEGA], g[F.WALL_X], g[F.WALL_Y]) if keep else (0.0, 0.0, 0.0, 0.0)
+            out.update({f"psi_{name}": float(vals[0]), f"omega_{name}": float(vals[1]), f"psi_{name}_x": float(vals[2]),
+                        f"psi_{name}_y": float(vals[3])})
         return out
 
     def _post_field(self, name) -> np.ndarray:

@@ -1,6 +1,6 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
  * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc and
- * csrc/ldc_fv_wide_pressure.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip).
+ * csrc/ldc_fv_wide_pressure.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip, csrc/ldc_fv_wall_post.hip).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -223,6 +223,46 @@
  *    element (ix, iy) at (ix - 1)(My - 2) + (iy - 1);
  *  - blockIdx.y is the job and the work-groups of a job stride over its nodes: no waits, no atomics, no LDS, so a job's
  *    result does not depend on what else is in the call, bit for bit.
+ *
+ * Wall-anchored streamfunction and sub-cell vortex centres (csrc/ldc_fv_wall_post.hip, ldc_fv_wall_post_enqueue): a second
+ * post-processing rule beside the reference's above, whose psi = 0 at the CENTRES of the boundary ring is an O(h) error
+ * under the lid and whose centres are cell centres.  A job holds raw device pointers only, no handle, so a trial of any
+ * mapping is served, LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N cells per axis; the state is only read.
+ *  - omega (ny x nx): as above, but the ghost above the top row is 2 ulid[i] - u, the lid PROFILE, not the scalar
+ *    lid_velocity (second order for the smoothed lids too).  Nothing writes psi in this phase;
+ *  - psi (ny x nx): (cx Tx + cy Ty) psi = omega on ALL nx x ny cells, T_n = tridiag(-1, 2, -1) with T[0][0] = T[n-1][n-1] = 3
+ *    (the ghost is -psi: psi = 0 on the wall face), cx = 1/dx^2, cy = 1/dy^2, solved exactly with T_n = C Lam C^T,
+ *    lam[k] = 2 - 2 cos(pi (k+1)/n), C[j][k] = sqrt(2/n) sin(pi (k+1)(j+1/2)/n) for k = 0 .. n-1 with the last column
+ *    (k = n-1) divided by sqrt(2) (C row-major n x n, column k the k-th vector; NOT symmetric):
+ *    psi = Cy ((Cy^T Omega Cx) / (cy lamy[a] + cx lamx[b])) Cx^T, four GEMMs, the second with the division in its epilogue;
+ *  - the extrema: the five candidates, the four index bounds and the tie rule (lowest cell) of ldc_fv_post_enqueue;
+ *  - result: LDC_FV_WALL_RESULT_LEN doubles.  Slots 0 .. 15 are the LDC_FV_POST_* slots.  Then four groups of
+ *    LDC_FV_WALL_GROUP_LEN doubles for the primary minimum, BR, BL and TL: x, y, psi, omega, status, sx, sy, 0
+ *    (LDC_FV_WALL_X ..).  With refine = 0 a group carries the cell's own values (x = (i + 1/2) dx, y = (j + 1/2) dy) and
+ *    status -1; a group without a cell (-1) is all zeros but for its status;
+ *  - refine = 1: per extremum the 3 x 3 stencil of psi around its cell (i, j), cells outside the grid filled by odd
+ *    reflection (the mirror cell's -psi, +psi across a corner).  In index units
+ *      gx = (E - W)/2, gy = (N - S)/2, Hxx = E - 2C + W, Hyy = N - 2C + S, Hxy = (NE - NW - SE + SW)/4,
+ *      det = Hxx Hyy - Hxy^2, sx = -(Hyy gx - Hxy gy)/det, sy = -(Hxx gy - Hxy gx)/det,
+ *      x = (i + 1/2 + sx) dx, y = (j + 1/2 + sy) dy, psi* = C + (gx sx + gy sy)/2,
+ *    and omega* is the same six-term quadratic of omega, C + gx sx + gy sy + Hxx sx^2/2 + Hyy sy^2/2 + Hxy sx sy with the
+ *    stencil of omega, where the cell is not on the boundary ring; on the ring it is the cell's omega.  Definiteness is
+ *    judged against rounding, with eps = 2^-52 and the floors Fxx = 4 eps (|E| + 2|C| + |W|), Fyy = 4 eps (|N| + 2|C| + |S|),
+ *    Fxy = eps (|NE| + |NW| + |SE| + |SW|): a fit counts only if |Hxx| > Fxx, |Hyy| > Fyy,
+ *    det > Fxx |Hyy| + Fyy |Hxx| + 2 Fxy |Hxy| and Hxx > 0 for the minimum, < 0 for the three maxima.  No multiply-add of
+ *    this part is contracted (tests/fv_wall_post_numpy.py states it with the same roundings);
+ *  - status: 0 refined; 1 no candidate (cell -1, a corner value <= 0, or the not-finite flag); 2 flat or indefinite;
+ *    3 a result that is not finite, |sx| > 1, |sy| > 1, or a point outside [0, nx dx] x [0, ny dy].  Any status but 0
+ *    reports the cell's own x, y, psi and omega, and sx = sy = 0;
+ *  - the mapping: seven launches per group of up to LDC_FV_WALL_LAUNCH_MAX jobs (omega | gemm x 4 | extrema | result), the
+ *    launch boundary the only barrier, no waits, no atomics, every sum and merge in a fixed order.  blockIdx.y is the job
+ *    and blockIdx.x the work-group within it; the x extent is the largest count among the group's jobs and a work-group
+ *    beyond its own job's count returns at once.  Per job LDC_FV_WIDE_GROUPS(nx, ny) work-groups for the cell sweeps,
+ *    LDC_FV_WIDE_GEMM_GROUPS(nx, ny) for a GEMM, one for `result`; the job structs travel as kernel arguments.  A job's
+ *    psi, omega and block do not depend on what else is in the call, bit for bit;
+ *  - scratch: LDC_FV_WALL_SCRATCH_LEN(nx, ny) doubles per job, the caller's: two fields of n, then one slot of 12 doubles
+ *    per work-group of a sweep (five keys, five cells, two not-finite flags).  No two jobs of a call may share scratch,
+ *    psi, omega or result.
  */
 #ifndef LDC_FV_H
 #define LDC_FV_H
@@ -279,6 +319,19 @@ extern "C" {
 #define LDC_FV_WIDE_PRESSURE_BUDGET_DEFAULT 12
 #define LDC_FV_WIDE_PRESSURE_SCRATCH_LEN 4
 #define LDC_FV_PRESSURE_STATS_LEN 4 /* the statistics words of ldc_fv_set_pressure (a one-CU trial) */
+/* ldc_fv_wall_post_enqueue: jobs per launch (136 bytes per job in the arguments), the caller's scratch per job in doubles, */
+/* the result block (the LDC_FV_POST_* slots, then four groups) and the slots of a group                                   */
+#define LDC_FV_WALL_LAUNCH_MAX 24
+#define LDC_FV_WALL_SCRATCH_LEN(nx, ny) (2 * (int64_t)(nx) * (ny) + 12 * LDC_FV_WIDE_GROUPS(nx, ny))
+#define LDC_FV_WALL_GROUP_LEN 8
+#define LDC_FV_WALL_RESULT_LEN 48  /* LDC_FV_POST_RESULT_LEN + 4 groups: the primary minimum, BR, BL, TL */
+#define LDC_FV_WALL_X 0
+#define LDC_FV_WALL_Y 1
+#define LDC_FV_WALL_PSI 2
+#define LDC_FV_WALL_OMEGA 3
+#define LDC_FV_WALL_STATUS 4       /* -1 not asked for, 0 refined, 1 no candidate, 2 flat or indefinite, 3 rejected */
+#define LDC_FV_WALL_SX 5           /* the step from the cell centre, in cells */
+#define LDC_FV_WALL_SY 6
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
 #define LDC_FV_DBG_GRAD_P 0        /* 2n: d/dx p, then d/dy p                                    */
@@ -364,6 +417,19 @@ struct ldc_fv_sample_job {
   int32_t Mx, My;                 /* >= 3 each */
   double *U, *V;                  /* out: Mx * My each, element (ix, iy) at ix * My + iy */
   double *P;                      /* out: (Mx - 2) * (My - 2), the inner nodes */
+};
+
+struct ldc_fv_wall_job {
+  const double *u, *v, *ulid;     /* cell-centred state (ny x nx, c = j*nx + i), lid profile (nx) */
+  const double *Cx, *lamx, *Cy, *lamy; /* the tables above: nx x nx and ny x ny row-major, nx and ny */
+  double *psi, *omega;            /* out: ny x nx each */
+  double *scratch;                /* LDC_FV_WALL_SCRATCH_LEN(nx, ny) */
+  double *result;                 /* out: LDC_FV_WALL_RESULT_LEN */
+  double dx, dy;                  /* > 0 */
+  int32_t nx, ny;                 /* LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N each */
+  int32_t ix_lt, ix_gt;           /* as in ldc_fv_post: 0 .. nx */
+  int32_t jy_lt, jy_gt;           /* 0 .. ny */
+  int32_t refine, pad;            /* 0: the cells' own values in the groups; 1: the quadratic fit */
 };
 
 typedef struct ldc_fv ldc_fv;
@@ -494,6 +560,14 @@ int ldc_fv_wide_prolong_enqueue(ldc_fv_wide *coarse, ldc_fv_wide *fine, void *st
 /* LDC_E_NODEVICE.  That x and y lie inside the source's domain is the caller's to see to (a node outside is              */
 /* extrapolated from the last interval; no read leaves the source arrays).                                                */
 int ldc_fv_sample_nodes(const struct ldc_fv_sample_job *jobs, int n, void *stream);
+/* n jobs (a host array; every pointer inside a job is a device pointer, nothing of it in flight elsewhere): omega, psi and */
+/* the result block of every job as described above, ldc_fv_wall_post_launches(n) launches on `stream`, nothing            */
+/* synchronises.  Validation comes before any launch and needs no device: LDC_E_ARG for a null list or n < 1, for a null    */
+/* pointer in a job, for nx or ny outside LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N, for dx or dy not > 0, for a bound outside      */
+/* 0 .. nx (0 .. ny) and for refine other than 0 or 1; then LDC_E_NODEVICE.                                                 */
+int ldc_fv_wall_post_enqueue(const struct ldc_fv_wall_job *jobs, int n, void *stream);
+/* Kernel launches of that call: 7 per group of LDC_FV_WALL_LAUNCH_MAX jobs.  Needs no device; LDC_E_ARG for n < 1. */
+int ldc_fv_wall_post_launches(int n);
 
 #ifdef __cplusplus
 }
