@@ -1,8 +1,8 @@
 // ldc_fv_common.inc -- what all translation units of the finite-volume solver share (include/ldc_fv.h):
 // ldc_kernels.hip (through ldc_fv_kernel.inc, the SIMPLE iteration with one trial per CU), ldc_fv_wide.hip (the same
 // iteration by the whole chip), ldc_fv_post.hip (streamfunction and vortex metrics), ldc_fv_prolong.hip (coarse-to-fine
-// transfer of the state), ldc_fv_anderson.hip (Anderson mixing) and ldc_fv_cu_pressure.hip (the one-CU iteration with the
-// consistent pressure equation).
+// transfer of the state), ldc_fv_anderson.hip (Anderson mixing), ldc_fv_cu_pressure.hip (the one-CU iteration with the
+// consistent pressure equation) and ldc_fv_stretched.hip (the one-CU iteration on a wall-clustered grid).
 // Types, constants and host-side helpers (the fill of a descriptor, as_stream) only, no device function: each unit's
 // code object holds what that unit needs and depends on no other's.  The device functions that two mappings share are
 // in ldc_fv_cells.inc (the SIMPLE iteration), ldc_fv_post_cells.inc, ldc_fv_prolong_cells.inc and
@@ -45,6 +45,7 @@ static_assert(sizeof(FvDesc) <= LDC_FV_DESC_DOUBLES * sizeof(double), "descripto
 // The descriptor slot (LDC_FV_DESC_DOUBLES doubles = 512 bytes in the tail of `work`), byte by byte:
 //     0 .. 255  FvDesc (ldc_fv_create; it travels by value in the 256-byte table entry of a shared batch: it must not grow)
 //   256 .. 327  the post block (ldc_fv_post.hip, kFvPostOffset)
+//   328 .. 343  the grid block of a one-CU trial on a stretched grid (FvGridBlk below; ldc_fv_set_grid)
 //   384 .. 407  the pressure block of a one-CU trial (FvCuPcg below; ldc_fv_set_pressure)
 //   448 .. 511  the mixing kernel's kept record row (ldc_fv_anderson.hip, kFvAaKeepOffset)
 // The consistent pressure equation of a one-CU trial (ldc_fv_cu_pressure.hip): tolerance, cap, mode and the caller's four
@@ -59,6 +60,15 @@ static_assert(sizeof(FvDesc) <= 256, "the pressure block is clear of the descrip
 static_assert(kFvCuPcgOffset >= 256 + 72, "the pressure block is clear of the post block (ldc_fv_post.hip: 72 bytes at 256)");
 static_assert(kFvCuPcgOffset + sizeof(FvCuPcg) <= (LDC_FV_DESC_DOUBLES - LDC_FV_REC_LEN) * sizeof(double),
               "the pressure block is clear of the mixing kernel's kept row");
+
+// The per-axis geometry tables of a one-CU trial on a stretched grid (ldc_fv_stretched.hip), written by ldc_fv_set_grid with the
+// synchronous copy of ldc_fv_create: per axis [h (n) | d (n + 1) | g (n + 1)] (include/ldc_fv.h).
+struct FvGridBlk {
+  const double *ax, *ay;
+};
+constexpr int kFvGridOffset = 328;
+static_assert(kFvGridOffset >= 256 + 72 && kFvGridOffset + sizeof(FvGridBlk) <= kFvCuPcgOffset,
+              "the grid block is clear of the post block and of the pressure block");
 
 // host: the caller's stream handle of the C ABI
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -95,10 +105,16 @@ struct ldc_fv {
   int nx, ny;               // (host-side copies for validation: ldc_fv_prolong_enqueue)
   double dx, dy;
   int pressure_mode;        // LDC_FV_PRESSURE_*: the kernel that advances the trial (ldc_fv_set_pressure)
+  int grid_mode;            // LDC_FV_GRID_*: tables attached (ldc_fv_set_grid): fv_stretched_kernel advances the trial
 };
 
 // host: consistent handles (pressure_mode LDC_FV_PRESSURE_CONSISTENT) of the CURRENT device go to fv_cu_pressure_kernel,
 // LDC_FV_LAUNCH_MAX per launch (ldc_fv_cu_pressure.hip; called by ldc_fv_enqueue and ldc_fv_batch_enqueue only)
 __attribute__((visibility("hidden"))) int ldc_fv_cu_pressure_launch(ldc_fv* const* hs, int n, int n_iters, void* stream);
+
+// host: handles with geometry tables (grid_mode LDC_FV_GRID_TABLES) of the CURRENT device, all in the pressure mode
+// `consistent` says, go to fv_stretched_kernel, LDC_FV_LAUNCH_MAX per launch (ldc_fv_stretched.hip; called by ldc_fv_enqueue and
+// ldc_fv_batch_enqueue only)
+__attribute__((visibility("hidden"))) int ldc_fv_stretched_launch(ldc_fv* const* hs, int n, int n_iters, int consistent, void* stream);
 
 #endif  // LDC_FV_COMMON_INC

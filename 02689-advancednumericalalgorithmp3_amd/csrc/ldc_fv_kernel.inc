@@ -35,7 +35,8 @@
 // (kFvThreads, kFvWaves, FvVec, FvDesc, fv_desc_of and struct ldc_fv: ldc_fv_common.inc, shared with the other FV
 // units; FvCtx, FvKrylov, fv_cell_*, fv_kry_*, fv_rec_* and fv_gemm_tile: ldc_fv_cells.inc, shared with ldc_fv_wide.hip;
 // FvLaunch, fv_reduce, fv_gemm, FvRed, FvRun and the seven phases: ldc_fv_cu_phases.inc, included below, shared with
-// ldc_fv_cu_pressure.hip -- the kernel of a handle in mode LDC_FV_PRESSURE_CONSISTENT, a unit of its own)
+// ldc_fv_cu_pressure.hip -- the kernel of a handle in mode LDC_FV_PRESSURE_CONSISTENT, a unit of its own -- and with
+// ldc_fv_stretched.hip, the kernel of a handle with geometry tables, ldc_fv_set_grid)
 
 namespace {
 
@@ -105,17 +106,28 @@ int fv_launch(ldc_fv* const* hs, int n, int n_iters, bool debug, const FvDebug& 
 
 // n_iters iterations of every handle, each by the kernel of its mode: the reference handles through fv_launch exactly as
 // before, in list order; the consistent ones (ldc_fv_set_pressure) through the launch function of ldc_fv_cu_pressure.hip,
-// in list order too.  A list of both modes is two launch groups; nothing waits for anything, so the order does not matter.
+// in list order too; the handles with geometry tables (ldc_fv_set_grid) through that of ldc_fv_stretched.hip, one group per
+// pressure mode.  A mixed list is up to four launch groups; nothing waits for anything, so the order does not matter.
 int fv_dispatch(ldc_fv* const* hs, int n, int n_iters, void* stream) {
-  int nc = 0;
-  for (int q = 0; q < n; ++q) nc += hs[q]->pressure_mode == LDC_FV_PRESSURE_CONSISTENT ? 1 : 0;
-  if (nc == 0) return fv_launch(hs, n, n_iters, false, FvDebug{}, stream);
-  if (nc == n) return ldc_fv_cu_pressure_launch(hs, n, n_iters, stream);
-  std::vector<ldc_fv*> ref, con;
-  for (int q = 0; q < n; ++q) (hs[q]->pressure_mode == LDC_FV_PRESSURE_CONSISTENT ? con : ref).push_back(hs[q]);
-  const int rc = fv_launch(ref.data(), (int)ref.size(), n_iters, false, FvDebug{}, stream);
-  if (rc != 0) return rc;
-  return ldc_fv_cu_pressure_launch(con.data(), (int)con.size(), n_iters, stream);
+  int count[4] = {0, 0, 0, 0};
+  const auto group = [](const ldc_fv* h) {
+    return (h->grid_mode == LDC_FV_GRID_TABLES ? 2 : 0) + (h->pressure_mode == LDC_FV_PRESSURE_CONSISTENT ? 1 : 0);
+  };
+  for (int q = 0; q < n; ++q) ++count[group(hs[q])];
+  const auto launch = [&](int g, ldc_fv* const* list, int m) {
+    if (g == 0) return fv_launch(list, m, n_iters, false, FvDebug{}, stream);
+    if (g == 1) return ldc_fv_cu_pressure_launch(list, m, n_iters, stream);
+    return ldc_fv_stretched_launch(list, m, n_iters, g == 3, stream);
+  };
+  for (int g = 0; g < 4; ++g) if (count[g] == n) return launch(g, hs, n);
+  for (int g = 0; g < 4; ++g) {
+    if (count[g] == 0) continue;
+    std::vector<ldc_fv*> part;
+    for (int q = 0; q < n; ++q) if (group(hs[q]) == g) part.push_back(hs[q]);
+    const int rc = launch(g, part.data(), (int)part.size());
+    if (rc != 0) return rc;
+  }
+  return 0;
 }
 
 }  // namespace
@@ -140,6 +152,7 @@ int ldc_fv_create(const struct ldc_fv_problem* pr, ldc_fv** out) {
   s->dev = slot; s->ctrl = h.ctrl; s->rec_cap = pr->rec_cap; s->device = dev;
   s->nx = pr->nx; s->ny = pr->ny; s->dx = pr->dx; s->dy = pr->dy;
   s->pressure_mode = LDC_FV_PRESSURE_REFERENCE;
+  s->grid_mode = LDC_FV_GRID_UNIFORM;
   *out = s;
   return 0;
 }
@@ -180,6 +193,21 @@ int ldc_fv_set_pressure(ldc_fv* h, const struct ldc_fv_pressure* cfg, int64_t* s
   return 0;
 }
 
+int ldc_fv_set_grid(ldc_fv* h, const struct ldc_fv_grid* grid) {
+  if (!h) return LDC_E_STATE;
+  if (!grid || grid->mode == LDC_FV_GRID_UNIFORM) {
+    h->grid_mode = LDC_FV_GRID_UNIFORM;
+    return 0;
+  }
+  if (grid->mode != LDC_FV_GRID_TABLES || !grid->x_tables || !grid->y_tables) return LDC_E_ARG;
+  if (grid->x_len < LDC_FV_GRID_TABLE_LEN(h->nx) || grid->y_len < LDC_FV_GRID_TABLE_LEN(h->ny)) return LDC_E_ARG;
+  const FvGridBlk blk = {grid->x_tables, grid->y_tables};
+  const hipError_t e = copy_now(reinterpret_cast<char*>(h->dev) + kFvGridOffset, &blk, sizeof(blk), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return (int)e;
+  h->grid_mode = LDC_FV_GRID_TABLES;
+  return 0;
+}
+
 int ldc_fv_status(ldc_fv* h) {
   if (!h) return LDC_E_STATE;
   long long flag = 0;
@@ -192,6 +220,7 @@ int ldc_fv_step_debug(ldc_fv* h, int which, double* const* out, void* stream) {
   if (!h) return LDC_E_STATE;
   if (which < 0 || which >= (1 << LDC_FV_DBG_COUNT) || (which && !out)) return LDC_E_ARG;
   if (h->pressure_mode != LDC_FV_PRESSURE_REFERENCE) return LDC_E_ARG;      // (the debug kernel is the reference iteration)
+  if (h->grid_mode != LDC_FV_GRID_UNIFORM) return LDC_E_ARG;                // (... on the uniform grid)
   FvDebug dbg = {};
   for (int k = 0; k < LDC_FV_DBG_COUNT; ++k) {
     if (!(which & (1 << k))) continue;

@@ -145,6 +145,12 @@ class FVParameters(Parameters):
     # 3 x 3 cells around it; "wall" only).  Both change the reported metrics: they go to MLflow
     streamfunction: str = "reference"
     vortex_refine: str = "none"
+    # the mesh: "uniform" (the reference's) or "tanh" (wall-clustered in both axes: vertices x_k = Lx s(k / nx),
+    # s(xi) = (1 + tanh(beta (2 xi - 1)) / tanh(beta)) / 2 with beta = grid_stretch >= 0, read only then; 0 gives uniform
+    # vertices through the stretched kernel).  mapping "cu" only, either pressure equation; no acceleration, sequencing,
+    # start_from, device or chip vortex metrics, wall streamfunction or refinement.  Both change results: they go to MLflow
+    grid: str = "uniform"
+    grid_stretch: float = 1.5
 
     def to_mlflow(self) -> dict:
         skip = {"device", "check_every", "vortex_metrics", "mapping", "linear_budget"}

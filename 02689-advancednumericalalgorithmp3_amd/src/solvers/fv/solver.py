@@ -14,6 +14,8 @@ per trial, the same quantities by the same rules; ``"chip"``: ``ldc_fv_wide_post
 ``streamfunction="wall"`` reads the vortices by a second-order rule instead of the reference's (psi = 0 on the wall faces,
 the lid profile in omega's ghost row; ``vortex_refine="quadratic"``: sub-cell centres), always on the device and for every
 mapping and size (``ldc_fv_wall_post_enqueue``: the wall trials of a call share seven launches per 24 of them).
+``grid="tanh"`` clusters the cells of a ``mapping="cu"`` trial at the walls (``ldc_fv_set_grid``: the same iteration with the
+geometry read from per-axis tables, either pressure equation); its vortex metrics are computed on the host.
 """
 from __future__ import annotations
 
@@ -38,6 +40,7 @@ MAPPINGS = ("cu", "chip", "shared")
 PRESSURE_EQUATIONS = ("reference", "consistent", "consistent_cu")
 STREAMFUNCTIONS = ("reference", "wall")
 VORTEX_REFINES = ("none", "quadratic")
+GRIDS = ("uniform", "tanh")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
 
 
@@ -57,6 +60,98 @@ def lid_profile(nx, Lx=1.0, lid_velocity=1.0, corner_treatment="none", corner_sm
             elif x_face > (Lx - d):
                 u[i] = 0.5 * (1 - np.cos(np.pi * (Lx - x_face) / d)) * lid_velocity
     return u
+
+
+def tanh_vertices(n: int, L: float, beta: float) -> np.ndarray:
+    """The n + 1 vertices of one axis of the wall-clustered grid: L s(k / n), s(xi) = (1 + tanh(beta (2 xi - 1)) / tanh(beta)) / 2,
+    s(xi) = xi at beta = 0."""
+    xi = np.arange(n + 1) / n
+    if beta == 0:
+        return L * xi
+    return L * (0.5 * (1.0 + np.tanh(beta * (2.0 * xi - 1.0)) / np.tanh(beta)))
+
+
+def axis_tables(xv):
+    """(centres, h, d, g) of one axis with the vertices ``xv``: widths h (n); per face k = 0 .. n the distance d between the
+    centres it separates (walls: h / 2) and the weight g of the cell behind it, (xv[k] - xc[k-1]) / d (walls: 0, not read).
+    ``np.concatenate([h, d, g])`` is the table of ``ldc_fv_set_grid``."""
+    xv = np.asarray(xv, dtype=np.float64)
+    n = xv.size - 1
+    xc = 0.5 * (xv[:-1] + xv[1:])
+    h = xv[1:] - xv[:-1]
+    d, g = np.zeros(n + 1), np.zeros(n + 1)
+    d[0], d[n] = 0.5 * h[0], 0.5 * h[-1]
+    d[1:n] = xc[1:] - xc[:-1]
+    g[1:n] = (xv[1:n] - xc[:-1]) / d[1:n]
+    return xc, h, d, g
+
+
+def generalised_eig_host(h, d, rho=1.0):
+    """(eigenvalues ascending, eigenvectors as columns) of K q = lam H q with Q^T H Q = I: K the 1-D Neumann stiffness with the
+    weights rho / d of the inner faces, H = diag(h); index 0 = zero mode.  With them the operator Hy (x) Kx + Ky (x) Hx of the
+    pressure correction on a tensor grid is solved by the four products of the uniform case, divisor lamy[a] + lamx[b]."""
+    from scipy.linalg import eigh
+    n = h.size
+    w = rho / d[1:n]
+    K = np.zeros((n, n))
+    i = np.arange(n - 1)
+    K[i, i] += w
+    K[i + 1, i + 1] += w
+    K[i, i + 1] -= w
+    K[i + 1, i] -= w
+    lam, Q = eigh(K, np.diag(h))
+    assert abs(lam[0]) < 1e-9 * lam[-1] and lam[1] > 1e-6 * lam[-1], "Neumann stiffness: one zero mode, first"
+    return lam, Q
+
+
+_grid_cache = {}
+
+
+def grid_axis(n: int, L: float, beta: float, device, rho=1.0):
+    """The device tensors of one axis of a tanh grid, cached per (n, L, beta, rho, device) like ``sine_eig``: (table
+    [h | d | g], lam, Q).  Trials of equal axes share one upload and one eigen-decomposition."""
+    import torch
+    device = torch.device(device)
+    key = (int(n), float(L), float(beta), float(rho), device.type,
+           torch.cuda.current_device() if device.index is None else device.index)
+    if key not in _grid_cache:
+        _, h, d, g = axis_tables(tanh_vertices(n, L, beta))
+        lam, Q = generalised_eig_host(h, d, rho)
+        f64 = dict(dtype=torch.float64, device=device)
+        _grid_cache[key] = (torch.tensor(np.concatenate([h, d, g]), **f64), torch.tensor(lam, **f64),
+                            torch.tensor(Q, **f64).contiguous())
+    return _grid_cache[key]
+
+
+def lid_profile_at(xf, Lx=1.0, lid_velocity=1.0, corner_treatment="none", corner_smoothing=0.15) -> np.ndarray:
+    """``lid_profile`` at the face centres ``xf`` of any mesh (the reference's builder evaluates the lid at the face centre)."""
+    xf = np.asarray(xf, dtype=np.float64)
+    xi = xf / Lx
+    if corner_treatment in ("polynomial", "saad"):
+        return 16.0 * xi**2 * (1.0 - xi) ** 2 * lid_velocity
+    u = np.full(xf.size, float(lid_velocity))
+    if corner_treatment == "smoothing":
+        d = corner_smoothing * Lx
+        for i, x_face in enumerate(xf):
+            if x_face < d:
+                u[i] = 0.5 * (1 - np.cos(np.pi * x_face / d)) * lid_velocity
+            elif x_face > (Lx - d):
+                u[i] = 0.5 * (1 - np.cos(np.pi * (Lx - x_face) / d)) * lid_velocity
+    return u
+
+
+def stretched_streamfunction_matrix(dxf, dyf):
+    """The non-uniform 5-point operator on the interior cells, rows in the order j (outer), i (inner), sparse: per axis
+    (2 / (d_w + d_e)) ((psi_E - psi_P) / d_e - (psi_P - psi_W) / d_w) with the distances between cell centres; the ring of
+    boundary cells is 0 as in the uniform rule."""
+    from scipy.sparse import diags, identity, kron
+
+    def axis(d):                              # cells 1 .. n - 2; d[k] is the face between cells k - 1 and k
+        dw, de = d[1:-2], d[2:-1]
+        s = 2.0 / (dw + de)
+        return diags([(s / dw)[1:], -s * (1.0 / de + 1.0 / dw), (s / de)[:-1]], [-1, 0, 1], format="csr")
+    nx, ny = dxf.size - 1, dyf.size - 1
+    return (kron(identity(ny - 2), axis(dxf)) + kron(axis(dyf), identity(nx - 2))).tocsr()
 
 
 def neumann_eig(n: int):
@@ -162,6 +257,10 @@ def postprocess(trials):
     from solvers.spectral import ldc_lib
     if not trials:
         return
+    for s in trials:
+        if s.stretched:
+            raise ValueError("postprocess: grid='tanh' trials are post-processed on the host (the device kernels assume "
+                             "equal spacing); give the trial vortex_metrics='host'")
     routes = [post_route(s.params.vortex_metrics, s._has_cu_handle, s.params.streamfunction) for s in trials]
     for s, route in zip(trials, routes):
         if route == "cu":
@@ -228,6 +327,10 @@ def prolong(pairs):
     pairs = list(pairs)
     if not pairs:
         return
+    for c, f in pairs:
+        if c.stretched or f.stretched:
+            raise ValueError("prolong / start_from with grid='tanh': the prolongation kernel assumes equal spacing on both "
+                             "trials")
     dev = pairs[0][1].device
     index = torch.cuda.current_device() if dev.index is None else dev.index
     routes = [prolong_route(c._has_cu_handle, f._has_cu_handle, c.chip, f.chip) for c, f in pairs]
@@ -601,6 +704,30 @@ class FVSolver(LidDrivenCavitySolver):
             raise ValueError(f"pressure_max_iters={p.pressure_max_iters}: CG iterations per pressure solve, at least 1")
         if int(p.pressure_budget) < 1:
             raise ValueError(f"pressure_budget={p.pressure_budget}: CG iterations per SIMPLE iteration, at least 1")
+        if p.grid not in GRIDS:
+            raise ValueError(f"grid={p.grid!r}: 'uniform' or 'tanh'")
+        self.stretched = p.grid == "tanh"         # geometry tables on the handle: fv_stretched_kernel advances the trial
+        if self.stretched:
+            if not float(p.grid_stretch) >= 0.0 or not np.isfinite(float(p.grid_stretch)):
+                raise ValueError(f"grid_stretch={p.grid_stretch}: the tanh clustering parameter, a finite number >= 0")
+            if p.mapping != "cu":
+                raise ValueError(f"grid='tanh' with mapping={p.mapping!r}: stretched grids run on the one-CU kernel only "
+                                 f"(mapping='cu')")
+            if p.acceleration != "none":
+                raise ValueError(f"grid='tanh' with acceleration={p.acceleration!r}: Anderson mixing has not been tested "
+                                 f"on stretched grids, give the trial acceleration='none'")
+            if self._needs_cu_handle:
+                raise ValueError("grid='tanh' with solver=fv/fsg: the prolongation between the levels assumes equal "
+                                 "spacing, run the trial with solver=fv")
+            if p.vortex_metrics != "host":
+                raise ValueError(f"grid='tanh' with vortex_metrics={p.vortex_metrics!r}: the post-processing kernels assume "
+                                 f"equal spacing, give the trial vortex_metrics='host'")
+            if p.streamfunction != "reference":
+                raise ValueError(f"grid='tanh' with streamfunction={p.streamfunction!r}: the wall rule's kernel assumes "
+                                 f"equal spacing, give the trial streamfunction='reference'")
+            if p.vortex_refine != "none":
+                raise ValueError(f"grid='tanh' with vortex_refine={p.vortex_refine!r}: sub-cell centres come with the "
+                                 f"wall rule, which assumes equal spacing")
         self.shared = p.mapping == "shared"       # the phase kernels of csrc/ldc_fv_wide.hip: a launch of its own per
         self.chip = p.mapping == "chip" or self.shared        # phase ("chip") or one for all trials of a batch ("shared")
         nx, ny = int(p.nx), int(p.ny)
@@ -630,6 +757,11 @@ class FVSolver(LidDrivenCavitySolver):
         self.shape_full = (ny, nx)               # as the reference's FV solver: cells c = j*nx + i
         self.mu = self.rho * p.lid_velocity * p.Lx / p.Re
         xc, yc = (np.arange(nx) + 0.5) * self.dx_min, (np.arange(ny) + 0.5) * self.dy_min
+        if self.stretched:                       # (dx_min, dy_min stay the mean widths: the kernel does not read them)
+            beta = float(p.grid_stretch)
+            self._xv, self._yv = tanh_vertices(nx, p.Lx, beta), tanh_vertices(ny, p.Ly, beta)
+            xc, self._hx, self._dxf, self._gxf = axis_tables(self._xv)
+            yc, self._hy, self._dyf, self._gyf = axis_tables(self._yv)
         X, Y = np.meshgrid(xc, yc)
         self._init_fields(x=X.ravel(), y=Y.ravel())
         self._mask_bounds = mask_bounds(np.sort(np.unique(self.fields.x)), np.sort(np.unique(self.fields.y)))
@@ -643,13 +775,21 @@ class FVSolver(LidDrivenCavitySolver):
         if L.ldc_fv_version() != F.VERSION:
             raise ldc_lib.LdcError(f"ldc_fv ABI {L.ldc_fv_version()} != {F.VERSION}: rebuild the library")
         f64 = dict(dtype=torch.float64, device=self.device)
-        lamx, Qx = neumann_eig(nx)
-        lamy, Qy = neumann_eig(ny)
         self.rec_cap = max(1, int(p.check_every))
+        if self.stretched:                       # shared per (n, L, beta, device); the lid at the stretched face centres
+            gridx, lamx, Qx = grid_axis(nx, p.Lx, float(p.grid_stretch), self.device, self.rho)
+            gridy, lamy, Qy = grid_axis(ny, p.Ly, float(p.grid_stretch), self.device, self.rho)
+            ulid = lid_profile_at(xc, p.Lx, p.lid_velocity, p.corner_treatment, p.corner_smoothing)
+            ops = dict(Qx=Qx, lamx=lamx, Qy=Qy, lamy=lamy, gridx=gridx, gridy=gridy)
+        else:
+            lamx, Qx = neumann_eig(nx)
+            lamy, Qy = neumann_eig(ny)
+            ulid = lid_profile(nx, p.Lx, p.lid_velocity, p.corner_treatment, p.corner_smoothing)
+            ops = dict(Qx=torch.tensor(Qx, **f64).contiguous(), lamx=torch.tensor(lamx, **f64),
+                       Qy=torch.tensor(Qy, **f64).contiguous(), lamy=torch.tensor(lamy, **f64))
+        self._ulid_host = np.asarray(ulid, dtype=np.float64)
         self.t = dict(
-            ulid=torch.tensor(lid_profile(nx, p.Lx, p.lid_velocity, p.corner_treatment, p.corner_smoothing), **f64),
-            Qx=torch.tensor(Qx, **f64).contiguous(), lamx=torch.tensor(lamx, **f64),
-            Qy=torch.tensor(Qy, **f64).contiguous(), lamy=torch.tensor(lamy, **f64),
+            ulid=torch.tensor(ulid, **f64), **ops,
             u=torch.zeros(nx * ny, **f64), v=torch.zeros(nx * ny, **f64), p=torch.zeros(nx * ny, **f64),
             mdot=torch.zeros(F.faces(nx, ny), **f64), work=torch.zeros(F.work_len(nx, ny), **f64),
             rec=torch.zeros((self.rec_cap, F.REC_LEN), **f64),
@@ -703,6 +843,9 @@ class FVSolver(LidDrivenCavitySolver):
                 if self.consistent_cu:
                     F.set_pressure(h, "consistent", float(self.params.pressure_tol), int(self.params.pressure_max_iters),
                                    self.t["pstats"].data_ptr(), self.t["pstats"].numel())
+                if self.stretched:
+                    F.set_grid(h, self.t["gridx"].data_ptr(), self.t["gridx"].numel(), self.t["gridy"].data_ptr(),
+                               self.t["gridy"].numel())
             if self.chip:
                 h = C.c_void_p()
                 F.check(F.lib().ldc_fv_wide_create(C.byref(pr), self.t["scratch"].data_ptr(),
@@ -908,8 +1051,23 @@ class FVSolver(LidDrivenCavitySolver):
         g[1:-1, -1] = -f2[:, -1]
         return ((g[1:-1, 2:] - g[1:-1, :-2]) / (2 * self.dx_min), (g[2:, 1:-1] - g[:-2, 1:-1]) / (2 * self.dy_min))
 
+    def _gauss_gradient(self, f2, lid):
+        """(d f / dx, d f / dy) on the stretched grid: (f_e - f_w) / hx with g-weighted face values, 0 on the walls and
+        ``lid`` (nx values) on the lid: the rule of the kernel's record (include/ldc_fv.h)."""
+        ny, nx = self.shape_full
+        gx, gy = self._gxf[1:-1][None, :], self._gyf[1:-1][:, None]
+        fx, fy = np.zeros((ny, nx + 1)), np.zeros((ny + 1, nx))
+        fx[:, 1:-1] = gx * f2[:, 1:] + (1.0 - gx) * f2[:, :-1]
+        fy[1:-1, :] = gy * f2[1:, :] + (1.0 - gy) * f2[:-1, :]
+        fy[-1, :] = lid
+        return (fx[:, 1:] - fx[:, :-1]) / self._hx[None, :], (fy[1:, :] - fy[:-1, :]) / self._hy[:, None]
+
     def _vorticity(self) -> np.ndarray:
         U, V = self.fields.u.reshape(self.shape_full), self.fields.v.reshape(self.shape_full)
+        if getattr(self, "stretched", False):
+            dvdx, _ = self._gauss_gradient(V, 0.0)
+            _, dudy = self._gauss_gradient(U, self._ulid_host)
+            return dvdx - dudy
         dvdx, _ = self._ghost_gradient(V, 0.0)
         _, dudy = self._ghost_gradient(U, float(getattr(self.params, "lid_velocity", 1.0)))
         return dvdx - dudy
@@ -919,6 +1077,11 @@ class FVSolver(LidDrivenCavitySolver):
         from scipy.sparse import diags
         from scipy.sparse.linalg import spsolve
         ny, nx = self.shape_full
+        if getattr(self, "stretched", False):
+            A = stretched_streamfunction_matrix(self._dxf, self._dyf)
+            psi = np.zeros((ny, nx))
+            psi[1:-1, 1:-1] = spsolve(A, -omega[1:-1, 1:-1].ravel()).reshape(ny - 2, nx - 2)
+            return psi
         dx, dy = self.dx_min, self.dy_min
         ni = (ny - 2) * (nx - 2)
         cx, cy = 1.0 / (dx * dx), 1.0 / (dy * dy)
@@ -1029,6 +1192,10 @@ class FVSolver(LidDrivenCavitySolver):
         return out
 
     def _post_field(self, name) -> np.ndarray:
+        if self.stretched:                        # on the host, from the current device state
+            self._finalize_fields()
+            omega = self._vorticity()
+            return omega if name == "omega" else self._streamfunction(omega)
         postprocess([self])
         self._post = None
         return self.t[name].cpu().numpy().reshape(self.shape_full).copy()

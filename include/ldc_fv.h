@@ -1,6 +1,7 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
  * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc and
- * csrc/ldc_fv_wide_pressure.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip, csrc/ldc_fv_wall_post.hip).
+ * csrc/ldc_fv_wide_pressure.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip, csrc/ldc_fv_wall_post.hip,
+ * csrc/ldc_fv_stretched.hip).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -194,6 +195,34 @@
  *  - ldc_fv_step_debug on such a handle returns LDC_E_ARG: the debug kernel is the reference iteration.  The work vectors
  *    hold the intermediates.  ldc_fv_post_enqueue and ldc_fv_prolong_enqueue take the handle as any other.
  *
+ * Stretched grids of a one-CU trial (ldc_fv_set_grid; csrc/ldc_fv_stretched.hip, a unit of its own so that the code objects
+ * of the kernels above stay what they were).  A handle with geometry tables attached runs the same iteration on a tensor
+ * grid with any spacing per axis (the solver builds tanh-clustered vertices, cell centres at their midpoints), with the
+ * reference's own rules on such a mesh (tests/fv_stretched_numpy.py states them array by array), by either pressure
+ * equation (ldc_fv_set_pressure), one work-group of 512 threads per trial as before.  ldc_fv_enqueue / ldc_fv_batch_enqueue
+ * send such handles to fv_stretched_kernel, one launch group per pressure mode, so a list may mix uniform and stretched
+ * trials of any sizes.
+ *  - per axis ONE table of LDC_FV_GRID_TABLE_LEN(n) = 3 n + 2 doubles, [h | d | g]: h[i], i = 0 .. n-1, the cell widths; then
+ *    per face k = 0 .. n (face k lies between cells k-1 and k) d[k], the distance between the two centres, h[0] / 2 and
+ *    h[n-1] / 2 on the walls, and g[k] = (face - centre of cell k-1) / d[k], the weight of cell k in
+ *    phi_f = g phi_N + (1 - g) phi_P (the walls' g is not read).  V = hx[i] hy[j]; |S| = hy[j] on x faces, hx[i] on y faces;
+ *  - the gradient is the mean of the one-sided slopes (f_N - f_P) / d a cell has, with the pinned-cell exclusions; inner
+ *    diffusion mu |S| / d, wall diffusion mu |S| / (h / 2); u*, v*, grad p, D = V / (a_P + 1e-14) and u', v' go to the
+ *    faces with g; `ulid` is the caller's lid profile at the stretched face centres; dx, dy of the problem are not read;
+ *  - reference mode: the operator with the weights rho |S| / d is Hy (x) Kx + Ky (x) Hx, so Qx, lamx (Qy, lamy) are the
+ *    generalised eigenpairs Kx q = lam Hx q with Q^T Hx Q = I (Kx: the 1-D Neumann stiffness with the weights rho / d,
+ *    Hx = diag(h); ascending, index 0 the zero mode), and the exact solve is the same four GEMMs with the divisor
+ *    lamy[a] + lamx[b]; the c_0 and y - y_0 rules and FV-Q4 (wall faces of mdot') are kept;
+ *  - consistent mode: w_f = rho (g D_N + (1 - g) D_P) |S| / d, CG preconditioned by the operator above, the loop, the stop
+ *    rule, the work vectors and the statistics words of ldc_fv_cu_pressure.hip; walls exactly 0.0;
+ *  - omega, E, Z, P: d f / dx at a cell is (f_e - f_w) / hx[i] with g-weighted face values and the wall's own value on a
+ *    wall face (0; ulid[i] for u on the lid; 0 for omega); the sums carry the weight V.  With equal widths and a constant lid
+ *    this is algebraically the ghost-cell rule above;
+ *  - the block (two pointers) lives at byte 328 of the descriptor slot, clear of the post block (256 .. 327) and the pressure
+ *    block (384 .. 407); the descriptor itself does not change;
+ *  - ldc_fv_step_debug on such a handle returns LDC_E_ARG.  ldc_fv_post_enqueue, ldc_fv_prolong_enqueue, the wall rule, the
+ *    sampling and the mixing kernel's callers assume equal spacing: the solver refuses those combinations.
+ *
  * Post-processing and prolongation of such a trial (ldc_fv_wide_post_enqueue, ldc_fv_wide_prolong_enqueue; the same
  * unit): what ldc_fv_post_enqueue and ldc_fv_prolong_enqueue do for a trial of up to LDC_FV_MAX_N cells per axis, by the
  * chip mapping's rules for LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N: one launch per phase, a grid that depends on (nx, ny) alone,
@@ -319,6 +348,10 @@ extern "C" {
 #define LDC_FV_WIDE_PRESSURE_BUDGET_DEFAULT 12
 #define LDC_FV_WIDE_PRESSURE_SCRATCH_LEN 4
 #define LDC_FV_PRESSURE_STATS_LEN 4 /* the statistics words of ldc_fv_set_pressure (a one-CU trial) */
+/* ldc_fv_set_grid: the modes and the doubles of one axis' table [h (n) | d (n + 1) | g (n + 1)] */
+#define LDC_FV_GRID_UNIFORM 0
+#define LDC_FV_GRID_TABLES 1
+#define LDC_FV_GRID_TABLE_LEN(n) (3 * (int64_t)(n) + 2)
 /* ldc_fv_wall_post_enqueue: jobs per launch (136 bytes per job in the arguments), the caller's scratch per job in doubles, */
 /* the result block (the LDC_FV_POST_* slots, then four groups) and the slots of a group                                   */
 #define LDC_FV_WALL_LAUNCH_MAX 24
@@ -407,6 +440,14 @@ struct ldc_fv_pressure {
   double tol;                     /* CG stops at |r|_2 <= tol |b|_2 (0 < tol < 1)                                          */
 };
 
+struct ldc_fv_grid {
+  int32_t mode;                   /* LDC_FV_GRID_UNIFORM (dx, dy of the problem) or LDC_FV_GRID_TABLES */
+  int32_t pad;
+  const double *x_tables;         /* device: LDC_FV_GRID_TABLE_LEN(nx) doubles, [h | d | g] of the x axis */
+  const double *y_tables;         /* device: LDC_FV_GRID_TABLE_LEN(ny) doubles, the same for y */
+  int64_t x_len, y_len;           /* the lengths of the two buffers */
+};
+
 struct ldc_fv_sample_job {
   const double *u, *v, *p;        /* source: the FV state at the cells c = j*nx + i (n each) */
   const double *ulid;             /* source: the FV lid profile (nx) */
@@ -458,6 +499,13 @@ int ldc_fv_step_debug(ldc_fv *h, int which, double *const *out, void *stream);
 /* LDC_E_STATE for a null handle; LDC_E_ARG for another mode, max_iters < 1, tol outside (0, 1) or NaN, a null or short       */
 /* stats.  A refused call leaves the handle as it was.                                                                        */
 int ldc_fv_set_pressure(ldc_fv *h, const struct ldc_fv_pressure *cfg, int64_t *stats, int64_t stats_len);
+/* The grid of a one-CU trial: grid == NULL or mode LDC_FV_GRID_UNIFORM is the grid of a new handle (dx, dy); mode              */
+/* LDC_FV_GRID_TABLES attaches the per-axis tables described above, device buffers owned by the caller and left alone while   */
+/* the handle lives in that mode; the problem's Qx, lamx, Qy, lamy and ulid must then be those of that grid.  Call it between  */
+/* solves, with nothing of the handle in flight (one synchronous copy into the tail of `work` on the library's own stream).   */
+/* Validation comes first and needs no device: LDC_E_STATE for a null handle; LDC_E_ARG for another mode, a null table or a   */
+/* length below LDC_FV_GRID_TABLE_LEN.  A refused call leaves the handle as it was.  The pressure mode is kept either way.    */
+int ldc_fv_set_grid(ldc_fv *h, const struct ldc_fv_grid *grid);
 /* omega, psi and the result block of n trials (any sizes, one device), one work-group each; trial q takes posts[q]. */
 /* Validation comes first and needs no device.  The trials must not be in flight on another stream.                  */
 int ldc_fv_post_enqueue(ldc_fv *const *hs, const struct ldc_fv_post *posts, int n, void *stream);
