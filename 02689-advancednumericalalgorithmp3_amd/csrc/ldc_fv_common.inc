@@ -2,7 +2,8 @@
 // ldc_kernels.hip (through ldc_fv_kernel.inc, the SIMPLE iteration with one trial per CU), ldc_fv_wide.hip (the same
 // iteration by the whole chip), ldc_fv_post.hip (streamfunction and vortex metrics), ldc_fv_prolong.hip (coarse-to-fine
 // transfer of the state), ldc_fv_anderson.hip (Anderson mixing), ldc_fv_cu_pressure.hip (the one-CU iteration with the
-// consistent pressure equation) and ldc_fv_stretched.hip (the one-CU iteration on a wall-clustered grid).
+// consistent pressure equation), ldc_fv_stretched.hip (the one-CU iteration on a wall-clustered grid) and
+// ldc_fv_stretched_sep.hip (the same with the separable scaled preconditioner).
 // Types, constants and host-side helpers (the fill of a descriptor, as_stream) only, no device function: each unit's
 // code object holds what that unit needs and depends on no other's.  The device functions that two mappings share are
 // in ldc_fv_cells.inc (the SIMPLE iteration), ldc_fv_post_cells.inc, ldc_fv_prolong_cells.inc and
@@ -46,6 +47,7 @@ static_assert(sizeof(FvDesc) <= LDC_FV_DESC_DOUBLES * sizeof(double), "descripto
 //     0 .. 255  FvDesc (ldc_fv_create; it travels by value in the 256-byte table entry of a shared batch: it must not grow)
 //   256 .. 327  the post block (ldc_fv_post.hip, kFvPostOffset)
 //   328 .. 343  the grid block of a one-CU trial on a stretched grid (FvGridBlk below; ldc_fv_set_grid)
+//   344 .. 359  the preconditioner block of such a trial (FvPrecondBlk below; ldc_fv_set_preconditioner)
 //   384 .. 407  the pressure block of a one-CU trial (FvCuPcg below; ldc_fv_set_pressure)
 //   448 .. 511  the mixing kernel's kept record row (ldc_fv_anderson.hip, kFvAaKeepOffset)
 // The consistent pressure equation of a one-CU trial (ldc_fv_cu_pressure.hip): tolerance, cap, mode and the caller's four
@@ -69,6 +71,15 @@ struct FvGridBlk {
 constexpr int kFvGridOffset = 328;
 static_assert(kFvGridOffset >= 256 + 72 && kFvGridOffset + sizeof(FvGridBlk) <= kFvCuPcgOffset,
               "the grid block is clear of the post block and of the pressure block");
+
+// The per-axis tables of the separable scaled preconditioner of such a trial (ldc_fv_stretched_sep.hip), written by
+// ldc_fv_set_preconditioner with the same copy: per axis [a (n) | lam (n) | Q (n x n)] (include/ldc_fv.h).
+struct FvPrecondBlk {
+  const double *px, *py;
+};
+constexpr int kFvPrecondOffset = 344;
+static_assert(kFvPrecondOffset >= kFvGridOffset + (int)sizeof(FvGridBlk) && kFvPrecondOffset + sizeof(FvPrecondBlk) <= kFvCuPcgOffset,
+              "the preconditioner block is clear of the grid block and of the pressure block");
 
 // host: the caller's stream handle of the C ABI
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -106,6 +117,7 @@ struct ldc_fv {
   double dx, dy;
   int pressure_mode;        // LDC_FV_PRESSURE_*: the kernel that advances the trial (ldc_fv_set_pressure)
   int grid_mode;            // LDC_FV_GRID_*: tables attached (ldc_fv_set_grid): fv_stretched_kernel advances the trial
+  int precond_mode;         // LDC_FV_PRECOND_*: tables attached (ldc_fv_set_preconditioner): fv_stretched_sep_kernel does
 };
 
 // host: consistent handles (pressure_mode LDC_FV_PRESSURE_CONSISTENT) of the CURRENT device go to fv_cu_pressure_kernel,
@@ -116,5 +128,10 @@ __attribute__((visibility("hidden"))) int ldc_fv_cu_pressure_launch(ldc_fv* cons
 // `consistent` says, go to fv_stretched_kernel, LDC_FV_LAUNCH_MAX per launch (ldc_fv_stretched.hip; called by ldc_fv_enqueue and
 // ldc_fv_batch_enqueue only)
 __attribute__((visibility("hidden"))) int ldc_fv_stretched_launch(ldc_fv* const* hs, int n, int n_iters, int consistent, void* stream);
+
+// host: consistent handles with geometry tables and the separable preconditioner (precond_mode LDC_FV_PRECOND_SEPARABLE) of
+// the CURRENT device go to fv_stretched_sep_kernel, LDC_FV_LAUNCH_MAX per launch (ldc_fv_stretched_sep.hip; called by
+// ldc_fv_enqueue and ldc_fv_batch_enqueue only)
+__attribute__((visibility("hidden"))) int ldc_fv_stretched_sep_launch(ldc_fv* const* hs, int n, int n_iters, void* stream);
 
 #endif  // LDC_FV_COMMON_INC

@@ -36,7 +36,8 @@
 // units; FvCtx, FvKrylov, fv_cell_*, fv_kry_*, fv_rec_* and fv_gemm_tile: ldc_fv_cells.inc, shared with ldc_fv_wide.hip;
 // FvLaunch, fv_reduce, fv_gemm, FvRed, FvRun and the seven phases: ldc_fv_cu_phases.inc, included below, shared with
 // ldc_fv_cu_pressure.hip -- the kernel of a handle in mode LDC_FV_PRESSURE_CONSISTENT, a unit of its own -- and with
-// ldc_fv_stretched.hip, the kernel of a handle with geometry tables, ldc_fv_set_grid)
+// ldc_fv_stretched.hip, the kernel of a handle with geometry tables, ldc_fv_set_grid, and ldc_fv_stretched_sep.hip, the
+// kernel of such a handle with the separable preconditioner, ldc_fv_set_preconditioner)
 
 namespace {
 
@@ -107,20 +108,24 @@ int fv_launch(ldc_fv* const* hs, int n, int n_iters, bool debug, const FvDebug& 
 // n_iters iterations of every handle, each by the kernel of its mode: the reference handles through fv_launch exactly as
 // before, in list order; the consistent ones (ldc_fv_set_pressure) through the launch function of ldc_fv_cu_pressure.hip,
 // in list order too; the handles with geometry tables (ldc_fv_set_grid) through that of ldc_fv_stretched.hip, one group per
-// pressure mode.  A mixed list is up to four launch groups; nothing waits for anything, so the order does not matter.
+// pressure mode; of these the consistent ones with the separable preconditioner (ldc_fv_set_preconditioner) through that of
+// ldc_fv_stretched_sep.hip.  A mixed list is up to five launch groups; nothing waits for anything, so the order does not
+// matter.
 int fv_dispatch(ldc_fv* const* hs, int n, int n_iters, void* stream) {
-  int count[4] = {0, 0, 0, 0};
+  int count[5] = {0, 0, 0, 0, 0};
   const auto group = [](const ldc_fv* h) {
-    return (h->grid_mode == LDC_FV_GRID_TABLES ? 2 : 0) + (h->pressure_mode == LDC_FV_PRESSURE_CONSISTENT ? 1 : 0);
+    const int g = (h->grid_mode == LDC_FV_GRID_TABLES ? 2 : 0) + (h->pressure_mode == LDC_FV_PRESSURE_CONSISTENT ? 1 : 0);
+    return g == 3 && h->precond_mode == LDC_FV_PRECOND_SEPARABLE ? 4 : g;
   };
   for (int q = 0; q < n; ++q) ++count[group(hs[q])];
   const auto launch = [&](int g, ldc_fv* const* list, int m) {
     if (g == 0) return fv_launch(list, m, n_iters, false, FvDebug{}, stream);
     if (g == 1) return ldc_fv_cu_pressure_launch(list, m, n_iters, stream);
+    if (g == 4) return ldc_fv_stretched_sep_launch(list, m, n_iters, stream);
     return ldc_fv_stretched_launch(list, m, n_iters, g == 3, stream);
   };
-  for (int g = 0; g < 4; ++g) if (count[g] == n) return launch(g, hs, n);
-  for (int g = 0; g < 4; ++g) {
+  for (int g = 0; g < 5; ++g) if (count[g] == n) return launch(g, hs, n);
+  for (int g = 0; g < 5; ++g) {
     if (count[g] == 0) continue;
     std::vector<ldc_fv*> part;
     for (int q = 0; q < n; ++q) if (group(hs[q]) == g) part.push_back(hs[q]);
@@ -153,6 +158,7 @@ int ldc_fv_create(const struct ldc_fv_problem* pr, ldc_fv** out) {
   s->nx = pr->nx; s->ny = pr->ny; s->dx = pr->dx; s->dy = pr->dy;
   s->pressure_mode = LDC_FV_PRESSURE_REFERENCE;
   s->grid_mode = LDC_FV_GRID_UNIFORM;
+  s->precond_mode = LDC_FV_PRECOND_LAPLACIAN;
   *out = s;
   return 0;
 }
@@ -196,7 +202,7 @@ int ldc_fv_set_pressure(ldc_fv* h, const struct ldc_fv_pressure* cfg, int64_t* s
 int ldc_fv_set_grid(ldc_fv* h, const struct ldc_fv_grid* grid) {
   if (!h) return LDC_E_STATE;
   if (!grid || grid->mode == LDC_FV_GRID_UNIFORM) {
-    h->grid_mode = LDC_FV_GRID_UNIFORM;
+    h->grid_mode = LDC_FV_GRID_UNIFORM;             // (precond_mode is not read without tables: fv_dispatch)
     return 0;
   }
   if (grid->mode != LDC_FV_GRID_TABLES || !grid->x_tables || !grid->y_tables) return LDC_E_ARG;
@@ -205,6 +211,23 @@ int ldc_fv_set_grid(ldc_fv* h, const struct ldc_fv_grid* grid) {
   const hipError_t e = copy_now(reinterpret_cast<char*>(h->dev) + kFvGridOffset, &blk, sizeof(blk), hipMemcpyHostToDevice);
   if (e != hipSuccess) return (int)e;
   h->grid_mode = LDC_FV_GRID_TABLES;
+  h->precond_mode = LDC_FV_PRECOND_LAPLACIAN;       // (preconditioner tables belong to the mesh they were fitted to)
+  return 0;
+}
+
+int ldc_fv_set_preconditioner(ldc_fv* h, const struct ldc_fv_precond* cfg) {
+  if (!h) return LDC_E_STATE;
+  if (!cfg || cfg->mode == LDC_FV_PRECOND_LAPLACIAN) {
+    h->precond_mode = LDC_FV_PRECOND_LAPLACIAN;
+    return 0;
+  }
+  if (cfg->mode != LDC_FV_PRECOND_SEPARABLE || h->grid_mode != LDC_FV_GRID_TABLES) return LDC_E_ARG;
+  if (!cfg->x_table || !cfg->y_table) return LDC_E_ARG;
+  if (cfg->x_len < LDC_FV_PRECOND_TABLE_LEN(h->nx) || cfg->y_len < LDC_FV_PRECOND_TABLE_LEN(h->ny)) return LDC_E_ARG;
+  const FvPrecondBlk blk = {cfg->x_table, cfg->y_table};
+  const hipError_t e = copy_now(reinterpret_cast<char*>(h->dev) + kFvPrecondOffset, &blk, sizeof(blk), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return (int)e;
+  h->precond_mode = LDC_FV_PRECOND_SEPARABLE;
   return 0;
 }
 

@@ -151,6 +151,12 @@ class FVParameters(Parameters):
     # start_from, device or chip vortex metrics, wall streamfunction or refinement.  Both change results: they go to MLflow
     grid: str = "uniform"
     grid_stretch: float = 1.5
+    # what preconditions the CG of the consistent pressure equation: "laplacian" (the operator with D left out, exactly
+    # inverted) or "separable" (D fitted by a product a_i b_j, that operator exactly inverted, and the rest of D taken by a
+    # diagonal scaling: ldc_fv_set_preconditioner; grid "tanh" with pressure_equation "consistent_cu" only, where it takes a
+    # third of the CG iterations; on a uniform grid nothing is gained).  Both solve the same equation to pressure_tol, so the
+    # results differ at that level: it goes to MLflow
+    pressure_preconditioner: str = "laplacian"
 
     def to_mlflow(self) -> dict:
         skip = {"device", "check_every", "vortex_metrics", "mapping", "linear_budget"}

@@ -31,6 +31,7 @@ PSTAT_ITERS, PSTAT_SOLVES, PSTAT_CAPS, PSTAT_LAST = range(4)
 PRESSURE_STATS_LEN = 4         # LDC_FV_PRESSURE_STATS_LEN: the same four words for a one-CU trial (ldc_fv_set_pressure)
 OVERFLOW_LINEAR, OVERFLOW_PRESSURE = 1, 2
 GRID_MODES = {"uniform": 0, "tanh": 1}      # LDC_FV_GRID_UNIFORM, LDC_FV_GRID_TABLES (ldc_fv_set_grid)
+PRECOND_MODES = {"laplacian": 0, "separable": 1}    # LDC_FV_PRECOND_LAPLACIAN, LDC_FV_PRECOND_SEPARABLE (ldc_fv_set_preconditioner)
 CTRL_DONE, CTRL_ITER, CTRL_NAN, CTRL_GIVEUP, CTRL_LIN_ITERS, CTRL_SOLVES = range(6)
 # slots of a result block of ldc_fv_post_enqueue (LDC_FV_POST_*)
 (POST_PSI_MIN, POST_OMEGA_CENTER, POST_OMEGA_MAX, POST_PSI_BR, POST_PSI_BL, POST_PSI_TL, POST_PSI_MIN_CELL,
@@ -82,6 +83,12 @@ class Grid(C.Structure):
                 ("y_len", C.c_int64)]
 
 
+class Precond(C.Structure):
+    """Mirror of ``struct ldc_fv_precond`` -- keep field order in sync with the header."""
+    _fields_ = [("mode", C.c_int32), ("pad", C.c_int32), ("x_table", _dp), ("y_table", _dp), ("x_len", C.c_int64),
+                ("y_len", C.c_int64)]
+
+
 class SampleJob(C.Structure):
     """Mirror of ``struct ldc_fv_sample_job`` -- keep field order in sync with the header."""
     _fields_ = (
@@ -104,7 +111,7 @@ class WallJob(C.Structure):
 
 # every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
-           "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_set_pressure", "ldc_fv_set_grid", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
+           "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_set_pressure", "ldc_fv_set_grid", "ldc_fv_set_preconditioner", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
            "ldc_fv_anderson_enqueue", "ldc_fv_wide_create", "ldc_fv_wide_destroy", "ldc_fv_wide_enqueue",
            "ldc_fv_wide_launches", "ldc_fv_wide_status", "ldc_fv_wide_set_graph", "ldc_fv_wide_batch_create",
            "ldc_fv_wide_batch_destroy", "ldc_fv_wide_batch_enqueue", "ldc_fv_wide_batch_set_graph",
@@ -184,6 +191,7 @@ def lib() -> C.CDLL:
         L.ldc_fv_step_debug.argtypes = [_dp, C.c_int, C.POINTER(_dp), _dp]
         L.ldc_fv_set_pressure.argtypes = [_dp, C.POINTER(Pressure), _dp, C.c_int64]
         L.ldc_fv_set_grid.argtypes = [_dp, C.POINTER(Grid)]
+        L.ldc_fv_set_preconditioner.argtypes = [_dp, C.POINTER(Precond)]
         L.ldc_fv_post_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(Post), C.c_int, _dp]
         L.ldc_fv_prolong_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(_dp), C.c_int, _dp]
         L.ldc_fv_anderson_enqueue.argtypes = [C.POINTER(_dp), C.POINTER(Anderson), C.c_int, C.c_int, _dp]
@@ -246,6 +254,19 @@ def set_grid(handle, x_tables_ptr: int, x_len: int, y_tables_ptr: int, y_len: in
     cfg = Grid(mode=GRID_MODES["tanh"], pad=0, x_tables=x_tables_ptr, y_tables=y_tables_ptr, x_len=int(x_len),
                y_len=int(y_len))
     check(lib().ldc_fv_set_grid(handle, C.byref(cfg)), "ldc_fv_set_grid")
+
+
+def precond_table_len(n: int) -> int:
+    """LDC_FV_PRECOND_TABLE_LEN: one axis' table [a (n) | lam (n) | Q (n x n)]."""
+    return n * (n + 2)
+
+
+def set_preconditioner(handle, x_table_ptr: int, x_len: int, y_table_ptr: int, y_len: int) -> None:
+    """Attach the per-axis tables of the separable scaled preconditioner to an ``ldc_fv`` handle with geometry tables
+    (include/ldc_fv.h).  One synchronous copy into the tail of the trial's work buffer: nothing of the handle may be in flight."""
+    cfg = Precond(mode=PRECOND_MODES["separable"], pad=0, x_table=x_table_ptr, y_table=y_table_ptr, x_len=int(x_len),
+                  y_len=int(y_len))
+    check(lib().ldc_fv_set_preconditioner(handle, C.byref(cfg)), "ldc_fv_set_preconditioner")
 
 
 def post_enqueue(handles, posts, stream) -> None:

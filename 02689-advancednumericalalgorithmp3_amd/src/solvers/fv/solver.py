@@ -41,6 +41,7 @@ PRESSURE_EQUATIONS = ("reference", "consistent", "consistent_cu")
 STREAMFUNCTIONS = ("reference", "wall")
 VORTEX_REFINES = ("none", "quadratic")
 GRIDS = ("uniform", "tanh")
+PRESSURE_PRECONDITIONERS = ("laplacian", "separable")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
 
 
@@ -121,6 +122,65 @@ def grid_axis(n: int, L: float, beta: float, device, rho=1.0):
         _grid_cache[key] = (torch.tensor(np.concatenate([h, d, g]), **f64), torch.tensor(lam, **f64),
                             torch.tensor(Q, **f64).contiguous())
     return _grid_cache[key]
+
+
+def separable_fit(hx, dxf, hy, dyf):
+    """(a (nx), b (ny)) with a_i b_j ~ G_ij = hx_i hy_j / (hy_j ax_i + hx_i ay_j), ax_i = 1 / dx[i] + 1 / dx[i+1] (ay likewise):
+    G is V / a_P of pure diffusion with mu left out (a constant factor in a preconditioner does not change CG), the fit the
+    least-squares one of log G by a sum: a_i = exp(mean_j l_ij - m / 2), b_j = exp(mean_i l_ij - m / 2), m = mean(l)."""
+    ax = 1.0 / dxf[:-1] + 1.0 / dxf[1:]
+    ay = 1.0 / dyf[:-1] + 1.0 / dyf[1:]
+    G = (hy[:, None] * hx[None, :]) / (hy[:, None] * ax[None, :] + hx[None, :] * ay[:, None])
+    l = np.log(G)
+    m = l.mean()
+    return np.exp(l.mean(axis=0) - 0.5 * m), np.exp(l.mean(axis=1) - 0.5 * m)
+
+
+def separable_axis_host(h, d, g, a, rho=1.0):
+    """(eigenvalues ascending, eigenvectors as columns) of K q = lam M q with Q^T M Q = I: K the 1-D Neumann stiffness with the
+    weights rho a_f / d of the inner faces, a_f[k] = g[k] a[k] + (1 - g[k]) a[k-1] (the rule that takes D to a face),
+    M = diag(h a); index 0 = zero mode."""
+    from scipy.linalg import eigh
+    n = h.size
+    af = g[1:n] * a[1:] + (1.0 - g[1:n]) * a[:-1]
+    w = rho * af / d[1:n]
+    K = np.zeros((n, n))
+    i = np.arange(n - 1)
+    K[i, i] += w
+    K[i + 1, i + 1] += w
+    K[i, i + 1] -= w
+    K[i + 1, i] -= w
+    lam, Q = eigh(K, np.diag(h * a))
+    assert abs(lam[0]) < 1e-9 * lam[-1] and lam[1] > 1e-6 * lam[-1], "Neumann stiffness: one zero mode, first"
+    return lam, Q
+
+
+def separable_tables_host(nx, ny, Lx, Ly, beta, rho=1.0):
+    """The two tables of ``ldc_fv_set_preconditioner`` for a tanh grid, [a | lam | Q (row-major)] per axis (y: b for a)."""
+    _, hx, dxf, gxf = axis_tables(tanh_vertices(nx, Lx, beta))
+    _, hy, dyf, gyf = axis_tables(tanh_vertices(ny, Ly, beta))
+    a, b = separable_fit(hx, dxf, hy, dyf)
+    lamx, Qx = separable_axis_host(hx, dxf, gxf, a, rho)
+    lamy, Qy = separable_axis_host(hy, dyf, gyf, b, rho)
+    return (np.concatenate([a, lamx, np.ascontiguousarray(Qx).ravel()]),
+            np.concatenate([b, lamy, np.ascontiguousarray(Qy).ravel()]))
+
+
+_separable_cache = {}
+
+
+def separable_tables(nx: int, ny: int, Lx: float, Ly: float, beta: float, device, rho=1.0):
+    """The device tensors of ``separable_tables_host``, cached per (nx, ny, Lx, Ly, beta, rho, device) like ``grid_axis``: the
+    fit couples the axes, so the key names both.  Trials of equal meshes share one upload and two eigen-decompositions."""
+    import torch
+    device = torch.device(device)
+    key = (int(nx), int(ny), float(Lx), float(Ly), float(beta), float(rho), device.type,
+           torch.cuda.current_device() if device.index is None else device.index)
+    if key not in _separable_cache:
+        tx, ty = separable_tables_host(nx, ny, Lx, Ly, beta, rho)
+        f64 = dict(dtype=torch.float64, device=device)
+        _separable_cache[key] = (torch.tensor(tx, **f64), torch.tensor(ty, **f64))
+    return _separable_cache[key]
 
 
 def lid_profile_at(xf, Lx=1.0, lid_velocity=1.0, corner_treatment="none", corner_smoothing=0.15) -> np.ndarray:
@@ -728,6 +788,13 @@ class FVSolver(LidDrivenCavitySolver):
             if p.vortex_refine != "none":
                 raise ValueError(f"grid='tanh' with vortex_refine={p.vortex_refine!r}: sub-cell centres come with the "
                                  f"wall rule, which assumes equal spacing")
+        if p.pressure_preconditioner not in PRESSURE_PRECONDITIONERS:
+            raise ValueError(f"pressure_preconditioner={p.pressure_preconditioner!r}: 'laplacian' or 'separable'")
+        self.separable = p.pressure_preconditioner == "separable"     # tables on the handle: fv_stretched_sep_kernel
+        if self.separable and not (self.stretched and self.consistent_cu):
+            raise ValueError(f"pressure_preconditioner='separable' with grid={p.grid!r}, pressure_equation="
+                             f"{p.pressure_equation!r}: it preconditions the CG of a stretched one-CU trial, give the trial "
+                             f"grid='tanh' and pressure_equation='consistent_cu'")
         self.shared = p.mapping == "shared"       # the phase kernels of csrc/ldc_fv_wide.hip: a launch of its own per
         self.chip = p.mapping == "chip" or self.shared        # phase ("chip") or one for all trials of a batch ("shared")
         nx, ny = int(p.nx), int(p.ny)
@@ -781,6 +848,9 @@ class FVSolver(LidDrivenCavitySolver):
             gridy, lamy, Qy = grid_axis(ny, p.Ly, float(p.grid_stretch), self.device, self.rho)
             ulid = lid_profile_at(xc, p.Lx, p.lid_velocity, p.corner_treatment, p.corner_smoothing)
             ops = dict(Qx=Qx, lamx=lamx, Qy=Qy, lamy=lamy, gridx=gridx, gridy=gridy)
+            if self.separable:                   # shared per (nx, ny, Lx, Ly, beta, rho, device): the fit couples the axes
+                ops["precx"], ops["precy"] = separable_tables(nx, ny, p.Lx, p.Ly, float(p.grid_stretch), self.device,
+                                                              self.rho)
         else:
             lamx, Qx = neumann_eig(nx)
             lamy, Qy = neumann_eig(ny)
@@ -846,6 +916,9 @@ class FVSolver(LidDrivenCavitySolver):
                 if self.stretched:
                     F.set_grid(h, self.t["gridx"].data_ptr(), self.t["gridx"].numel(), self.t["gridy"].data_ptr(),
                                self.t["gridy"].numel())
+                if self.separable:                # (after the grid: the call refuses a handle without geometry tables)
+                    F.set_preconditioner(h, self.t["precx"].data_ptr(), self.t["precx"].numel(),
+                                         self.t["precy"].data_ptr(), self.t["precy"].numel())
             if self.chip:
                 h = C.c_void_p()
                 F.check(F.lib().ldc_fv_wide_create(C.byref(pr), self.t["scratch"].data_ptr(),

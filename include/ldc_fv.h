@@ -1,7 +1,7 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
  * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc and
  * csrc/ldc_fv_wide_pressure.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip, csrc/ldc_fv_wall_post.hip,
- * csrc/ldc_fv_stretched.hip).
+ * csrc/ldc_fv_stretched.hip, csrc/ldc_fv_stretched_sep.hip).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -223,6 +223,26 @@
  *  - ldc_fv_step_debug on such a handle returns LDC_E_ARG.  ldc_fv_post_enqueue, ldc_fv_prolong_enqueue, the wall rule, the
  *    sampling and the mixing kernel's callers assume equal spacing: the solver refuses those combinations.
  *
+ * The separable scaled preconditioner of such a trial (ldc_fv_set_preconditioner; csrc/ldc_fv_stretched_sep.hip, a unit of
+ * its own so that fv_stretched_kernel stays what it was).  In consistent mode the CG above is preconditioned by the operator
+ * with D left out; on a stretched mesh D = V / a_P varies with V, and the count per solve grows several times.  A handle with
+ * preconditioner tables attached runs the same iteration with another z in the CG loop, and nothing else changed: the
+ * operator, b, the start x = 0, the stop rule and the cap, the statistics words, p', the face correction, walls exactly 0.0.
+ *  - the caller fits D by a product a[i] b[j] on the host (the solver: a least-squares fit of log G, G = V / a_P of pure
+ *    diffusion with mu left out) and builds L_s = My (x) Kx^a + Ky^b (x) Mx: Kx^a the 1-D Neumann stiffness with the weights
+ *    rho a_f / d, a_f[k] = g[k] a[k] + (1 - g[k]) a[k-1] on the inner faces, Mx = diag(hx a); y likewise with b;
+ *  - per axis ONE table of LDC_FV_PRECOND_TABLE_LEN(n) = n (n + 2) doubles, [a (n) | lam (n) | Q (n x n, row-major, column k
+ *    the k-th vector)]: the generalised eigenpairs Kx^a q = lam Mx q with Q^T Mx Q = I, ascending, index 0 the zero mode;
+ *  - L_s+ R = Qy ((Qy^T R Qx) / (lamy[a] + lamx[b])) Qx^T with entry (0, 0) set to 0: the four GEMMs of the exact solve with
+ *    these tables; per solve s_c = sqrt(a[i] b[j] / D_c), D_c = V / (a_P + 1e-14), and z = s . L_s+ (s . r).  z . r > 0 for
+ *    every r != 0 of zero sum, so CG is defined on the range of A; a constant in z is harmless, p' = x - x_0;
+ *  - s and s . r live in the work vectors 15 and 17, which are dead during the pressure solve; the loop has the sweeps and
+ *    barriers of the other, LDC_FV_NWORK is unchanged;
+ *  - the block (two pointers) lives at byte 344 of the descriptor slot, behind the grid block; the descriptor itself does
+ *    not change.  ldc_fv_enqueue / ldc_fv_batch_enqueue send consistent handles with both kinds of tables to
+ *    fv_stretched_sep_kernel as one more launch group, in list order within it.  A handle in reference mode keeps the
+ *    setting and does not read the block.
+ *
  * Post-processing and prolongation of such a trial (ldc_fv_wide_post_enqueue, ldc_fv_wide_prolong_enqueue; the same
  * unit): what ldc_fv_post_enqueue and ldc_fv_prolong_enqueue do for a trial of up to LDC_FV_MAX_N cells per axis, by the
  * chip mapping's rules for LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N: one launch per phase, a grid that depends on (nx, ny) alone,
@@ -352,6 +372,10 @@ extern "C" {
 #define LDC_FV_GRID_UNIFORM 0
 #define LDC_FV_GRID_TABLES 1
 #define LDC_FV_GRID_TABLE_LEN(n) (3 * (int64_t)(n) + 2)
+/* ldc_fv_set_preconditioner: the modes and the doubles of one axis' table [a (n) | lam (n) | Q (n x n)] */
+#define LDC_FV_PRECOND_LAPLACIAN 0
+#define LDC_FV_PRECOND_SEPARABLE 1
+#define LDC_FV_PRECOND_TABLE_LEN(n) ((int64_t)(n) * ((int64_t)(n) + 2))
 /* ldc_fv_wall_post_enqueue: jobs per launch (136 bytes per job in the arguments), the caller's scratch per job in doubles, */
 /* the result block (the LDC_FV_POST_* slots, then four groups) and the slots of a group                                   */
 #define LDC_FV_WALL_LAUNCH_MAX 24
@@ -448,6 +472,14 @@ struct ldc_fv_grid {
   int64_t x_len, y_len;           /* the lengths of the two buffers */
 };
 
+struct ldc_fv_precond {
+  int32_t mode;                   /* LDC_FV_PRECOND_LAPLACIAN (the operator with D left out) or LDC_FV_PRECOND_SEPARABLE */
+  int32_t pad;
+  const double *x_table;          /* device: LDC_FV_PRECOND_TABLE_LEN(nx) doubles, [a | lam | Q] of the x axis */
+  const double *y_table;          /* device: LDC_FV_PRECOND_TABLE_LEN(ny) doubles, the same for y (b in place of a) */
+  int64_t x_len, y_len;           /* the lengths of the two buffers */
+};
+
 struct ldc_fv_sample_job {
   const double *u, *v, *p;        /* source: the FV state at the cells c = j*nx + i (n each) */
   const double *ulid;             /* source: the FV lid profile (nx) */
@@ -506,6 +538,16 @@ int ldc_fv_set_pressure(ldc_fv *h, const struct ldc_fv_pressure *cfg, int64_t *s
 /* Validation comes first and needs no device: LDC_E_STATE for a null handle; LDC_E_ARG for another mode, a null table or a   */
 /* length below LDC_FV_GRID_TABLE_LEN.  A refused call leaves the handle as it was.  The pressure mode is kept either way.    */
 int ldc_fv_set_grid(ldc_fv *h, const struct ldc_fv_grid *grid);
+/* The preconditioner of the consistent pressure equation on a handle with geometry tables: cfg == NULL or mode                */
+/* LDC_FV_PRECOND_LAPLACIAN is that of a new handle; mode LDC_FV_PRECOND_SEPARABLE attaches the per-axis tables described      */
+/* above, device buffers owned by the caller and left alone while the handle lives in that mode.  Call it after                */
+/* ldc_fv_set_grid, between solves, with nothing of the handle in flight (one synchronous copy into the tail of `work`).  A    */
+/* call of ldc_fv_set_grid that makes the handle uniform restores the behaviour of before too: a uniform handle runs the       */
+/* uniform kernels whatever this mode says, and attaching geometry tables again resets it to LDC_FV_PRECOND_LAPLACIAN (the     */
+/* tables belong to the mesh they were fitted to).  Validation comes first and needs no device: LDC_E_STATE for a null handle; */
+/* LDC_E_ARG for another mode, a handle without geometry tables, a null table or a length below LDC_FV_PRECOND_TABLE_LEN.  A   */
+/* refused call leaves the handle as it was.                                                                                   */
+int ldc_fv_set_preconditioner(ldc_fv *h, const struct ldc_fv_precond *cfg);
 /* omega, psi and the result block of n trials (any sizes, one device), one work-group each; trial q takes posts[q]. */
 /* Validation comes first and needs no device.  The trials must not be in flight on another stream.                  */
 int ldc_fv_post_enqueue(ldc_fv *const *hs, const struct ldc_fv_post *posts, int n, void *stream);
