@@ -142,13 +142,15 @@ class FVParameters(Parameters):
     # of cells, the reference's rule, by whichever vortex_metrics route) or "wall" (psi = 0 on the wall faces and the lid
     # profile in omega's ghost row: second order; ldc_fv_wall_post_enqueue, always on the device, any mapping and size).
     # vortex_refine: "none" (every centre is a cell centre) or "quadratic" (the extremum of the quadratic through the
-    # 3 x 3 cells around it; "wall" only).  Both change the reported metrics: they go to MLflow
+    # 3 x 3 cells around it; with a wall rule only).  Both change the reported metrics: they go to MLflow
     streamfunction: str = "reference"
     vortex_refine: str = "none"
     # the mesh: "uniform" (the reference's) or "tanh" (wall-clustered in both axes: vertices x_k = Lx s(k / nx),
     # s(xi) = (1 + tanh(beta (2 xi - 1)) / tanh(beta)) / 2 with beta = grid_stretch >= 0, read only then; 0 gives uniform
     # vertices through the stretched kernel).  mapping "cu" only, either pressure equation; no acceleration, sequencing,
-    # start_from, device or chip vortex metrics, wall streamfunction or refinement.  Both change results: they go to MLflow
+    # start_from, device or chip vortex metrics by the reference's rule, or streamfunction "wall" (the equal-spacing kernel);
+    # streamfunction "wall_stretched" (tanh only, with or without the refinement) is the wall rule on the stretched mesh, on
+    # the device (ldc_fv_wall_stretched_post_enqueue).  Both change results: they go to MLflow
     grid: str = "uniform"
     grid_stretch: float = 1.5
     # what preconditions the CG of the consistent pressure equation: "laplacian" (the operator with D left out, exactly

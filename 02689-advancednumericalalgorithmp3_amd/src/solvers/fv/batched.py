@@ -35,7 +35,7 @@ import numpy as np
 from ..base import WARMUP_ITERATIONS
 from . import ldc_fv_lib as F
 from .fsg import FVFSGSolver, level_tolerance
-from .solver import FVSolver, SharedBatch, advance, postprocess, prolong
+from .solver import WALL_RULES, FVSolver, SharedBatch, advance, postprocess, prolong
 
 log = logging.getLogger(__name__)
 
@@ -190,10 +190,10 @@ class BatchedFVSolver:
         work = [0 if q in self.errors else total * s.nx * s.ny + (extra_work[q] if extra_work else 0)
                 for q, (s, (_, _, total, _)) in enumerate(zip(self.solvers, out))]
         work_all = max(1, sum(work))
-        # the device paths of the vortex metrics ("device", "chip" and streamfunction="wall"): every finished trial that asks for one in one go (_store_results below
+        # the device paths of the vortex metrics ("device", "chip" and the wall rules of streamfunction): every finished trial that asks for one in one go (_store_results below
         # finds its result block); a trial in `errors` is left alone
         postprocess([s for q, s in enumerate(self.solvers)
-                     if q not in self.errors and (s.params.vortex_metrics in ("device", "chip") or s.params.streamfunction == "wall")])
+                     if q not in self.errors and (s.params.vortex_metrics in ("device", "chip") or s.params.streamfunction in WALL_RULES)])
         for q, (s, (done, _, total, hist)) in enumerate(zip(self.solvers, out)):
             if q in self.errors:
                 continue

@@ -44,6 +44,7 @@ WALL_GROUP_LEN, WALL_RESULT_LEN = 8, 48
 WALL_X, WALL_Y, WALL_PSI, WALL_OMEGA, WALL_STATUS, WALL_SX, WALL_SY = range(7)
 WALL_NOT_ASKED, WALL_REFINED, WALL_NO_CANDIDATE, WALL_INDEFINITE, WALL_REJECTED = -1, 0, 1, 2, 3
 WALL_POST_LAUNCHES = 7         # omega | gemm x 4 | extrema | result, per group of WALL_LAUNCH_MAX jobs
+WALL_STRETCHED_LAUNCH_MAX = 32     # LDC_FV_WALL_STRETCHED_LAUNCH_MAX: jobs per launch of ldc_fv_wall_stretched_post_enqueue
 DBG = ("grad_p", "diag", "b", "u_star", "v_star", "mdot_star", "rhs_p", "p_prime", "u_prime", "v_prime", "mdot")
 
 _dp = C.c_void_p
@@ -109,6 +110,14 @@ class WallJob(C.Structure):
     )
 
 
+class WallStretchedJob(C.Structure):
+    """Mirror of ``struct ldc_fv_wall_stretched_job`` -- keep field order in sync with the header."""
+    _fields_ = (
+        [(n, _dp) for n in ("u", "v", "ulid", "x_grid", "y_grid", "x_post", "y_post", "psi", "omega", "scratch", "result")]
+        + [(n, C.c_int32) for n in ("nx", "ny", "ix_lt", "ix_gt", "jy_lt", "jy_gt", "refine", "pad")]
+    )
+
+
 # every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
            "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_set_pressure", "ldc_fv_set_grid", "ldc_fv_set_preconditioner", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
@@ -118,7 +127,8 @@ EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue"
            "ldc_fv_wide_batch_launches", "ldc_fv_wide_post_enqueue", "ldc_fv_wide_post_launches",
            "ldc_fv_wide_prolong_enqueue", "ldc_fv_wide_set_anderson", "ldc_fv_wide_set_pressure",
            "ldc_fv_wide_set_pressure_budget", "ldc_fv_wide_batch_set_pressure_budget", "ldc_fv_sample_nodes",
-           "ldc_fv_wall_post_enqueue", "ldc_fv_wall_post_launches")
+           "ldc_fv_wall_post_enqueue", "ldc_fv_wall_post_launches", "ldc_fv_wall_stretched_post_enqueue",
+           "ldc_fv_wall_stretched_post_launches")
 
 _bound = None
 
@@ -216,6 +226,8 @@ def lib() -> C.CDLL:
         L.ldc_fv_sample_nodes.argtypes = [C.POINTER(SampleJob), C.c_int, _dp]
         L.ldc_fv_wall_post_enqueue.argtypes = [C.POINTER(WallJob), C.c_int, _dp]
         L.ldc_fv_wall_post_launches.argtypes = [C.c_int]
+        L.ldc_fv_wall_stretched_post_enqueue.argtypes = [C.POINTER(WallStretchedJob), C.c_int, _dp]
+        L.ldc_fv_wall_stretched_post_launches.argtypes = [C.c_int]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -351,3 +363,15 @@ def wall_post_enqueue(jobs, stream) -> None:
     which the library checks first and launches WALL_LAUNCH_MAX at a time, seven launches each; nothing synchronises."""
     arr = (WallJob * len(jobs))(*jobs)
     check(lib().ldc_fv_wall_post_enqueue(arr, len(jobs), _dp(stream)), "ldc_fv_wall_post_enqueue")
+
+
+def wall_stretched_table_len(n: int) -> int:
+    """LDC_FV_WALL_STRETCHED_TABLE_LEN: one axis' post table [xc (n) | lam (n) | Q (n x n)]."""
+    return n * (n + 2)
+
+
+def wall_stretched_post_enqueue(jobs, stream) -> None:
+    """The same for every ``WallStretchedJob`` (a trial on a stretched tensor grid; include/ldc_fv.h): ONE call for all jobs,
+    which the library checks first and launches WALL_STRETCHED_LAUNCH_MAX at a time, seven launches each; nothing synchronises."""
+    arr = (WallStretchedJob * len(jobs))(*jobs)
+    check(lib().ldc_fv_wall_stretched_post_enqueue(arr, len(jobs), _dp(stream)), "ldc_fv_wall_stretched_post_enqueue")

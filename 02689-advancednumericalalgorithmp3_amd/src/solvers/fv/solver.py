@@ -15,7 +15,10 @@ per trial, the same quantities by the same rules; ``"chip"``: ``ldc_fv_wide_post
 the lid profile in omega's ghost row; ``vortex_refine="quadratic"``: sub-cell centres), always on the device and for every
 mapping and size (``ldc_fv_wall_post_enqueue``: the wall trials of a call share seven launches per 24 of them).
 ``grid="tanh"`` clusters the cells of a ``mapping="cu"`` trial at the walls (``ldc_fv_set_grid``: the same iteration with the
-geometry read from per-axis tables, either pressure equation); its vortex metrics are computed on the host.
+geometry read from per-axis tables, either pressure equation); its vortex metrics are computed on the host by the
+reference's rule, or with ``streamfunction="wall_stretched"`` on the device by the wall rule on the stretched mesh
+(``ldc_fv_wall_stretched_post_enqueue``: the Dirichlet generalised eigenpairs of each axis, the quadratic fit with unequal
+spacing; such trials of a call share seven launches per 32 of them).
 """
 from __future__ import annotations
 
@@ -38,7 +41,8 @@ MAPPINGS = ("cu", "chip", "shared")
 # "consistent": the chain of launches over the whole chip (mapping "chip" / "shared"); "consistent_cu": the same equation
 # inside the work-group of a one-CU trial (mapping "cu"); both are LDC_FV_PRESSURE_CONSISTENT to the library
 PRESSURE_EQUATIONS = ("reference", "consistent", "consistent_cu")
-STREAMFUNCTIONS = ("reference", "wall")
+STREAMFUNCTIONS = ("reference", "wall", "wall_stretched")
+WALL_RULES = ("wall", "wall_stretched")      # the wall rule on equal spacing, and on the tables of grid="tanh"
 VORTEX_REFINES = ("none", "quadratic")
 GRIDS = ("uniform", "tanh")
 PRESSURE_PRECONDITIONERS = ("laplacian", "separable")
@@ -122,6 +126,37 @@ def grid_axis(n: int, L: float, beta: float, device, rho=1.0):
         _grid_cache[key] = (torch.tensor(np.concatenate([h, d, g]), **f64), torch.tensor(lam, **f64),
                             torch.tensor(Q, **f64).contiguous())
     return _grid_cache[key]
+
+
+def dirichlet_eig_host(h, d):
+    """(eigenvalues ascending, eigenvectors as columns) of K q = lam H q with Q^T H Q = I: K the 1-D stiffness with the
+    weights 1 / d on ALL n + 1 faces (the walls carry 1 / (h / 2): zero on the wall FACE), H = diag(h).  Every lam > 0.  With
+    them (Hy (x) Kx + Ky (x) Hx) psi = V . omega, the wall rule's problem on a tensor grid, is solved by the four products of
+    the uniform case, divisor lamy[a] + lamx[b]."""
+    from scipy.linalg import eigh
+    n = h.size
+    w = 1.0 / d
+    K = np.diag(w[:-1] + w[1:]) - np.diag(w[1:n], 1) - np.diag(w[1:n], -1)
+    lam, Q = eigh(K, np.diag(h))
+    assert lam[0] > 0, "Dirichlet stiffness: no zero mode"
+    return lam, Q
+
+
+_wall_stretched_cache = {}
+
+
+def wall_stretched_axis(n: int, L: float, beta: float, device):
+    """The device tensor of one axis' post table of ``ldc_fv_wall_stretched_post_enqueue``, [xc | lam | Q (row-major)],
+    cached per (n, L, beta, device) like ``grid_axis``: one eigen-decomposition and one upload per axis and mesh."""
+    import torch
+    device = torch.device(device)
+    key = (int(n), float(L), float(beta), device.type, torch.cuda.current_device() if device.index is None else device.index)
+    if key not in _wall_stretched_cache:
+        xc, h, d, _ = axis_tables(tanh_vertices(n, L, beta))
+        lam, Q = dirichlet_eig_host(h, d)
+        _wall_stretched_cache[key] = torch.tensor(np.concatenate([xc, lam, np.ascontiguousarray(Q).ravel()]),
+                                                  dtype=torch.float64, device=device)
+    return _wall_stretched_cache[key]
 
 
 def separable_fit(hx, dxf, hy, dyf):
@@ -286,12 +321,13 @@ def mask_bounds(xs, ys):
 
 def post_route(vortex_metrics: str, has_cu_handle: bool, streamfunction: str = "reference") -> str:
     """The entry that post-processes a trial: ``"wall"`` (``ldc_fv_wall_post_enqueue``, launches shared by the wall trials
-    of the call) for a ``streamfunction="wall"`` trial, whatever ``vortex_metrics`` says and for every mapping and size;
+    of the call) for a ``streamfunction="wall"`` trial, whatever ``vortex_metrics`` says and for every mapping and size,
+    ``"wall_stretched"`` (``ldc_fv_wall_stretched_post_enqueue``, likewise) for a ``streamfunction="wall_stretched"`` one;
     else ``"chip"`` (``ldc_fv_wide_post_enqueue``, a chain of launches over the
     whole chip for this trial alone) when the trial asks for it or has no one-CU handle, else ``"cu"``
     (``ldc_fv_post_enqueue``, one work-group, beside the other such trials of the call)."""
-    if streamfunction == "wall":
-        return "wall"
+    if streamfunction in WALL_RULES:
+        return streamfunction
     return "chip" if vortex_metrics == "chip" or not has_cu_handle else "cu"
 
 
@@ -309,8 +345,8 @@ def prolong_route(coarse_has_cu: bool, fine_has_cu: bool, coarse_chip: bool, fin
 
 def postprocess(trials):
     """omega, psi and the vortex extrema of ``trials`` (FVSolvers on one device, none in flight) on the device: one
-    launch per 256 trials of the one-CU route, one chain of launches per trial of the chip route and one chain per 24
-    trials of the wall route (``post_route``), then ONE copy of all result blocks (rows of ``WALL_RESULT_LEN`` doubles when
+    launch per 256 trials of the one-CU route, one chain of launches per trial of the chip route, one chain per 24
+    trials of the wall route and one per 32 of the stretched wall route (``post_route``), then ONE copy of all result blocks (rows of ``WALL_RESULT_LEN`` doubles when
     the call has a wall trial: the ``POST_*`` slots come first either way).  ``psi`` and ``omega`` stay on the device as ``t["psi"]``, ``t["omega"]``; every
     trial keeps its row of the result blocks for ``compute_vortex_metrics``."""
     import torch
@@ -318,9 +354,10 @@ def postprocess(trials):
     if not trials:
         return
     for s in trials:
-        if s.stretched:
-            raise ValueError("postprocess: grid='tanh' trials are post-processed on the host (the device kernels assume "
-                             "equal spacing); give the trial vortex_metrics='host'")
+        if s.stretched and not getattr(s, "stretched_wall", False):
+            raise ValueError("postprocess: grid='tanh' trials with streamfunction='reference' are post-processed on the host "
+                             "(those device kernels assume equal spacing); give the trial vortex_metrics='host', or "
+                             "streamfunction='wall_stretched'")
     routes = [post_route(s.params.vortex_metrics, s._has_cu_handle, s.params.streamfunction) for s in trials]
     for s, route in zip(trials, routes):
         if route == "cu":
@@ -331,15 +368,19 @@ def postprocess(trials):
     dev = trials[0].device
     index = torch.cuda.current_device() if dev.index is None else dev.index
     with torch.cuda.device(dev):
-        width = F.WALL_RESULT_LEN if "wall" in routes else F.POST_RESULT_LEN
+        width = F.WALL_RESULT_LEN if "wall" in routes or "wall_stretched" in routes else F.POST_RESULT_LEN
         results = torch.zeros((len(trials), width), dtype=torch.float64, device=dev)
-        posts, jobs = [], []
+        posts, jobs, stretched_jobs = [], [], []
         for q, s in enumerate(trials):
             if (torch.cuda.current_device() if s.device.index is None else s.device.index) != index:
                 raise ValueError("postprocess: all trials must be on one device")
             if routes[q] == "wall":
                 posts.append(None)
                 jobs.append(s._wall_job(results[q].data_ptr()))
+                continue
+            if routes[q] == "wall_stretched":
+                posts.append(None)
+                stretched_jobs.append(s._wall_stretched_job(results[q].data_ptr()))
                 continue
             lamx, Sx = sine_eig(s.nx - 2, dev)
             lamy, Sy = sine_eig(s.ny - 2, dev)
@@ -366,6 +407,8 @@ def postprocess(trials):
                 F.wide_post_enqueue(trials[q]._wide, posts[q], scratch.data_ptr(), scratch.numel(), stream)
             if jobs:
                 F.wall_post_enqueue(jobs, stream)
+            if stretched_jobs:
+                F.wall_stretched_post_enqueue(stretched_jobs, stream)
             rows = results.cpu().numpy()          # (synchronises the stream)
     for s, row in zip(trials, rows):
         s._post = row.copy()
@@ -728,10 +771,10 @@ class FVSolver(LidDrivenCavitySolver):
         if p.vortex_metrics not in VORTEX_METRICS:
             raise ValueError(f"vortex_metrics={p.vortex_metrics!r}: 'host', 'device' or 'chip'")
         if p.streamfunction not in STREAMFUNCTIONS:
-            raise ValueError(f"streamfunction={p.streamfunction!r}: 'reference' or 'wall'")
+            raise ValueError(f"streamfunction={p.streamfunction!r}: 'reference', 'wall' or 'wall_stretched'")
         if p.vortex_refine not in VORTEX_REFINES:
             raise ValueError(f"vortex_refine={p.vortex_refine!r}: 'none' or 'quadratic'")
-        if p.vortex_refine == "quadratic" and p.streamfunction != "wall":
+        if p.vortex_refine == "quadratic" and p.streamfunction not in WALL_RULES:
             raise ValueError("vortex_refine='quadratic' with streamfunction='reference': the ring rule's O(h) error in psi "
                              "makes sub-cell centres moot, give the trial streamfunction='wall'")
         self.vortex_refine_status = None         # per (primary, BR, BL, TL) after a refined compute_vortex_metrics()
@@ -779,15 +822,19 @@ class FVSolver(LidDrivenCavitySolver):
             if self._needs_cu_handle:
                 raise ValueError("grid='tanh' with solver=fv/fsg: the prolongation between the levels assumes equal "
                                  "spacing, run the trial with solver=fv")
-            if p.vortex_metrics != "host":
-                raise ValueError(f"grid='tanh' with vortex_metrics={p.vortex_metrics!r}: the post-processing kernels assume "
-                                 f"equal spacing, give the trial vortex_metrics='host'")
-            if p.streamfunction != "reference":
-                raise ValueError(f"grid='tanh' with streamfunction={p.streamfunction!r}: the wall rule's kernel assumes "
-                                 f"equal spacing, give the trial streamfunction='reference'")
-            if p.vortex_refine != "none":
-                raise ValueError(f"grid='tanh' with vortex_refine={p.vortex_refine!r}: sub-cell centres come with the "
-                                 f"wall rule, which assumes equal spacing")
+            # (streamfunction="wall_stretched" is served on the device by ldc_fv_wall_stretched_post_enqueue and does not
+            # consult vortex_metrics, as "wall" does not for uniform trials)
+            if p.vortex_metrics != "host" and p.streamfunction != "wall_stretched":
+                raise ValueError(f"grid='tanh' with vortex_metrics={p.vortex_metrics!r}: the post-processing kernels of the "
+                                 f"reference's rule assume equal spacing, give the trial vortex_metrics='host' (or "
+                                 f"streamfunction='wall_stretched')")
+            if p.streamfunction == "wall":
+                raise ValueError("grid='tanh' with streamfunction='wall': that kernel assumes equal spacing, give the trial "
+                                 "streamfunction='wall_stretched' (the wall rule on the stretched mesh)")
+        elif p.streamfunction == "wall_stretched":
+            raise ValueError(f"streamfunction='wall_stretched' with grid={p.grid!r}: it reads the tables of a stretched mesh, "
+                             f"give the trial grid='tanh' (or streamfunction='wall')")
+        self.stretched_wall = p.streamfunction == "wall_stretched"      # postprocess() routes on it
         if p.pressure_preconditioner not in PRESSURE_PRECONDITIONERS:
             raise ValueError(f"pressure_preconditioner={p.pressure_preconditioner!r}: 'laplacian' or 'separable'")
         self.separable = p.pressure_preconditioner == "separable"     # tables on the handle: fv_stretched_sep_kernel
@@ -1172,7 +1219,7 @@ class FVSolver(LidDrivenCavitySolver):
 
     def compute_vortex_metrics(self) -> dict:
         # (getattr: tests/fv_post_numpy.py calls this method on a bare namespace that has only the host branch's parameters)
-        if getattr(self.params, "streamfunction", "reference") == "wall":
+        if getattr(self.params, "streamfunction", "reference") in WALL_RULES:
             return self._wall_vortex_metrics()
         if self.params.vortex_metrics in ("device", "chip"):
             return self._device_vortex_metrics()
@@ -1238,6 +1285,26 @@ class FVSolver(LidDrivenCavitySolver):
                          dx=self.dx_min, dy=self.dy_min, nx=self.nx, ny=self.ny, ix_lt=ix_lt, ix_gt=ix_gt, jy_lt=jy_lt,
                          jy_gt=jy_gt, refine=int(self.params.vortex_refine == "quadratic"), pad=0)
 
+    def _wall_stretched_job(self, result_ptr: int) -> F.WallStretchedJob:
+        """This trial's job of a ``wall_stretched_post_enqueue`` call: the state, the geometry tables its handle reads, the
+        post tables of its axes (shared per mesh and device), its own psi, omega and scratch, and the row of the call's
+        result tensor."""
+        import torch
+        dev, t, p = self.device, self.t, self.params
+        postx = wall_stretched_axis(self.nx, p.Lx, float(p.grid_stretch), dev)
+        posty = wall_stretched_axis(self.ny, p.Ly, float(p.grid_stretch), dev)
+        for name, size in (("psi", self.n_cells), ("omega", self.n_cells),
+                           ("wall_scratch", F.wall_scratch_len(self.nx, self.ny))):
+            if name not in t:
+                t[name] = torch.zeros(size, dtype=torch.float64, device=dev)
+        ix_lt, ix_gt, jy_lt, jy_gt = self._mask_bounds
+        return F.WallStretchedJob(u=t["u"].data_ptr(), v=t["v"].data_ptr(), ulid=t["ulid"].data_ptr(),
+                                  x_grid=t["gridx"].data_ptr(), y_grid=t["gridy"].data_ptr(), x_post=postx.data_ptr(),
+                                  y_post=posty.data_ptr(), psi=t["psi"].data_ptr(), omega=t["omega"].data_ptr(),
+                                  scratch=t["wall_scratch"].data_ptr(), result=result_ptr, nx=self.nx, ny=self.ny,
+                                  ix_lt=ix_lt, ix_gt=ix_gt, jy_lt=jy_lt, jy_gt=jy_gt,
+                                  refine=int(p.vortex_refine == "quadratic"), pad=0)
+
     def _wall_vortex_metrics(self) -> dict:
         """The metrics dict of a wall trial from its result block: the primary minimum and the corners from the groups
         (refined, or the cell's own values), under the existing rule that a corner counts when its grid value is > 0;
@@ -1265,7 +1332,7 @@ class FVSolver(LidDrivenCavitySolver):
         return out
 
     def _post_field(self, name) -> np.ndarray:
-        if self.stretched:                        # on the host, from the current device state
+        if self.stretched and not self.stretched_wall:      # the reference's rule: on the host, from the current device state
             self._finalize_fields()
             omega = self._vorticity()
             return omega if name == "omega" else self._streamfunction(omega)

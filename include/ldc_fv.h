@@ -220,8 +220,9 @@
  *    this is algebraically the ghost-cell rule above;
  *  - the block (two pointers) lives at byte 328 of the descriptor slot, clear of the post block (256 .. 327) and the pressure
  *    block (384 .. 407); the descriptor itself does not change;
- *  - ldc_fv_step_debug on such a handle returns LDC_E_ARG.  ldc_fv_post_enqueue, ldc_fv_prolong_enqueue, the wall rule, the
- *    sampling and the mixing kernel's callers assume equal spacing: the solver refuses those combinations.
+ *  - ldc_fv_step_debug on such a handle returns LDC_E_ARG.  ldc_fv_post_enqueue, ldc_fv_prolong_enqueue, ldc_fv_wall_post_enqueue,
+ *    the sampling and the mixing kernel's callers assume equal spacing: the solver refuses those combinations.  The wall rule
+ *    of such a trial is ldc_fv_wall_stretched_post_enqueue (below).
  *
  * The separable scaled preconditioner of such a trial (ldc_fv_set_preconditioner; csrc/ldc_fv_stretched_sep.hip, a unit of
  * its own so that fv_stretched_kernel stays what it was).  In consistent mode the CG above is preconditioned by the operator
@@ -312,6 +313,44 @@
  *  - scratch: LDC_FV_WALL_SCRATCH_LEN(nx, ny) doubles per job, the caller's: two fields of n, then one slot of 12 doubles
  *    per work-group of a sweep (five keys, five cells, two not-finite flags).  No two jobs of a call may share scratch,
  *    psi, omega or result.
+ *
+ * The same reading on a stretched tensor grid (csrc/ldc_fv_wall_post_stretched.hip, ldc_fv_wall_stretched_post_enqueue; a
+ * unit of its own, every other code object stays what it was): the wall-anchored psi and the sub-cell centres of a trial
+ * whose geometry comes from the per-axis tables of ldc_fv_set_grid.  A job holds raw device pointers only, no handle,
+ * LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N cells per axis; the state is only read.  tests/fv_wall_stretched_numpy.py states every
+ * array of it.
+ *  - tables: per axis the geometry table [h (n) | d (n + 1) | g (n + 1)] above, and ONE post table of
+ *    LDC_FV_WALL_STRETCHED_TABLE_LEN(n) = n (n + 2) doubles, [xc (n) | lam (n) | Q (n x n, row-major, column k the k-th
+ *    vector)]: the cell centres and the generalised eigenpairs K^D q = lam H q with Q^T H Q = I, H = diag(h), K^D the 1-D
+ *    stiffness with the weights 1 / d[k] on ALL n + 1 faces (the walls carry 1 / (h / 2): psi = 0 on the wall face).  Every
+ *    lam > 0, there is no zero mode;
+ *  - omega (ny x nx): the Gauss rule of the stretched kernels' record, (v_e - v_w) / hx[i] - (u_n - u_s) / hy[j] with the face
+ *    values g[k] f_k + (1 - g[k]) f_(k-1) on inner faces, 0 on the walls and ulid[i] for u on the lid;
+ *  - psi (ny x nx): (Hy (x) Kx^D + Ky^D (x) Hx) psi = (Hy (x) Hx) omega on ALL cells, solved exactly:
+ *    psi = Qy ((Qy^T B Qx) / (lamy[a] + lamx[b])) Qx^T with B = V . omega, V = hx[i] hy[j] -- the four GEMMs of the uniform
+ *    rule with cx = cy = 1; the omega launch leaves B in the second scratch field.  With equal widths this is
+ *    (cx Tx + cy Ty) psi = omega of ldc_fv_wall_post_enqueue;
+ *  - the extrema, slots 0 .. 15 and the layout of the four groups are those of ldc_fv_wall_post_enqueue; a group's own
+ *    values are x = xc[i], y = yc[j], psi and omega of the cell;
+ *  - refine = 1: the 3 x 3 stencil with odd reflection as above, in PHYSICAL coordinates.  With dw = dx[i], de = dx[i+1],
+ *    ds = dy[j], dn = dy[j+1] the distances to the neighbours' centres (d of the geometry table; beyond a wall the mirror
+ *    cell lies at 2 d_wall = h),
+ *      gx  = ((E - C) dw / de + (C - W) de / dw) / (dw + de),      Hxx = 2 ((E - C) / de - (C - W) / dw) / (dw + de),
+ *      gy, Hyy likewise with N, S, ds, dn,                          Hxy = (NE - NW - SE + SW) / ((dw + de) (ds + dn)),
+ *      det = Hxx Hyy - Hxy^2, sx = -(Hyy gx - Hxy gy) / det, sy = -(Hxx gy - Hxy gx) / det   (lengths),
+ *      x = xc[i] + sx, y = yc[j] + sy, psi* = C + (gx sx + gy sy) / 2,
+ *    exact for a six-term quadratic on any spacing; omega* is the same quadratic of omega off the boundary ring, the cell's
+ *    omega on it.  The floors are those of the uniform rule carried through the same divisions, every |term| divided as its
+ *    value is: Fxx = 4 eps 2 ((|E| + |C|) / de + (|C| + |W|) / dw) / (dw + de), Fyy likewise,
+ *    Fxy = 4 eps (|NE| + |NW| + |SE| + |SW|) / ((dw + de) (ds + dn)); the definiteness rule and its signs are unchanged.  No
+ *    multiply-add of omega, B or the refinement is contracted;
+ *  - status: as above, with 3 for a result that is not finite, sx outside [-dw, de], sy outside [-ds, dn] (the step leaves
+ *    the stencil) or a point outside [0, xc[nx-1] + d[nx]] x [0, yc[ny-1] + d[ny]].  LDC_FV_WALL_SX / SY hold the step as a
+ *    fraction of the distance to the neighbour on its side: sx / dw for sx < 0, else sx / de (the uniform value with equal
+ *    widths).  Any status but 0 reports the cell's own values and sx = sy = 0;
+ *  - the mapping and the scratch (LDC_FV_WALL_SCRATCH_LEN) are those of ldc_fv_wall_post_enqueue, seven launches per group of
+ *    up to LDC_FV_WALL_STRETCHED_LAUNCH_MAX jobs; a job's psi, omega and block do not depend on what else is in the call,
+ *    bit for bit.  Two jobs may share tables, never scratch, psi, omega or result.
  */
 #ifndef LDC_FV_H
 #define LDC_FV_H
@@ -389,6 +428,11 @@ extern "C" {
 #define LDC_FV_WALL_STATUS 4       /* -1 not asked for, 0 refined, 1 no candidate, 2 flat or indefinite, 3 rejected */
 #define LDC_FV_WALL_SX 5           /* the step from the cell centre, in cells */
 #define LDC_FV_WALL_SY 6
+/* ldc_fv_wall_stretched_post_enqueue: jobs per launch (120 bytes per job in the arguments) and the doubles of one axis'    */
+/* post table [xc (n) | lam (n) | Q (n x n)]; the scratch, the result block and the slots of a group are those above, with   */
+/* LDC_FV_WALL_SX / SY as fractions of the distance to the neighbour on the step's side                                    */
+#define LDC_FV_WALL_STRETCHED_LAUNCH_MAX 32
+#define LDC_FV_WALL_STRETCHED_TABLE_LEN(n) ((int64_t)(n) * ((int64_t)(n) + 2))
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
 #define LDC_FV_DBG_GRAD_P 0        /* 2n: d/dx p, then d/dy p                                    */
@@ -499,6 +543,19 @@ struct ldc_fv_wall_job {
   double *scratch;                /* LDC_FV_WALL_SCRATCH_LEN(nx, ny) */
   double *result;                 /* out: LDC_FV_WALL_RESULT_LEN */
   double dx, dy;                  /* > 0 */
+  int32_t nx, ny;                 /* LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N each */
+  int32_t ix_lt, ix_gt;           /* as in ldc_fv_post: 0 .. nx */
+  int32_t jy_lt, jy_gt;           /* 0 .. ny */
+  int32_t refine, pad;            /* 0: the cells' own values in the groups; 1: the quadratic fit */
+};
+
+struct ldc_fv_wall_stretched_job {
+  const double *u, *v, *ulid;     /* cell-centred state (ny x nx, c = j*nx + i), lid profile at the cell centres (nx) */
+  const double *x_grid, *y_grid;  /* the geometry tables [h | d | g]: LDC_FV_GRID_TABLE_LEN(nx), LDC_FV_GRID_TABLE_LEN(ny) */
+  const double *x_post, *y_post;  /* the post tables [xc | lam | Q]: LDC_FV_WALL_STRETCHED_TABLE_LEN(nx), .. (ny) */
+  double *psi, *omega;            /* out: ny x nx each */
+  double *scratch;                /* LDC_FV_WALL_SCRATCH_LEN(nx, ny) */
+  double *result;                 /* out: LDC_FV_WALL_RESULT_LEN */
   int32_t nx, ny;                 /* LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N each */
   int32_t ix_lt, ix_gt;           /* as in ldc_fv_post: 0 .. nx */
   int32_t jy_lt, jy_gt;           /* 0 .. ny */
@@ -658,6 +715,13 @@ int ldc_fv_sample_nodes(const struct ldc_fv_sample_job *jobs, int n, void *strea
 int ldc_fv_wall_post_enqueue(const struct ldc_fv_wall_job *jobs, int n, void *stream);
 /* Kernel launches of that call: 7 per group of LDC_FV_WALL_LAUNCH_MAX jobs.  Needs no device; LDC_E_ARG for n < 1. */
 int ldc_fv_wall_post_launches(int n);
+/* The same for jobs on stretched tensor grids, as described above: ldc_fv_wall_stretched_post_launches(n) launches on      */
+/* `stream`, nothing synchronises.  Validation comes before any launch and needs no device: LDC_E_ARG for a null list or     */
+/* n < 1, for a null pointer in a job, for nx or ny outside LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N, for a bound outside 0 .. nx     */
+/* (0 .. ny) and for refine other than 0 or 1; then LDC_E_NODEVICE.  The tables are the caller's to get right.               */
+int ldc_fv_wall_stretched_post_enqueue(const struct ldc_fv_wall_stretched_job *jobs, int n, void *stream);
+/* Kernel launches of that call: 7 per group of LDC_FV_WALL_STRETCHED_LAUNCH_MAX jobs.  Needs no device; LDC_E_ARG for n < 1. */
+int ldc_fv_wall_stretched_post_launches(int n);
 
 #ifdef __cplusplus
 }
