@@ -147,12 +147,19 @@ class FVParameters(Parameters):
     vortex_refine: str = "none"
     # the mesh: "uniform" (the reference's) or "tanh" (wall-clustered in both axes: vertices x_k = Lx s(k / nx),
     # s(xi) = (1 + tanh(beta (2 xi - 1)) / tanh(beta)) / 2 with beta = grid_stretch >= 0, read only then; 0 gives uniform
-    # vertices through the stretched kernel).  mapping "cu" only, either pressure equation; no acceleration, sequencing,
-    # start_from, device or chip vortex metrics by the reference's rule, or streamfunction "wall" (the equal-spacing kernel);
+    # vertices through the stretched kernel).  mapping "cu" only, either pressure equation; no acceleration, device or chip
+    # vortex metrics by the reference's rule, or streamfunction "wall" (the equal-spacing kernel); sequencing (solver=fv/fsg)
+    # and start_from with transfer "tables" only (below);
     # streamfunction "wall_stretched" (tanh only, with or without the refinement) is the wall rule on the stretched mesh, on
     # the device (ldc_fv_wall_stretched_post_enqueue).  Both change results: they go to MLflow
     grid: str = "uniform"
     grid_stretch: float = 1.5
+    # what prolong, start_from and the levels of solver=fv/fsg read the geometry from when THIS trial is the fine one of a pair:
+    # "uniform" (dx, dy: ldc_fv_prolong_enqueue and its chip twin, equal spacing on both trials) or "tables" (per-axis tables
+    # of centres, widths and face weights: ldc_fv_prolong_tables_enqueue; mapping "cu" only, either grid on either side, so a
+    # grid "tanh" trial can be sequenced, continued in Re, or started from a uniform one).  On a uniform pair the two agree to
+    # rounding, not bit for bit (the centres are vertex midpoints here and (k + 1/2) h there): it goes to MLflow
+    transfer: str = "uniform"
     # what preconditions the CG of the consistent pressure equation: "laplacian" (the operator with D left out, exactly
     # inverted) or "separable" (D fitted by a product a_i b_j, that operator exactly inverted, and the rest of D taken by a
     # diagonal scaling: ldc_fv_set_preconditioner; grid "tanh" with pressure_equation "consistent_cu" only, where it takes a

@@ -23,7 +23,8 @@ trials stay in the batch object and cost empty work-groups; a trial whose moment
 than the chunk carried is enqueued again on its own with twice the budget (``solver.advance_batch_with_budget``).
 
 ``BatchedFVFSGSolver`` is the same for coarse-to-fine sequences (solvers.fv.fsg): stage by stage, every stage a batch of
-ordinary trials, one ``prolong`` launch between stages.
+ordinary trials, one ``prolong`` call between stages, which splits its pairs by route: ``grid="tanh"`` trials with
+``transfer="tables"`` ride beside uniform ones.
 """
 from __future__ import annotations
 

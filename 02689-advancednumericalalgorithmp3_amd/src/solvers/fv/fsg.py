@@ -5,7 +5,9 @@ The counterpart of ``solvers.spectral.fsg`` for ``solver=fv`` (conf/solver/fv/fs
 solved by the same ``_begin`` / ``_advance`` loop as a lone trial; the coarsest level starts from rest, every other from
 the prolongation of the level below (``solver.prolong``: ``ldc_fv_prolong_enqueue``, one work-group per pair, the state
 never leaves the device).  ``start_from`` is the same transfer from ANY other FV trial of the device, whatever its grid
-and parameters: continuation in Re is ``start_from`` at equal size.
+and parameters: continuation in Re is ``start_from`` at equal size.  With ``grid="tanh"`` the trial needs
+``transfer="tables"``: every level is then a stretched ``FVSolver`` of the same stretch, pressure equation and preconditioner
+at its own size, and the transfer between them reads both grids from tables (``ldc_fv_prolong_tables_enqueue``).
 
 Sequencing is a capability, not a promised saving: the reference's stop rule (relative change per iteration) is bound
 by the asymptotic rate, so the fine level may take as many iterations from the prolonged state as from rest (DESIGN.md

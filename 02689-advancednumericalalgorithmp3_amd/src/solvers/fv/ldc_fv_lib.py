@@ -45,6 +45,7 @@ WALL_X, WALL_Y, WALL_PSI, WALL_OMEGA, WALL_STATUS, WALL_SX, WALL_SY = range(7)
 WALL_NOT_ASKED, WALL_REFINED, WALL_NO_CANDIDATE, WALL_INDEFINITE, WALL_REJECTED = -1, 0, 1, 2, 3
 WALL_POST_LAUNCHES = 7         # omega | gemm x 4 | extrema | result, per group of WALL_LAUNCH_MAX jobs
 WALL_STRETCHED_LAUNCH_MAX = 32     # LDC_FV_WALL_STRETCHED_LAUNCH_MAX: jobs per launch of ldc_fv_wall_stretched_post_enqueue
+PROLONG_TABLES_LAUNCH_MAX = 23     # LDC_FV_PROLONG_TABLES_LAUNCH_MAX: jobs per launch of ldc_fv_prolong_tables_enqueue
 DBG = ("grad_p", "diag", "b", "u_star", "v_star", "mdot_star", "rhs_p", "p_prime", "u_prime", "v_prime", "mdot")
 
 _dp = C.c_void_p
@@ -118,6 +119,16 @@ class WallStretchedJob(C.Structure):
     )
 
 
+class ProlongTablesJob(C.Structure):
+    """Mirror of ``struct ldc_fv_prolong_tables_job`` -- keep field order in sync with the header."""
+    _fields_ = (
+        [(n, _dp) for n in ("coarse_u", "coarse_v", "coarse_p", "coarse_ulid", "coarse_xc", "coarse_yc", "fine_u", "fine_v",
+                            "fine_p", "fine_mdot", "fine_x_grid", "fine_y_grid", "fine_xc", "fine_yc")]
+        + [(n, C.c_double) for n in ("Lx", "Ly", "rho")]
+        + [(n, C.c_int32) for n in ("coarse_nx", "coarse_ny", "fine_nx", "fine_ny")]
+    )
+
+
 # every symbol include/ldc_fv.h declares (tests check the .so exports all of them)
 EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue", "ldc_fv_batch_enqueue",
            "ldc_fv_status", "ldc_fv_step_debug", "ldc_fv_set_pressure", "ldc_fv_set_grid", "ldc_fv_set_preconditioner", "ldc_fv_post_enqueue", "ldc_fv_prolong_enqueue",
@@ -128,7 +139,7 @@ EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue"
            "ldc_fv_wide_prolong_enqueue", "ldc_fv_wide_set_anderson", "ldc_fv_wide_set_pressure",
            "ldc_fv_wide_set_pressure_budget", "ldc_fv_wide_batch_set_pressure_budget", "ldc_fv_sample_nodes",
            "ldc_fv_wall_post_enqueue", "ldc_fv_wall_post_launches", "ldc_fv_wall_stretched_post_enqueue",
-           "ldc_fv_wall_stretched_post_launches")
+           "ldc_fv_wall_stretched_post_launches", "ldc_fv_prolong_tables_enqueue", "ldc_fv_prolong_tables_launches")
 
 _bound = None
 
@@ -228,6 +239,8 @@ def lib() -> C.CDLL:
         L.ldc_fv_wall_post_launches.argtypes = [C.c_int]
         L.ldc_fv_wall_stretched_post_enqueue.argtypes = [C.POINTER(WallStretchedJob), C.c_int, _dp]
         L.ldc_fv_wall_stretched_post_launches.argtypes = [C.c_int]
+        L.ldc_fv_prolong_tables_enqueue.argtypes = [C.POINTER(ProlongTablesJob), C.c_int, _dp]
+        L.ldc_fv_prolong_tables_launches.argtypes = [C.c_int]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -375,3 +388,11 @@ def wall_stretched_post_enqueue(jobs, stream) -> None:
     which the library checks first and launches WALL_STRETCHED_LAUNCH_MAX at a time, seven launches each; nothing synchronises."""
     arr = (WallStretchedJob * len(jobs))(*jobs)
     check(lib().ldc_fv_wall_stretched_post_enqueue(arr, len(jobs), _dp(stream)), "ldc_fv_wall_stretched_post_enqueue")
+
+
+def prolong_tables_enqueue(jobs, stream) -> None:
+    """The fine u, v, p and mdot of every ``ProlongTablesJob`` from its coarse state, the geometry of both read from tables
+    (tensor grids with any spacing per axis; include/ldc_fv.h): ONE call for all jobs, which the library checks first and
+    launches PROLONG_TABLES_LAUNCH_MAX at a time, one work-group each; nothing synchronises."""
+    arr = (ProlongTablesJob * len(jobs))(*jobs)
+    check(lib().ldc_fv_prolong_tables_enqueue(arr, len(jobs), _dp(stream)), "ldc_fv_prolong_tables_enqueue")

@@ -19,6 +19,9 @@ geometry read from per-axis tables, either pressure equation); its vortex metric
 reference's rule, or with ``streamfunction="wall_stretched"`` on the device by the wall rule on the stretched mesh
 (``ldc_fv_wall_stretched_post_enqueue``: the Dirichlet generalised eigenpairs of each axis, the quadratic fit with unequal
 spacing; such trials of a call share seven launches per 32 of them).
+``transfer="tables"`` on the FINE trial of a pair lets ``prolong`` / ``start_from`` read both grids from per-axis tables
+(``ldc_fv_prolong_tables_enqueue``: one work-group per pair, 23 pairs per launch), so stretched trials are sequenced, continued
+in Re and started from uniform ones; the default ``"uniform"`` is the equal-spacing transfer of before.
 """
 from __future__ import annotations
 
@@ -46,6 +49,9 @@ WALL_RULES = ("wall", "wall_stretched")      # the wall rule on equal spacing, a
 VORTEX_REFINES = ("none", "quadratic")
 GRIDS = ("uniform", "tanh")
 PRESSURE_PRECONDITIONERS = ("laplacian", "separable")
+# what prolong / start_from / the levels of solver=fv/fsg read the geometry from: "uniform" (dx, dy: the equal-spacing kernels)
+# or "tables" (per-axis tables of centres, widths and face weights: ldc_fv_prolong_tables_enqueue, either grid, mapping "cu")
+TRANSFERS = ("uniform", "tables")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
 
 
@@ -126,6 +132,22 @@ def grid_axis(n: int, L: float, beta: float, device, rho=1.0):
         _grid_cache[key] = (torch.tensor(np.concatenate([h, d, g]), **f64), torch.tensor(lam, **f64),
                             torch.tensor(Q, **f64).contiguous())
     return _grid_cache[key]
+
+
+_transfer_cache = {}
+
+
+def transfer_axis(n: int, L: float, beta: float, device):
+    """The device tensor of one axis of ``ldc_fv_prolong_tables_enqueue``, [xc (n) | h (n) | d (n + 1) | g (n + 1)], cached per
+    (n, L, beta, device) like ``grid_axis``: the cell centres, then the geometry table of ``ldc_fv_set_grid``.  ``beta`` = 0 is
+    an equally spaced axis (a uniform trial): the same table of its vertices k L / n, and no eigen-decomposition either way."""
+    import torch
+    device = torch.device(device)
+    key = (int(n), float(L), float(beta), device.type, torch.cuda.current_device() if device.index is None else device.index)
+    if key not in _transfer_cache:
+        xc, h, d, g = axis_tables(tanh_vertices(n, L, beta))
+        _transfer_cache[key] = torch.tensor(np.concatenate([xc, h, d, g]), dtype=torch.float64, device=device)
+    return _transfer_cache[key]
 
 
 def dirichlet_eig_host(h, d):
@@ -331,16 +353,27 @@ def post_route(vortex_metrics: str, has_cu_handle: bool, streamfunction: str = "
     return "chip" if vortex_metrics == "chip" or not has_cu_handle else "cu"
 
 
-def prolong_route(coarse_has_cu: bool, fine_has_cu: bool, coarse_chip: bool, fine_chip: bool) -> str:
-    """The entry that prolongs a (coarse, fine) pair: ``"cu"`` (``ldc_fv_prolong_enqueue``) when both trials have a one-CU
+def prolong_route(coarse_has_cu: bool, fine_has_cu: bool, coarse_chip: bool, fine_chip: bool, fine_tables: bool = False) -> str:
+    """The entry that prolongs a (coarse, fine) pair: ``"tables"`` (``ldc_fv_prolong_tables_enqueue``: the geometry of both
+    from per-axis tables) when the FINE trial has ``transfer="tables"``, whatever the coarse one's grid and option; else
+    ``"cu"`` (``ldc_fv_prolong_enqueue``) when both trials have a one-CU
     handle; else ``"chip"`` (``ldc_fv_wide_prolong_enqueue``), which takes the whole-chip handles of both: a trial without
     one is a ``ValueError``."""
+    if fine_tables:
+        if not (coarse_has_cu and fine_has_cu):
+            raise ValueError(f"prolong: transfer='tables' takes trials of at most {F.MAX_N} cells per axis on both sides")
+        return "tables"
     if coarse_has_cu and fine_has_cu:
         return "cu"
     if coarse_chip and fine_chip:
         return "chip"
     raise ValueError(f"prolong: a trial above {F.MAX_N} cells per axis is prolonged through the whole-chip handles of both "
                      f"trials, and one of them has none: give the coarse trial mapping='chip' (or 'shared')")
+
+
+def _same_extent(a: float, b: float) -> bool:
+    """One domain length, to the rounding the equal-spacing kernels allow (1e-12 relative)."""
+    return abs(float(a) - float(b)) <= 1e-12 * max(abs(float(a)), abs(float(b)))
 
 
 def postprocess(trials):
@@ -424,40 +457,55 @@ def prolong(pairs):
 
     A pair with a trial above 256 cells per axis (no one-CU handle) goes through ``ldc_fv_wide_prolong_enqueue`` instead,
     two launches over the whole chip per pair, the same arithmetic; both its trials must then be ``mapping="chip"`` or
-    ``"shared"`` trials (``prolong_route``)."""
+    ``"shared"`` trials (``prolong_route``).
+
+    A pair whose FINE trial has ``transfer="tables"`` goes through ``ldc_fv_prolong_tables_enqueue``: the same transfer with
+    the geometry of both trials read from per-axis tables, so either may be a ``grid="tanh"`` trial (the coarse one with any
+    ``transfer``); all such pairs of a call are one call of the library, 23 per launch, one work-group each.  A pair with a
+    stretched trial whose fine trial lacks the option is refused."""
     import torch
     from solvers.spectral import ldc_lib
     pairs = list(pairs)
     if not pairs:
         return
-    for c, f in pairs:
-        if c.stretched or f.stretched:
+    # (getattr: a trial built before the option, or a stand-in that has only `stretched`, is a transfer="uniform" trial)
+    by_tables = [bool(getattr(f, "transfer_tables", False)) for _, f in pairs]
+    for (c, f), tables in zip(pairs, by_tables):
+        if (c.stretched or f.stretched) and not tables:
             raise ValueError("prolong / start_from with grid='tanh': the prolongation kernel assumes equal spacing on both "
-                             "trials")
+                             "trials; give the FINE trial transfer='tables' (the transfer that reads both grids from tables)")
     dev = pairs[0][1].device
     index = torch.cuda.current_device() if dev.index is None else dev.index
-    routes = [prolong_route(c._has_cu_handle, f._has_cu_handle, c.chip, f.chip) for c, f in pairs]
+    routes = [prolong_route(c._has_cu_handle, f._has_cu_handle, c.chip, f.chip, tables)
+              for (c, f), tables in zip(pairs, by_tables)]
     for (c, f), route in zip(pairs, routes):
         for s in (c, f):
-            if route == "cu":
+            if route in ("cu", "tables"):
                 s._require_cu_handle("prolong")
             elif s._wide is None:
                 raise ValueError(f"prolong: a trial of {s.nx} x {s.ny} cells has no whole-chip handle")
             if (torch.cuda.current_device() if s.device.index is None else s.device.index) != index:
                 raise ValueError("prolong: all trials must be on one device")
+        if route == "tables" and not (_same_extent(c.params.Lx, f.params.Lx) and _same_extent(c.params.Ly, f.params.Ly)):
+            raise ValueError(f"prolong: the trials of a pair cover one domain, got Lx, Ly = {c.params.Lx}, {c.params.Ly} and "
+                             f"{f.params.Lx}, {f.params.Ly}")
     cu = [pair for pair, route in zip(pairs, routes) if route == "cu"]
     chip = [pair for pair, route in zip(pairs, routes) if route == "chip"]
-    if chip:        # (the library checks the one-CU pairs of a call together; with others beside them the rule is kept here)
+    tables = [pair for pair, route in zip(pairs, routes) if route == "tables"]
+    if chip or tables:  # (the library checks the pairs of ONE of its calls together; with others beside them the rule is kept here)
         for q, (_, f) in enumerate(pairs):
             if any(f is c2 or (r != q and f is f2) for r, (c2, f2) in enumerate(pairs)):
                 raise ValueError("prolong: a fine trial is the coarse or the fine trial of another pair of the call")
     with torch.cuda.device(dev):
+        jobs = [f._prolong_tables_job(c) for c, f in tables]
         with ldc_lib.resident_lock(index):
             stream = torch.cuda.current_stream(dev).cuda_stream
             if cu:
                 F.prolong_enqueue([c.handle for c, _ in cu], [f.handle for _, f in cu], stream)
             for c, f in chip:
                 F.wide_prolong_enqueue(c._wide, f._wide, stream)
+            if jobs:
+                F.prolong_tables_enqueue(jobs, stream)
             torch.cuda.current_stream(dev).synchronize()      # (the lock goes back with the CUs free)
     for _, f in pairs:
         f._post = None
@@ -807,6 +855,12 @@ class FVSolver(LidDrivenCavitySolver):
             raise ValueError(f"pressure_max_iters={p.pressure_max_iters}: CG iterations per pressure solve, at least 1")
         if int(p.pressure_budget) < 1:
             raise ValueError(f"pressure_budget={p.pressure_budget}: CG iterations per SIMPLE iteration, at least 1")
+        if p.transfer not in TRANSFERS:
+            raise ValueError(f"transfer={p.transfer!r}: 'uniform' or 'tables'")
+        self.transfer_tables = p.transfer == "tables"       # prolong() routes the pairs this trial is the FINE one of on it
+        if self.transfer_tables and p.mapping != "cu":
+            raise ValueError(f"transfer='tables' with mapping={p.mapping!r}: the transfer that reads the grids from tables "
+                             f"takes mapping='cu' trials")
         if p.grid not in GRIDS:
             raise ValueError(f"grid={p.grid!r}: 'uniform' or 'tanh'")
         self.stretched = p.grid == "tanh"         # geometry tables on the handle: fv_stretched_kernel advances the trial
@@ -819,9 +873,10 @@ class FVSolver(LidDrivenCavitySolver):
             if p.acceleration != "none":
                 raise ValueError(f"grid='tanh' with acceleration={p.acceleration!r}: Anderson mixing has not been tested "
                                  f"on stretched grids, give the trial acceleration='none'")
-            if self._needs_cu_handle:
+            if self._needs_cu_handle and not self.transfer_tables:
                 raise ValueError("grid='tanh' with solver=fv/fsg: the prolongation between the levels assumes equal "
-                                 "spacing, run the trial with solver=fv")
+                                 "spacing, run the trial with solver=fv (or give it transfer='tables', the transfer that "
+                                 "reads the grids of both levels from tables)")
             # (streamfunction="wall_stretched" is served on the device by ldc_fv_wall_stretched_post_enqueue and does not
             # consult vortex_metrics, as "wall" does not for uniform trials)
             if p.vortex_metrics != "host" and p.streamfunction != "wall_stretched":
@@ -1044,6 +1099,27 @@ class FVSolver(LidDrivenCavitySolver):
         its other parameters may differ) by one prolongation (``prolong``): a coarser trial to start from, or a trial of
         this size at another Re to continue from."""
         prolong([(other, self)])
+
+    def _transfer_axes(self):
+        """(x, y) tensors [xc | h | d | g] of this trial's mesh (``transfer_axis``: shared per axis, mesh and device); a
+        uniform trial is the mesh at beta = 0."""
+        p = self.params
+        beta = float(p.grid_stretch) if self.stretched else 0.0
+        return transfer_axis(self.nx, p.Lx, beta, self.device), transfer_axis(self.ny, p.Ly, beta, self.device)
+
+    def _prolong_tables_job(self, coarse: "FVSolver") -> F.ProlongTablesJob:
+        """The job of a ``prolong_tables_enqueue`` call that starts THIS trial from ``coarse``: the coarse state, lid profile
+        and centres, this trial's state, geometry tables and centres, the domain and this trial's rho."""
+        t, c = self.t, coarse.t
+        fx, fy = self._transfer_axes()
+        cx, cy = coarse._transfer_axes()
+        return F.ProlongTablesJob(
+            coarse_u=c["u"].data_ptr(), coarse_v=c["v"].data_ptr(), coarse_p=c["p"].data_ptr(),
+            coarse_ulid=c["ulid"].data_ptr(), coarse_xc=cx.data_ptr(), coarse_yc=cy.data_ptr(),
+            fine_u=t["u"].data_ptr(), fine_v=t["v"].data_ptr(), fine_p=t["p"].data_ptr(), fine_mdot=t["mdot"].data_ptr(),
+            fine_x_grid=fx[self.nx:].data_ptr(), fine_y_grid=fy[self.ny:].data_ptr(), fine_xc=fx.data_ptr(),
+            fine_yc=fy.data_ptr(), Lx=float(self.params.Lx), Ly=float(self.params.Ly), rho=float(self.rho),
+            coarse_nx=coarse.nx, coarse_ny=coarse.ny, fine_nx=self.nx, fine_ny=self.ny)
 
     # ---- state access (tests, tools) -------------------------------------------------------------------
     def set_state(self, u, v, p, mdot):

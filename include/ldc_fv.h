@@ -1,7 +1,8 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
  * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc and
  * csrc/ldc_fv_wide_pressure.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip, csrc/ldc_fv_wall_post.hip,
- * csrc/ldc_fv_stretched.hip, csrc/ldc_fv_stretched_sep.hip).
+ * csrc/ldc_fv_stretched.hip, csrc/ldc_fv_stretched_sep.hip, csrc/ldc_fv_wall_post_stretched.hip,
+ * csrc/ldc_fv_prolong_tables.hip).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -222,7 +223,8 @@
  *    block (384 .. 407); the descriptor itself does not change;
  *  - ldc_fv_step_debug on such a handle returns LDC_E_ARG.  ldc_fv_post_enqueue, ldc_fv_prolong_enqueue, ldc_fv_wall_post_enqueue,
  *    the sampling and the mixing kernel's callers assume equal spacing: the solver refuses those combinations.  The wall rule
- *    of such a trial is ldc_fv_wall_stretched_post_enqueue (below).
+ *    of such a trial is ldc_fv_wall_stretched_post_enqueue, its coarse-to-fine transfer ldc_fv_prolong_tables_enqueue (both
+ *    below).
  *
  * The separable scaled preconditioner of such a trial (ldc_fv_set_preconditioner; csrc/ldc_fv_stretched_sep.hip, a unit of
  * its own so that fv_stretched_kernel stays what it was).  In consistent mode the CG above is preconditioned by the operator
@@ -351,6 +353,30 @@
  *  - the mapping and the scratch (LDC_FV_WALL_SCRATCH_LEN) are those of ldc_fv_wall_post_enqueue, seven launches per group of
  *    up to LDC_FV_WALL_STRETCHED_LAUNCH_MAX jobs; a job's psi, omega and block do not depend on what else is in the call,
  *    bit for bit.  Two jobs may share tables, never scratch, psi, omega or result.
+ *
+ * The coarse-to-fine transfer on tensor grids with any spacing per axis (csrc/ldc_fv_prolong_tables.hip,
+ * ldc_fv_prolong_tables_enqueue; a unit of its own, every other code object stays what it was): what ldc_fv_prolong_enqueue
+ * does for two equally spaced trials, with the geometry of both read from tables, so that a stretched trial can start from a
+ * coarser one, from a trial of its own size at another Re, or from a uniform one (and the other way round).  A job holds raw
+ * device pointers only, no handle (a uniform source has no tables on its handle), LDC_FV_MIN_N .. LDC_FV_MAX_N cells per
+ * axis on both sides; the coarse state is only read.  tests/fv_prolong_tables_numpy.py states it operation by operation.
+ *  - tables: per coarse axis ONE table of its n cell centres, ascending inside (0, L); per fine axis the same, and the
+ *    geometry table [h (n) | d (n + 1) | g (n + 1)] of ldc_fv_set_grid (for an equally spaced trial the table of its vertices
+ *    k L / n); Lx, Ly are the domain lengths of BOTH trials;
+ *  - the extended coarse axis has the nodes e_0 = 0, e_k = xc[k-1] (k = 1 .. n), e_(n+1) = L; the ring values are those of
+ *    ldc_fv_prolong_enqueue: u and v 0.0 on the walls and corners, u above cell i on the lid the COARSE ulid[i], p repeats the
+ *    nearest cell;
+ *  - a fine centre x takes the largest k <= n with e_k <= x (k = 0 when there is none), found by bisection, and the weight
+ *    t = (x - e_k) / (e_(k+1) - e_k); the value is bilinear with x first, lo = a + tx (b - a), hi likewise on the row above,
+ *    then lo + ty (hi - lo); every thread subtracts from p the interpolated p at fine cell 0, so p[0] is exactly 0.0;
+ *  - mdot from the new u and v by the face rule of the stretched kernels: x face i of row j, 0 < i < nx, is
+ *    rho ((g_x[i] u[j][i] + (1 - g_x[i]) u[j][i-1]) hy[j]), the y faces likewise with g_y and hx; the faces on the four walls
+ *    are exactly 0.0.  No multiply-add is contracted;
+ *  - the mapping: one work-group of 512 threads per job, LDC_FV_PROLONG_TABLES_LAUNCH_MAX jobs per launch, the job structs
+ *    travelling as kernel arguments, no waits between work-groups, no reduction, no scratch.  (k, t) of the nx + ny fine
+ *    centres go to LDS first, one bisection per thread; then the cells; then the faces, a barrier between the phases.  A job's
+ *    result does not depend on what else is in the call, bit for bit;
+ *  - written: the fine u, v, p (ny x nx each) and mdot (LDC_FV_FACES), nothing else: no ctrl, no rec, no work vector.
  */
 #ifndef LDC_FV_H
 #define LDC_FV_H
@@ -433,6 +459,8 @@ extern "C" {
 /* LDC_FV_WALL_SX / SY as fractions of the distance to the neighbour on the step's side                                    */
 #define LDC_FV_WALL_STRETCHED_LAUNCH_MAX 32
 #define LDC_FV_WALL_STRETCHED_TABLE_LEN(n) ((int64_t)(n) * ((int64_t)(n) + 2))
+/* ldc_fv_prolong_tables_enqueue: jobs per launch (152 bytes per job in the arguments) */
+#define LDC_FV_PROLONG_TABLES_LAUNCH_MAX 23
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
 #define LDC_FV_DBG_GRAD_P 0        /* 2n: d/dx p, then d/dy p                                    */
@@ -560,6 +588,20 @@ struct ldc_fv_wall_stretched_job {
   int32_t ix_lt, ix_gt;           /* as in ldc_fv_post: 0 .. nx */
   int32_t jy_lt, jy_gt;           /* 0 .. ny */
   int32_t refine, pad;            /* 0: the cells' own values in the groups; 1: the quadratic fit */
+};
+
+struct ldc_fv_prolong_tables_job {
+  const double *coarse_u, *coarse_v, *coarse_p; /* the coarse state (coarse_ny x coarse_nx, c = j*nx + i): only read */
+  const double *coarse_ulid;      /* the coarse lid profile (coarse_nx) */
+  const double *coarse_xc, *coarse_yc; /* the coarse cell centres (coarse_nx), (coarse_ny) */
+  double *fine_u, *fine_v, *fine_p; /* out: fine_ny x fine_nx each */
+  double *fine_mdot;              /* out: LDC_FV_FACES(fine_nx, fine_ny) */
+  const double *fine_x_grid, *fine_y_grid; /* the fine geometry tables [h | d | g]: LDC_FV_GRID_TABLE_LEN(fine_nx), .. (fine_ny) */
+  const double *fine_xc, *fine_yc; /* the fine cell centres (fine_nx), (fine_ny) */
+  double Lx, Ly;                  /* > 0: the domain of both trials */
+  double rho;                     /* > 0: the fine trial's */
+  int32_t coarse_nx, coarse_ny;   /* LDC_FV_MIN_N .. LDC_FV_MAX_N each */
+  int32_t fine_nx, fine_ny;       /* LDC_FV_MIN_N .. LDC_FV_MAX_N each */
 };
 
 typedef struct ldc_fv ldc_fv;
@@ -722,6 +764,17 @@ int ldc_fv_wall_post_launches(int n);
 int ldc_fv_wall_stretched_post_enqueue(const struct ldc_fv_wall_stretched_job *jobs, int n, void *stream);
 /* Kernel launches of that call: 7 per group of LDC_FV_WALL_STRETCHED_LAUNCH_MAX jobs.  Needs no device; LDC_E_ARG for n < 1. */
 int ldc_fv_wall_stretched_post_launches(int n);
+/* n jobs (a host array; every pointer inside a job is a device pointer, nothing of it in flight elsewhere): the fine u, v, p */
+/* and mdot of every job from its coarse state as described above, ldc_fv_prolong_tables_launches(n) launches on `stream`,     */
+/* one work-group of 512 threads per job, nothing synchronises.  Validation comes before any launch and needs no device:       */
+/* LDC_E_ARG for a null list or n < 1, for a null pointer in a job, for a size outside LDC_FV_MIN_N .. LDC_FV_MAX_N, for Lx, Ly */
+/* or rho not > 0, and for a fine u, v, p or mdot that is also another field of its job, a coarse field of any job of the call  */
+/* or a fine field of another (what a launch writes nobody else in it may touch, however many launches the call takes); then    */
+/* LDC_E_NODEVICE.  A refused call launches nothing.  Several jobs may share a coarse state and tables.  The tables are the     */
+/* caller's to get right.                                                                                                      */
+int ldc_fv_prolong_tables_enqueue(const struct ldc_fv_prolong_tables_job *jobs, int n, void *stream);
+/* Kernel launches of that call: 1 per group of LDC_FV_PROLONG_TABLES_LAUNCH_MAX jobs.  Needs no device; LDC_E_ARG for n < 1. */
+int ldc_fv_prolong_tables_launches(int n);
 
 #ifdef __cplusplus
 }
