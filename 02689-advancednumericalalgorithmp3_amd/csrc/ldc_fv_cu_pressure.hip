@@ -11,11 +11,10 @@
 //   1. fv_assemble, 2. fv_bicgstab          unchanged (ldc_fv_cu_phases.inc)
 //   3. fv_cu_faces      fv_cell_faces on a context whose fluxes point at the dead work vectors PCG_MS: mdot* waits there,
 //                       and mdot is not touched before the solve is over (wide_pcg_faces); the sum of rhs_p
-//   4. fv_cu_pcg        conjugate gradients on A x = b from x = 0 with z = L+ r, the loop of the chip chain
-//                       (ldc_fv_wide_pressure.inc) between barriers where that one has launch boundaries: b, |b|^2; then
-//                       per iteration the stop test, four fv_gemm, r.z, p = z + beta p, q = A p and p.q, x += alpha p,
-//                       r -= alpha q and |r|^2.  One copy of p: the barrier between its update and the product does what
-//                       the chip chain's two alternating copies do.
+//   4. fv_pcg           conjugate gradients on A x = b from x = 0 with z = L+ r.  The loop, the four-GEMM solve
+//                       (fv_fastdiag) and the kernel frame are ldc_fv_cu_solve.inc, shared with the stretched-grid
+//                       kernels; this unit contributes FvCuPolicy: the Laplacian's eigenpairs with dy/dx, dx/dy and the
+//                       row of A on the uniform grid (wide_pcg_row).
 //   5. fv_correct       unchanged (p' = x - x_0, u' = -D grad p')
 //   6. fv_cu_fluxvort   mdot = mdot* - w_f (p'_N - p'_P), walls 0.0, the vorticity (wide_pcg_cell_fluxvort)
 //   7. fv_record        unchanged
@@ -41,11 +40,7 @@ namespace {
 typedef const __attribute__((address_space(4))) char* kernarg_ptr;
 
 #include "ldc_fv_cu_phases.inc"
-
-// this launch's increments of the caller's statistics words (last: the last solve's count)
-struct FvCuPcgRun {
-  long long iters, solves, caps, last;
-};
+#include "ldc_fv_cu_solve.inc"
 
 // ---- 3. fv_face_fluxes with mdot* left in the work vectors PCG_MS; b00 = minus the sum of rhs_p, entry 0 of b
 __device__ __forceinline__ void fv_cu_faces(const FvCtx& x, FvRed& red, double& b00) {
@@ -62,69 +57,24 @@ __device__ __forceinline__ void fv_cu_faces(const FvCtx& x, FvRed& red, double& 
   b00 = -csum[0];
 }
 
-// ---- 4. A x = b by preconditioned conjugate gradients (tests/fv_consistent_numpy.py::FVConsistentState.pcg)
-__device__ __forceinline__ void fv_cu_pcg(const FvCtx& x, const FvCuPcg& P, FvRed& red, double b00, FvCuPcgRun& st) {
-  const FvDesc& d = x.d;
-  const int nx = x.nx, ny = x.ny, n = x.n, tid = threadIdx.x;
-  const double ax = x.dy / x.dx, ay = x.dx / x.dy;
-  double bb[1] = {0.0};
-  for (int c = tid; c < n; c += kFvThreads) {
-    const double b = c == 0 ? b00 : x.vec(FV_C)[c];
-    x.vec(PCG_R)[c] = b;
-    x.vec(FV_Y)[c] = 0.0;
-    bb[0] += b * b;
+// ---- 4. what fv_pcg (ldc_fv_cu_solve.inc) takes from this unit: z = L+ r with the Laplacian's eigenpairs of the
+//         descriptor, and the row of A on the uniform grid (wide_pcg_row, ldc_fv_pressure_cells.inc).  ax = dy / dx and
+//         ay = dx / dy are formed once per solve, where the policy is made
+struct FvCuPolicy {
+  const FvCtx& x;
+  const double ax, ay;
+  __device__ __forceinline__ void start(int, double) const {}
+  __device__ __forceinline__ void precondition() const {
+    const FvDesc& d = x.d;
+    fv_fastdiag(x, d.Qx, d.lamx, d.Qy, d.lamy, ax, ay, x.vec(PCG_R), x.vec(PCG_Z));
   }
-  red.sum(bb);
-  double rr = bb[0], rz_prev = 0.0;
-  bool act = bb[0] != 0.0;
-  int its = 0;
-  for (int it = 0; it < P.max_iters && act; ++it) {
-    if (sqrt(rr) <= P.tol * sqrt(bb[0])) { act = false; break; }
-    // z = L+ r: W1 = Qy^T R, W2 = W1 Qx / Lambda (zero mode dropped), W1 = Qy W2, Z = W1 Qx^T (wide_pcg_gemm_of)
-    fv_gemm<false>(d.Qy, 1, ny, x.vec(PCG_R), nx, 1, x.vec(FV_W1), ny, nx, ny, nullptr, nullptr, 0, 0);
-    __syncthreads();
-    fv_gemm<true>(x.vec(FV_W1), nx, 1, d.Qx, nx, 1, x.vec(FV_W2), ny, nx, nx, d.lamx, d.lamy, ax, ay);
-    __syncthreads();
-    fv_gemm<false>(d.Qy, ny, 1, x.vec(FV_W2), nx, 1, x.vec(FV_W1), ny, nx, ny, nullptr, nullptr, 0, 0);
-    __syncthreads();
-    fv_gemm<false>(x.vec(FV_W1), nx, 1, d.Qx, 1, nx, x.vec(PCG_Z), ny, nx, nx, nullptr, nullptr, 0, 0);
-    __syncthreads();
-    double rz[1] = {0.0};
-    for (int c = tid; c < n; c += kFvThreads) rz[0] += x.vec(PCG_R)[c] * x.vec(PCG_Z)[c];
-    red.sum(rz);
-    const double beta = it > 0 ? rz[0] / rz_prev : 0.0;
-    rz_prev = rz[0];
-    for (int c = tid; c < n; c += kFvThreads) {
-      double* p = x.vec(PCG_P);
-      p[c] = it > 0 ? fma(beta, p[c], x.vec(PCG_Z)[c]) : x.vec(PCG_Z)[c];
-    }
-    __syncthreads();
-    double pq[1] = {0.0};
-    for (int c = tid; c < n; c += kFvThreads) {
-      const double* p = x.vec(PCG_P);
-      const double pc = p[c];
-      const double y = wide_pcg_row(x, c, c % nx, c / nx, pc, [&](int k) { return p[k]; });
-      x.vec(PCG_Q)[c] = y;
-      pq[0] += pc * y;
-    }
-    red.sum(pq);
-    const double alpha = rz[0] / pq[0];
-    double r2[1] = {0.0};
-    for (int c = tid; c < n; c += kFvThreads) {
-      double* r = x.vec(PCG_R);
-      x.vec(FV_Y)[c] += alpha * x.vec(PCG_P)[c];
-      const double rn = r[c] - alpha * x.vec(PCG_Q)[c];
-      r[c] = rn;
-      r2[0] += rn * rn;
-    }
-    red.sum(r2);
-    rr = r2[0];
-    its = it + 1;
+  __device__ __forceinline__ const double* src() const { return x.vec(PCG_R); }
+  __device__ __forceinline__ double z(int c) const { return x.vec(PCG_Z)[c]; }
+  __device__ __forceinline__ double row(int c, int i, int j, double pc, const double* p) const {
+    return wide_pcg_row(x, c, i, j, pc, [&](int k) { return p[k]; });
   }
-  if (act && sqrt(rr) <= P.tol * sqrt(bb[0])) act = false;      // (converged with the last iteration the cap allows)
-  st.iters += its; st.solves += 1; st.caps += act ? 1 : 0; st.last = its;
-  __syncthreads();
-}
+  __device__ __forceinline__ void residual(int, double) const {}
+};
 
 // ---- 6. mdot = mdot* - w_f (p'_N - p'_P) on the inner faces, exactly 0.0 on the walls; the vorticity
 __device__ __forceinline__ void fv_cu_fluxvort(const FvCtx& x, double (&part)[kFvRed]) {
@@ -136,53 +86,34 @@ __device__ __forceinline__ void fv_cu_fluxvort(const FvCtx& x, double (&part)[kF
 
 __global__ __launch_bounds__(kFvThreads) void fv_cu_pressure_kernel(FvLaunch L) {
   __shared__ double lds[2][kFvWaves * kFvRed];
-  // (the descriptor pointer from the kernarg segment: fv_kernel says why)
-  typedef const FvDesc* FvDescPtr;
-  const FvDesc& d = **(const __attribute__((address_space(4))) FvDescPtr*)((kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr() +
-                                                                           __builtin_offsetof(FvLaunch, d) + blockIdx.x * sizeof(FvDescPtr));
-  const FvCuPcg& P = *reinterpret_cast<const FvCuPcg*>(reinterpret_cast<const char*>(&d) + kFvCuPcgOffset);
+  const FvDesc& d = fv_block_desc();
+  const FvCuPcg& P = fv_slot_block<FvCuPcg>(d, kFvCuPcgOffset);
   const FvCtx x(d);
   const FvDebug dbg = {};                    // (phases 5 and 7 are the production instantiations: they read nothing of it)
   FvRed red = {lds, 0};
   FvRun run = {d.ctrl[0], d.ctrl[1], 0, 0, 0, d.ctrl[2] != 0};
-  FvCuPcgRun st = {0, 0, 0, 0};
+  FvPcgRun st = {0, 0, 0, 0};
   for (int k = 0; k < L.n_iters && !run.done && !run.nan_seen; ++k) {
     double b2[2];
     fv_assemble(x, red, b2);
     fv_bicgstab(x, red, b2, run);
     double b00;
     fv_cu_faces(x, red, b00);
-    fv_cu_pcg(x, P, red, b00, st);
+    fv_pcg(x, FvCuPolicy{x, x.dy / x.dx, x.dx / x.dy}, P, red, b00, st);
     double part[kFvRed] = {0.0};           // the sums of the record row (fv_correct)
     fv_correct<false>(x, part, dbg);
     fv_cu_fluxvort(x, part);
     fv_record<false>(x, red, part, k, run, dbg);
   }
   if (threadIdx.x == 0) {
-    d.ctrl[0] = run.done; d.ctrl[1] = run.iter; d.ctrl[2] = run.nan_seen ? 1 : 0;
-    d.ctrl[3] += run.giveups; d.ctrl[4] += run.lin_iters; d.ctrl[5] += run.solves;
-    P.stats[0] += st.iters; P.stats[1] += st.solves; P.stats[2] += st.caps;
-    if (st.solves) P.stats[3] = st.last;
+    fv_store_run(d, run);
+    fv_store_stats(P, st);
   }
 }
 
 }  // namespace
 
 int ldc_fv_cu_pressure_launch(ldc_fv* const* hs, int n, int n_iters, void* stream) {
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
-  for (int lo = 0; lo < n; lo += LDC_FV_LAUNCH_MAX) {
-    FvLaunch L;
-    const int b = n - lo < LDC_FV_LAUNCH_MAX ? n - lo : LDC_FV_LAUNCH_MAX;
-    for (int q = 0; q < b; ++q) {
-      if (hs[lo + q]->device != dev || hs[lo + q]->pressure_mode != LDC_FV_PRESSURE_CONSISTENT) return LDC_E_STATE;
-      L.d[q] = hs[lo + q]->dev;
-    }
-    for (int q = b; q < LDC_FV_LAUNCH_MAX; ++q) L.d[q] = nullptr;
-    L.n_iters = n_iters;
-    hipLaunchKernelGGL(fv_cu_pressure_kernel, dim3(b), dim3(kFvThreads), 0, as_stream(stream), L);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
+  return fv_launch_chunks(fv_cu_pressure_kernel, hs, n, n_iters, stream,
+                          [](const ldc_fv* h) { return h->pressure_mode == LDC_FV_PRESSURE_CONSISTENT; });
 }

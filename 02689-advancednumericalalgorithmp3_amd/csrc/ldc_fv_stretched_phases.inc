@@ -2,9 +2,9 @@
 // not depend on how the pressure equation is preconditioned (include/ldc_fv.h, "Stretched grids of a one-CU trial"): the
 // context with the tables of both axes (SgCtx), sg_assemble, sg_faces, sg_fastdiag, the face weights and the row of the
 // consistent operator (sg_wx, sg_wy, sg_row), sg_correct, sg_fluxvort and sg_record.
-// Included INSIDE the anonymous namespace of its unit, behind ldc_fv_cu_phases.inc, by ldc_fv_stretched.hip
-// (fv_stretched_kernel, where this text stood: the bodies are what they were, character for character) and by
-// ldc_fv_stretched_sep.hip (fv_stretched_sep_kernel, whose CG loop has another preconditioner).  Each names its twin on the
+// Included INSIDE the anonymous namespace of its unit, behind ldc_fv_cu_phases.inc and ldc_fv_cu_solve.inc (fv_fastdiag,
+// and fv_pcg, the CG loop that calls sg_row), by ldc_fv_stretched.hip (fv_stretched_kernel) and by
+// ldc_fv_stretched_sep.hip (fv_stretched_sep_kernel, whose CG has another preconditioner).  Each names its twin on the
 // uniform grid.
 
 // the trial's context with the tables of both axes
@@ -16,10 +16,6 @@ struct SgCtx {
         gyf(g.ay + 2 * x_.ny + 1) {}
   __device__ __forceinline__ double V(int i, int j) const { return hx[i] * hy[j]; }
   __device__ __forceinline__ double D(int c, int i, int j) const { return V(i, j) / (x.w[FV_AP * x.n + c] + 1e-14); }
-};
-
-struct SgPcgRun {
-  long long iters, solves, caps, last;
 };
 
 // twin of fv_grad (ldc_fv_cells.inc): the distances of the faces instead of dx, dy
@@ -155,18 +151,9 @@ __device__ __forceinline__ void sg_faces(const SgCtx& s, FvRed& red, double& b00
   }
 }
 
-// ---- 4. z = L+ r (or the exact solve of the reference mode): the four GEMMs of fv_pressure_correction with ax = ay = 1
+// ---- 4. z = L+ r (or the exact solve of the reference mode): fv_fastdiag with ax = ay = 1 and the generalised eigenpairs
 __device__ __forceinline__ void sg_fastdiag(const FvCtx& x, const double* rhs, double* out) {
-  const FvDesc& d = x.d;
-  const int nx = x.nx, ny = x.ny;
-  fv_gemm<false>(d.Qy, 1, ny, rhs, nx, 1, x.vec(FV_W1), ny, nx, ny, nullptr, nullptr, 0, 0);
-  __syncthreads();
-  fv_gemm<true>(x.vec(FV_W1), nx, 1, d.Qx, nx, 1, x.vec(FV_W2), ny, nx, nx, d.lamx, d.lamy, 1.0, 1.0);
-  __syncthreads();
-  fv_gemm<false>(d.Qy, ny, 1, x.vec(FV_W2), nx, 1, x.vec(FV_W1), ny, nx, ny, nullptr, nullptr, 0, 0);
-  __syncthreads();
-  fv_gemm<false>(x.vec(FV_W1), nx, 1, d.Qx, 1, nx, out, ny, nx, nx, nullptr, nullptr, 0, 0);
-  __syncthreads();
+  fv_fastdiag(x, x.d.Qx, x.d.lamx, x.d.Qy, x.d.lamy, 1.0, 1.0, rhs, out);
 }
 
 // the weight of the inner x face k (between cells i = k - 1 and k of row j) / the inner y face k of column i;
@@ -180,10 +167,10 @@ __device__ __forceinline__ double sg_wy(const SgCtx& s, int i, int k, double DP,
   return (s.x.rho * (g * DN + (1.0 - g) * DP)) * (s.hx[i] / s.dyf[k]);
 }
 
-// twin of wide_pcg_row: (A p)_c
-__device__ __forceinline__ double sg_row(const SgCtx& s, int c, int i, int j, const double* p) {
+// twin of wide_pcg_row: (A p)_c, pc = p[c]
+__device__ __forceinline__ double sg_row(const SgCtx& s, int c, int i, int j, double pc, const double* p) {
   const int nx = s.x.nx, ny = s.x.ny;
-  const double Dc = s.D(c, i, j), pc = p[c];
+  const double Dc = s.D(c, i, j);
   double y = 0.0;
   if (i > 0) y += sg_wx(s, j, i, s.D(c - 1, i - 1, j), Dc) * (pc - p[c - 1]);
   if (i < nx - 1) y += sg_wx(s, j, i + 1, Dc, s.D(c + 1, i + 1, j)) * (pc - p[c + 1]);

@@ -240,6 +240,9 @@ def test_set_preconditioner_is_declared_exported_and_bound(fvlib):
     # the shared phases moved into an include of both units
     for unit in ("ldc_fv_stretched.hip", "ldc_fv_stretched_sep.hip"):
         assert '#include "ldc_fv_stretched_phases.inc"' in (PKG / "csrc" / unit).read_text()
+    # the CG loop, the four-GEMM solve and the kernel frame: one include of the three units with a pressure CG of their own
+    for unit in ("ldc_fv_cu_pressure.hip", "ldc_fv_stretched.hip", "ldc_fv_stretched_sep.hip"):
+        assert '#include "ldc_fv_cu_solve.inc"' in (PKG / "csrc" / unit).read_text()
 
 
 def test_set_preconditioner_validation_needs_no_device(fvlib):
