@@ -19,6 +19,9 @@
 // `faces | gemm x 4` and `fluxvort` by
 //   faces | init | min(pressure budget, pressure_max_iters) x (gemm x 4 | rz | ap | xr) | pfinish    and    fluxvort
 // of its own: conjugate gradients on the a_P-weighted operator, preconditioned by the same four GEMMs.
+// A lone trial with geometry tables (ldc_fv_wide_set_grid; ldc_fv_wide_stretched.inc) runs either chain on a wall-clustered
+// tensor grid: launch for launch the same, with stretched twins of the phases that read the geometry (assemble, faces,
+// correct, fluxvort, sums, ap) around the cell bodies of ldc_fv_stretched_cells.inc, which the one-CU stretched units call too.
 // Rules every kernel keeps:
 //  - the grid is a function of (nx, ny) alone;
 //  - a work-group writes its partial sums to its own slot; the NEXT launch lets every work-group add all slots in one
@@ -511,6 +514,10 @@ __device__ __forceinline__ void wide_record(const FvWideArgs& a, double* lds) {
 // ---- 9. the consistent pressure equation: the launches that replace faces | gemm x 4 and fluxvort
 #include "ldc_fv_wide_pressure.inc"
 
+// ---- 10. a lone trial on a wall-clustered grid: the twins of the phases that read the geometry, from per-axis tables
+#include "ldc_fv_stretched_cells.inc"
+#include "ldc_fv_wide_stretched.inc"
+
 // ---- the kernels: every phase for a lone trial (arguments by value, g = blockIdx.x) and for a batch (the table)
 #define WIDE_LDS __shared__ double lds[kWW * kWS]
 // the trial and the work-group of this block of a batch launch, from a block map / for one work-group per trial
@@ -677,15 +684,20 @@ struct WideGraphs {
 struct ldc_fv_wide {
   FvWideArgs a;
   int device;
-  short graph;                               // replay ONE captured iteration per budget (ldc_fv_wide_set_graph)
+  signed char graph;                         // replay ONE captured iteration per budget (ldc_fv_wide_set_graph)
+  signed char grid_mode;                     // LDC_FV_GRID_*: tables attached (ldc_fv_wide_set_grid), `grid` below in use.
+                                             // In the head, in what was the high byte of `graph`: the calls that refuse a
+                                             // handle with tables read nothing behind the first 216 bytes of one without
   short mixing;                              // the iteration ends on the mixing chain (m.depth > 0).  Here, not in `m`:
                                              // ldc_fv_wide_launches reads nothing behind these first 216 bytes
   FvWideMix m;                               // ldc_fv_wide_set_anderson; all zero: no mixing
   WideGraphs gs;
   FvWidePcg x;                               // ldc_fv_wide_set_pressure (a.pmax > 0: in use).  Behind gs: nothing in front
   int pbudget;                               // of it moves, and only a handle with a.pmax > 0 is read this far
-};
-static_assert(sizeof(FvWideArgs) + sizeof(int) + 2 * sizeof(short) == 216, "the head of a handle");
+  FvGridBlk grid;                            // ldc_fv_wide_set_grid.  At the end, for the same reason: only a handle with
+};                                           // grid_mode LDC_FV_GRID_TABLES is read this far
+static_assert(LDC_FV_GRID_UNIFORM == 0, "a handle made of zeroes has the uniform grid");
+static_assert(sizeof(FvWideArgs) + sizeof(int) + 2 * sizeof(signed char) + sizeof(short) == 216, "the head of a handle");
 
 struct ldc_fv_wide_batch {
   int n, maxit, device, graph;               // (the head, with rec_cap, is all that validation without a device reads)
@@ -709,7 +721,10 @@ namespace {
 
 // the launches of ONE iteration with `nb` BiCGSTAB iterations and, for a trial with the consistent pressure equation, `np`
 // CG iterations; `par` alternates launch by launch
+int wide_sg_iteration(const ldc_fv_wide* h, int nb, int np, hipStream_t st);
+
 int wide_iteration(const ldc_fv_wide* h, int nb, int np, hipStream_t st) {
+  if (h->grid_mode == LDC_FV_GRID_TABLES) return wide_sg_iteration(h, nb, np, st);
   const FvWideArgs& a = h->a;
   const FvDesc& d = a.d;
   const int G = a.G, gg = (int)LDC_FV_WIDE_GEMM_GROUPS(d.nx, d.ny);
@@ -755,6 +770,56 @@ int wide_iteration(const ldc_fv_wide* h, int nb, int np, hipStream_t st) {
     WIDE_LAUNCH(fv_wide_mix_mix, G, kWT, a, h->m);
     WIDE_LAUNCH(fv_wide_mix_close, 1, 64, a, h->m);
   }
+  return 0;
+}
+
+// the same chain for a lone trial with geometry tables (ldc_fv_wide_set_grid; ldc_fv_wide_stretched.inc): launch for launch
+// the chain above, in the same grids and with the same `par`; the phases that read the geometry are their stretched twins,
+// and the scaled GEMM and `record` take the arguments with dx = dy = 1.  (No mixing chain: ldc_fv_wide_set_grid and
+// ldc_fv_wide_set_anderson refuse the combination.)
+int wide_sg_iteration(const ldc_fv_wide* h, int nb, int np, hipStream_t st) {
+  const FvWideArgs& a = h->a;
+  const FvWideArgs a1 = wide_sg_neutral(a);
+  const FvGridBlk& gb = h->grid;
+  const FvDesc& d = a.d;
+  const int G = a.G, gg = (int)LDC_FV_WIDE_GEMM_GROUPS(d.nx, d.ny);
+  int par = 0;
+  WIDE_LAUNCH(fv_wide_sg_assemble, G, kWT, a, gb, par); par ^= 1;
+  for (int it = 0; it < nb; ++it) {
+    WIDE_LAUNCH(fv_wide_bicg_p, G, kWT, a, it, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_bicg_v, G, kWT, a, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_bicg_s, G, kWT, a, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_bicg_t, G, kWT, a, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_bicg_x, G, kWT, a, it, par); par ^= 1;
+  }
+  WIDE_LAUNCH(fv_wide_linfinish, 1, kWT, a, nb, par); par ^= 1;
+  if (a.pmax == 0) {
+    WIDE_LAUNCH((fv_wide_sg_faces<false>), G, kWT, a, gb, par); par ^= 1;
+    WIDE_LAUNCH((fv_wide_gemm<true, false>), gg, kWT, a, wide_gemm_of(d, 0), par);
+    WIDE_LAUNCH((fv_wide_gemm<false, true>), gg, kWT, a1, wide_gemm_of(d, 1), par);
+    WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, wide_gemm_of(d, 2), par);
+    WIDE_LAUNCH((fv_wide_gemm<false, false>), gg, kWT, a, wide_gemm_of(d, 3), par);
+    WIDE_LAUNCH(fv_wide_sg_correct, G, kWT, a, gb);
+    WIDE_LAUNCH((fv_wide_sg_fluxvort<false>), G, kWT, a, gb);
+  } else {
+    const FvWidePcg& x = h->x;
+    WIDE_LAUNCH((fv_wide_sg_faces<true>), G, kWT, a, gb, par); par ^= 1;
+    WIDE_LAUNCH(fv_wide_pcg_init, G, kWT, a, par); par ^= 1;
+    for (int it = 0; it < np; ++it) {
+      WIDE_LAUNCH((fv_wide_pcg_gemm<true, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 0), it, par); par ^= 1;
+      WIDE_LAUNCH((fv_wide_pcg_gemm<false, true>), gg, kWT, a1, x, wide_pcg_gemm_of(d, 1), it, par);
+      WIDE_LAUNCH((fv_wide_pcg_gemm<false, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 2), it, par);
+      WIDE_LAUNCH((fv_wide_pcg_gemm<false, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 3), it, par);
+      WIDE_LAUNCH(fv_wide_pcg_rz, G, kWT, a, par); par ^= 1;
+      WIDE_LAUNCH(fv_wide_sg_pcg_ap, G, kWT, a, gb, it, par); par ^= 1;
+      WIDE_LAUNCH(fv_wide_pcg_xr, G, kWT, a, it, par); par ^= 1;
+    }
+    WIDE_LAUNCH(fv_wide_pcg_finish, 1, kWT, a, x, np, par);
+    WIDE_LAUNCH(fv_wide_sg_correct, G, kWT, a, gb);
+    WIDE_LAUNCH((fv_wide_sg_fluxvort<true>), G, kWT, a, gb);
+  }
+  WIDE_LAUNCH(fv_wide_sg_sums, G, kWT, a, gb);
+  WIDE_LAUNCH(fv_wide_record, 1, kWT, a1);
   return 0;
 }
 
@@ -917,6 +982,8 @@ int ldc_fv_wide_create(const struct ldc_fv_problem* pr, double* scratch, int64_t
   s->graph = LDC_FV_WIDE_GRAPH_DEFAULT;
   s->mixing = 0;
   s->m = FvWideMix{};
+  s->grid = FvGridBlk{};
+  s->grid_mode = LDC_FV_GRID_UNIFORM;
   *out = s;
   return 0;
 }
@@ -931,7 +998,7 @@ int ldc_fv_wide_destroy(ldc_fv_wide* h) {
 int ldc_fv_wide_set_graph(ldc_fv_wide* h, int on) {
   if (!h) return LDC_E_STATE;
   if (on != 0 && on != 1) return LDC_E_ARG;
-  h->graph = on;
+  h->graph = (signed char)on;
   return 0;
 }
 
@@ -944,6 +1011,7 @@ int ldc_fv_wide_set_anderson(ldc_fv_wide* h, const struct ldc_fv_anderson* acc, 
       const int nx = h->a.d.nx, ny = h->a.d.ny;
       if (!acc->hist || acc->hist_len < LDC_FV_ANDERSON_HIST_LEN(nx, ny, acc->depth)) return LDC_E_ARG;
       if (!scratch || scratch_len < LDC_FV_WIDE_ANDERSON_SCRATCH_LEN(nx, ny, acc->depth)) return LDC_E_ARG;
+      if (h->grid_mode == LDC_FV_GRID_TABLES) return LDC_E_ARG;             // (the mixing has not met a stretched trial)
       m.hist = acc->hist;
       m.astate = reinterpret_cast<long long*>(acc->astate);
       m.mscr = scratch;
@@ -972,6 +1040,25 @@ int ldc_fv_wide_set_pressure(ldc_fv_wide* h, const struct ldc_fv_pressure* cfg, 
   wide_graphs_free(h->gs);
   h->a.pmax = pmax;
   h->x = x;
+  return 0;
+}
+
+int ldc_fv_wide_set_grid(ldc_fv_wide* h, const struct ldc_fv_grid* grid) {
+  if (!h) return LDC_E_ARG;
+  FvGridBlk blk = {};
+  int mode = LDC_FV_GRID_UNIFORM;
+  if (grid && grid->mode != LDC_FV_GRID_UNIFORM) {
+    if (grid->mode != LDC_FV_GRID_TABLES || !grid->x_tables || !grid->y_tables) return LDC_E_ARG;
+    if (grid->x_len < LDC_FV_GRID_TABLE_LEN(h->a.d.nx) || grid->y_len < LDC_FV_GRID_TABLE_LEN(h->a.d.ny)) return LDC_E_ARG;
+    if (h->mixing) return LDC_E_ARG;                        // (the mixing has not met a stretched trial)
+    blk.ax = grid->x_tables;
+    blk.ay = grid->y_tables;
+    mode = LDC_FV_GRID_TABLES;
+  }
+  if (mode == LDC_FV_GRID_UNIFORM && h->grid_mode == LDC_FV_GRID_UNIFORM) return 0;   // (a plain handle stays as short as it is)
+  wide_graphs_free(h->gs);
+  h->grid = blk;
+  h->grid_mode = (signed char)mode;
   return 0;
 }
 
@@ -1021,6 +1108,7 @@ int ldc_fv_wide_batch_create(ldc_fv_wide* const* hs, int n, void* table, int64_t
     for (int r = 0; r < q; ++r)
       if (hs[r] == hs[q]) return LDC_E_ARG;
     if (hs[q]->a.d.maxit != hs[0]->a.d.maxit) return LDC_E_ARG;
+    if (hs[q]->grid_mode != LDC_FV_GRID_UNIFORM) return LDC_E_ARG;         // (the kernels of a batch assume equal spacing)
     if (hs[q]->a.pmax) {
       if (pmax && hs[q]->a.pmax != pmax) return LDC_E_ARG;
       pmax = hs[q]->a.pmax;
@@ -1227,6 +1315,7 @@ int ldc_fv_wide_post_enqueue(ldc_fv_wide* h, const struct ldc_fv_post* post, dou
                              void* stream) {
   if (!h) return LDC_E_STATE;
   if (!post) return LDC_E_ARG;
+  if (h->grid_mode != LDC_FV_GRID_UNIFORM) return LDC_E_ARG;                // (these kernels assume equal spacing)
   const struct ldc_fv_post& p = *post;
   const void* req[] = {p.Sx, p.lamx, p.Sy, p.lamy, p.psi, p.omega, p.result};
   for (const void* x : req) if (!x) return LDC_E_ARG;
@@ -1304,6 +1393,7 @@ extern "C" {
 int ldc_fv_wide_prolong_enqueue(ldc_fv_wide* coarse, ldc_fv_wide* fine, void* stream) {
   if (!coarse || !fine) return LDC_E_STATE;
   if (coarse == fine || !fv_same_domain(coarse->a.d, fine->a.d)) return LDC_E_ARG;
+  if (coarse->grid_mode != LDC_FV_GRID_UNIFORM || fine->grid_mode != LDC_FV_GRID_UNIFORM) return LDC_E_ARG;   // (equal spacing)
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
   if (coarse->device != dev || fine->device != dev) return LDC_E_STATE;

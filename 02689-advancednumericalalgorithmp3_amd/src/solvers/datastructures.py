@@ -147,7 +147,7 @@ class FVParameters(Parameters):
     vortex_refine: str = "none"
     # the mesh: "uniform" (the reference's) or "tanh" (wall-clustered in both axes: vertices x_k = Lx s(k / nx),
     # s(xi) = (1 + tanh(beta (2 xi - 1)) / tanh(beta)) / 2 with beta = grid_stretch >= 0, read only then; 0 gives uniform
-    # vertices through the stretched kernel).  mapping "cu" only, either pressure equation; no acceleration, device or chip
+    # vertices through the stretched kernel).  mapping "cu" (or "chip" with chip_grid "tables", below), either pressure equation; no acceleration, device or chip
     # vortex metrics by the reference's rule, or streamfunction "wall" (the equal-spacing kernel); sequencing (solver=fv/fsg)
     # and start_from with transfer "tables" only (below);
     # streamfunction "wall_stretched" (tanh only, with or without the refinement) is the wall rule on the stretched mesh, on
@@ -166,9 +166,16 @@ class FVParameters(Parameters):
     # third of the CG iterations; on a uniform grid nothing is gained).  Both solve the same equation to pressure_tol, so the
     # results differ at that level: it goes to MLflow
     pressure_preconditioner: str = "laplacian"
+    # what the phase kernels of a mapping "chip" trial read the geometry from: "uniform" (dx, dy) or "tables" (the per-axis
+    # tables of grid "tanh": ldc_fv_wide_set_grid; accepted only with grid "tanh" and mapping "chip", a lone trial of
+    # 8 ... 1024 cells per axis, pressure_equation "reference" or "consistent"; no acceleration, separable preconditioner,
+    # sequencing or start_from; vortex metrics on the host, or streamfunction "wall_stretched" at every size).  With the
+    # default a grid "tanh" trial takes mapping "cu" as before.  Like mapping it names where the same iteration runs (the
+    # two agree to rounding): it stays out of MLflow
+    chip_grid: str = "uniform"
 
     def to_mlflow(self) -> dict:
-        skip = {"device", "check_every", "vortex_metrics", "mapping", "linear_budget"}
+        skip = {"device", "check_every", "vortex_metrics", "mapping", "linear_budget", "chip_grid"}
         return {k: _mlflow_scalar(v) for k, v in self.as_dict().items() if k not in skip}
 
 

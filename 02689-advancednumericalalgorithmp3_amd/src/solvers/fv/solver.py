@@ -18,7 +18,9 @@ mapping and size (``ldc_fv_wall_post_enqueue``: the wall trials of a call share 
 geometry read from per-axis tables, either pressure equation); its vortex metrics are computed on the host by the
 reference's rule, or with ``streamfunction="wall_stretched"`` on the device by the wall rule on the stretched mesh
 (``ldc_fv_wall_stretched_post_enqueue``: the Dirichlet generalised eigenpairs of each axis, the quadratic fit with unequal
-spacing; such trials of a call share seven launches per 32 of them).
+spacing; such trials of a call share seven launches per 32 of them).  With ``mapping="chip"`` and ``chip_grid="tables"`` a
+lone such trial of 8 ... 1024 cells per axis runs on the whole chip (``ldc_fv_wide_set_grid``: the chip chain with stretched
+twins of the phases that read the geometry, ``pressure_equation`` ``"reference"`` or ``"consistent"``).
 ``transfer="tables"`` on the FINE trial of a pair lets ``prolong`` / ``start_from`` read both grids from per-axis tables
 (``ldc_fv_prolong_tables_enqueue``: one work-group per pair, 23 pairs per launch), so stretched trials are sequenced, continued
 in Re and started from uniform ones; the default ``"uniform"`` is the equal-spacing transfer of before.
@@ -48,6 +50,9 @@ STREAMFUNCTIONS = ("reference", "wall", "wall_stretched")
 WALL_RULES = ("wall", "wall_stretched")      # the wall rule on equal spacing, and on the tables of grid="tanh"
 VORTEX_REFINES = ("none", "quadratic")
 GRIDS = ("uniform", "tanh")
+# what the phase kernels of a mapping "chip" trial read the geometry from: "uniform" (dx, dy) or "tables" (the per-axis tables
+# of grid="tanh": ldc_fv_wide_set_grid, a lone chip trial of 8 ... 1024 cells per axis)
+CHIP_GRIDS = ("uniform", "tables")
 PRESSURE_PRECONDITIONERS = ("laplacian", "separable")
 # what prolong / start_from / the levels of solver=fv/fsg read the geometry from: "uniform" (dx, dy: the equal-spacing kernels)
 # or "tables" (per-axis tables of centres, widths and face weights: ldc_fv_prolong_tables_enqueue, either grid, mapping "cu")
@@ -111,7 +116,9 @@ def generalised_eig_host(h, d, rho=1.0):
     K[i, i + 1] -= w
     K[i + 1, i] -= w
     lam, Q = eigh(K, np.diag(h))
-    assert abs(lam[0]) < 1e-9 * lam[-1] and lam[1] > 1e-6 * lam[-1], "Neumann stiffness: one zero mode, first"
+    # (the first mode above zero stays near rho (pi / L)^2 whatever n is, while lam[-1] grows like 1 / h_min^2: on the grids of
+    # the chip mapping, up to 1024 cells, lam[1] / lam[-1] falls below 1e-6, so lam[1] is held against the former)
+    assert abs(lam[0]) < 1e-9 * lam[-1] and lam[1] > 0.5 * rho * (np.pi / h.sum()) ** 2, "Neumann stiffness: one zero mode, first"
     return lam, Q
 
 
@@ -864,10 +871,20 @@ class FVSolver(LidDrivenCavitySolver):
         if p.grid not in GRIDS:
             raise ValueError(f"grid={p.grid!r}: 'uniform' or 'tanh'")
         self.stretched = p.grid == "tanh"         # geometry tables on the handle: fv_stretched_kernel advances the trial
+        if p.chip_grid not in CHIP_GRIDS:
+            raise ValueError(f"chip_grid={p.chip_grid!r}: 'uniform' or 'tables'")
+        self.chip_tables = p.chip_grid == "tables"          # ... or, on the wide handle, the stretched twins of the chip chain
+        if self.chip_tables and not self.stretched:
+            raise ValueError(f"chip_grid='tables' with grid={p.grid!r}: the tables are those of a wall-clustered mesh, give the "
+                             f"trial grid='tanh' (or chip_grid='uniform')")
+        if self.chip_tables and p.mapping != "chip":
+            raise ValueError(f"chip_grid='tables' with mapping={p.mapping!r}: the stretched phase kernels advance a lone "
+                             f"mapping='chip' trial (a shared batch has no room for the tables in its table entry; a one-CU "
+                             f"trial reads them without the option)")
         if self.stretched:
             if not float(p.grid_stretch) >= 0.0 or not np.isfinite(float(p.grid_stretch)):
                 raise ValueError(f"grid_stretch={p.grid_stretch}: the tanh clustering parameter, a finite number >= 0")
-            if p.mapping != "cu":
+            if p.mapping != "cu" and not self.chip_tables:
                 raise ValueError(f"grid='tanh' with mapping={p.mapping!r}: stretched grids run on the one-CU kernel only "
                                  f"(mapping='cu')")
             if p.acceleration != "none":
@@ -1032,6 +1049,9 @@ class FVSolver(LidDrivenCavitySolver):
                     F.wide_set_pressure(h, "consistent", float(self.params.pressure_tol),
                                         int(self.params.pressure_max_iters), self.t["pstats"].data_ptr(),
                                         self.t["pstats"].numel())
+                if self.chip_tables:              # (the tables of grid_axis; Qx, lamx, Qy, lamy are its eigenpairs already)
+                    F.wide_set_grid(h, self.t["gridx"].data_ptr(), self.t["gridx"].numel(), self.t["gridy"].data_ptr(),
+                                    self.t["gridy"].numel())
                 if self.mixed_chip:               # (before the batch of one below: a batch copies the block)
                     F.wide_set_anderson(h, self._anderson_block(), self.t["mix_scratch"].data_ptr(),
                                         self.t["mix_scratch"].numel())

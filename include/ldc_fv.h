@@ -1,6 +1,6 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
  * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc and
- * csrc/ldc_fv_wide_pressure.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip, csrc/ldc_fv_wall_post.hip,
+ * csrc/ldc_fv_wide_pressure.inc and csrc/ldc_fv_wide_stretched.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip, csrc/ldc_fv_wall_post.hip,
  * csrc/ldc_fv_stretched.hip, csrc/ldc_fv_stretched_sep.hip, csrc/ldc_fv_wall_post_stretched.hip,
  * csrc/ldc_fv_prolong_tables.hip).
  *
@@ -245,6 +245,27 @@
  *    not change.  ldc_fv_enqueue / ldc_fv_batch_enqueue send consistent handles with both kinds of tables to
  *    fv_stretched_sep_kernel as one more launch group, in list order within it.  A handle in reference mode keeps the
  *    setting and does not read the block.
+ *
+ * Stretched grids of a chip trial (ldc_fv_wide_set_grid; csrc/ldc_fv_wide_stretched.inc, inside the wide unit).  A LONE
+ * ldc_fv_wide handle with geometry tables attached runs the iteration described under "Stretched grids of a one-CU trial" --
+ * the same tables [h | d | g], the same rules, either pressure equation, Qx, lamx, Qy, lamy the generalised eigenpairs, ulid at
+ * the stretched face centres, dx and dy not read -- as the launch-per-phase chain above, LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N
+ * cells per axis.
+ *  - the phases that read the geometry (assemble, faces, correct, fluxvort, sums; consistent mode: its faces, ap and
+ *    fluxvort) are twins that take the two table pointers by value beside the trial's arguments; their cell bodies are those
+ *    of the one-CU stretched kernels (csrc/ldc_fv_stretched_cells.inc: one definition for both mappings).  The BiCGSTAB
+ *    sweeps, linfinish, init, rz, xr, pfinish and the GEMMs are the uniform chain's kernels; the scaled GEMM and `record` are
+ *    launched with dx = dy = 1 in their copy of the arguments (the divisor is lamy[a] + lamx[b], and the sums of E, Z, P carry
+ *    each cell's volume already);
+ *  - the chain has the uniform chain's launches one for one, in the same grids: ldc_fv_wide_launches, the scratch, both
+ *    budgets and their overflow protocol, the statistics words and the graphs are unchanged, and the chip mapping's rules
+ *    hold (grids of (nx, ny) alone, slots added in one fixed order, `par` alternating, every kernel behind the gate, no
+ *    work-group reading what another of the same launch writes: ap recomputes p at the neighbours as before);
+ *  - the sums go through the slots in the chip mapping's order, not the one-CU kernel's: the two agree to rounding;
+ *  - not for such a handle, each LDC_E_ARG before any device call: Anderson mixing (ldc_fv_wide_set_anderson, in either
+ *    order), a batch (ldc_fv_wide_batch_create: the 256-byte table entry is full, and a stretched trial must never run the
+ *    uniform kernels unnoticed), ldc_fv_wide_post_enqueue and ldc_fv_wide_prolong_enqueue (equal spacing).  The wall rule of
+ *    such a trial is ldc_fv_wall_stretched_post_enqueue, which takes raw pointers and every size.
  *
  * Post-processing and prolongation of such a trial (ldc_fv_wide_post_enqueue, ldc_fv_wide_prolong_enqueue; the same
  * unit): what ldc_fv_post_enqueue and ldc_fv_prolong_enqueue do for a trial of up to LDC_FV_MAX_N cells per axis, by the
@@ -700,6 +721,16 @@ int ldc_fv_wide_set_anderson(ldc_fv_wide *h, const struct ldc_fv_anderson *acc, 
 /* needs no device: LDC_E_STATE for a null handle; LDC_E_ARG for another mode, max_iters < 1, tol outside (0, 1), a null or   */
 /* short scratch.                                                                                                             */
 int ldc_fv_wide_set_pressure(ldc_fv_wide *h, const struct ldc_fv_pressure *cfg, double *scratch, int64_t scratch_len);
+/* The grid of the handle: grid == NULL or mode LDC_FV_GRID_UNIFORM is the grid of a new handle (dx, dy); mode                */
+/* LDC_FV_GRID_TABLES attaches the per-axis tables of ldc_fv_set_grid (the same struct and layout), device buffers owned by   */
+/* the caller and left alone while the handle lives in that mode; the problem's Qx, lamx, Qy, lamy and ulid must then be      */
+/* those of that grid.  The two pointers travel by value in the kernel arguments: nothing is copied, and the handle's         */
+/* captured iterations are freed.  Call it between solves, with nothing of the handle in flight.  Validation comes first and  */
+/* needs no device: LDC_E_ARG for a null handle, another mode, a null table, a length below LDC_FV_GRID_TABLE_LEN, and for     */
+/* tables on a handle with Anderson mixing attached.  A refused call leaves the handle as it was.  The pressure mode is kept  */
+/* either way.  A handle with tables is refused (LDC_E_ARG) by ldc_fv_wide_set_anderson with depth > 0,                        */
+/* ldc_fv_wide_batch_create, ldc_fv_wide_post_enqueue and ldc_fv_wide_prolong_enqueue.                                         */
+int ldc_fv_wide_set_grid(ldc_fv_wide *h, const struct ldc_fv_grid *grid);
 /* The CG iterations the next enqueues carry per SIMPLE iteration (>= 1; min(budget, max_iters) x 7 launches).  LDC_E_ARG for */
 /* a handle in the reference mode.  Graphs are kept: they are keyed on both budgets.                                          */
 int ldc_fv_wide_set_pressure_budget(ldc_fv_wide *h, int budget);
