@@ -153,6 +153,13 @@ __device__ __forceinline__ double sg_row(const SgCtx& s, int c, int i, int j, do
   return sg_row(s, c, i, j, pc, [p](int k) { return p[k]; });
 }
 
+// the diagonal scaling of the separable preconditioner (Concus and Golub) at cell c: s_c = sqrt(a_i b_j / D_c), a and b the
+// fitted factors of the two axes (the heads of the tables of ldc_fv_set_preconditioner / ldc_fv_wide_set_preconditioner).
+// One definition for SepPolicy::start (ldc_fv_stretched_sep.hip) and wide_sep_init (ldc_fv_wide_separable.inc)
+__device__ __forceinline__ double sg_sep_scale(const SgCtx& s, const double* a, const double* b, int c, int i, int j) {
+  return sqrt((a[i] * b[j]) / s.D(c, i, j));
+}
+
 // ---- 5. twin of the cell body of fv_correct<false>: the gradient and D of this grid; u^2 + v^2 weighted by the cell's
 //         volume.  y0 = y[0]; part: the record sums 0 .. 6
 template <int K>

@@ -63,7 +63,7 @@ struct SepPolicy {
   __device__ __forceinline__ void start(int c, double b) const {
     const FvCtx& x = s.x;
     const int i = c % x.nx, j = c / x.nx;
-    const double sc = sqrt((t.ax[i] * t.ay[j]) / s.D(c, i, j));
+    const double sc = sg_sep_scale(s, t.ax, t.ay, c, i, j);
     x.vec(SEP_S)[c] = sc;
     x.vec(SEP_SR)[c] = sc * b;
   }

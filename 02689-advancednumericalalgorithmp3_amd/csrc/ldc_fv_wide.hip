@@ -22,6 +22,9 @@
 // A lone trial with geometry tables (ldc_fv_wide_set_grid; ldc_fv_wide_stretched.inc) runs either chain on a wall-clustered
 // tensor grid: launch for launch the same, with stretched twins of the phases that read the geometry (assemble, faces,
 // correct, fluxvort, sums, ap) around the cell bodies of ldc_fv_stretched_cells.inc, which the one-CU stretched units call too.
+// With the tables of the separable scaled preconditioner attached as well (ldc_fv_wide_set_preconditioner;
+// ldc_fv_wide_separable.inc) the consistent chain of such a trial takes twins of init, rz, ap and xr and hands the four GEMMs
+// the eigenpairs of the fitted operator: z = s . L_s+ (s . r), launch for launch the same chain.
 // Rules every kernel keeps:
 //  - the grid is a function of (nx, ny) alone;
 //  - a work-group writes its partial sums to its own slot; the NEXT launch lets every work-group add all slots in one
@@ -518,6 +521,9 @@ __device__ __forceinline__ void wide_record(const FvWideArgs& a, double* lds) {
 #include "ldc_fv_stretched_cells.inc"
 #include "ldc_fv_wide_stretched.inc"
 
+// ---- 11. such a trial with the separable scaled preconditioner: the twins of init, rz, ap and xr
+#include "ldc_fv_wide_separable.inc"
+
 // ---- the kernels: every phase for a lone trial (arguments by value, g = blockIdx.x) and for a batch (the table)
 #define WIDE_LDS __shared__ double lds[kWW * kWS]
 // the trial and the work-group of this block of a batch launch, from a block map / for one work-group per trial
@@ -695,7 +701,12 @@ struct ldc_fv_wide {
   FvWidePcg x;                               // ldc_fv_wide_set_pressure (a.pmax > 0: in use).  Behind gs: nothing in front
   int pbudget;                               // of it moves, and only a handle with a.pmax > 0 is read this far
   FvGridBlk grid;                            // ldc_fv_wide_set_grid.  At the end, for the same reason: only a handle with
-};                                           // grid_mode LDC_FV_GRID_TABLES is read this far
+                                             // grid_mode LDC_FV_GRID_TABLES is read this far
+  FvPrecondBlk prec;                         // ldc_fv_wide_set_preconditioner.  Behind `grid`, and only such a handle is read
+  int prec_mode;                             // this far: prec_mode != LDC_FV_PRECOND_LAPLACIAN implies grid_mode TABLES
+};
+static_assert(LDC_FV_PRECOND_LAPLACIAN == 0, "a handle made of zeroes has the laplacian preconditioner");
+static_assert(sizeof(ldc_fv_wide) <= 512, "a handle with tables ends within 512 bytes");
 static_assert(LDC_FV_GRID_UNIFORM == 0, "a handle made of zeroes has the uniform grid");
 static_assert(sizeof(FvWideArgs) + sizeof(int) + 2 * sizeof(signed char) + sizeof(short) == 216, "the head of a handle");
 
@@ -804,15 +815,31 @@ int wide_sg_iteration(const ldc_fv_wide* h, int nb, int np, hipStream_t st) {
   } else {
     const FvWidePcg& x = h->x;
     WIDE_LAUNCH((fv_wide_sg_faces<true>), G, kWT, a, gb, par); par ^= 1;
-    WIDE_LAUNCH(fv_wide_pcg_init, G, kWT, a, par); par ^= 1;
-    for (int it = 0; it < np; ++it) {
-      WIDE_LAUNCH((fv_wide_pcg_gemm<true, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 0), it, par); par ^= 1;
-      WIDE_LAUNCH((fv_wide_pcg_gemm<false, true>), gg, kWT, a1, x, wide_pcg_gemm_of(d, 1), it, par);
-      WIDE_LAUNCH((fv_wide_pcg_gemm<false, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 2), it, par);
-      WIDE_LAUNCH((fv_wide_pcg_gemm<false, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 3), it, par);
-      WIDE_LAUNCH(fv_wide_pcg_rz, G, kWT, a, par); par ^= 1;
-      WIDE_LAUNCH(fv_wide_sg_pcg_ap, G, kWT, a, gb, it, par); par ^= 1;
-      WIDE_LAUNCH(fv_wide_pcg_xr, G, kWT, a, it, par); par ^= 1;
+    if (h->prec_mode == LDC_FV_PRECOND_SEPARABLE) {       // (ldc_fv_wide_separable.inc: the same launches, z = s . L_s+ (s . r))
+      const FvPrecondBlk& pb = h->prec;
+      const FvWideArgs as = wide_sep_args(a, pb);
+      const FvDesc& ds = as.d;
+      WIDE_LAUNCH(fv_wide_sep_init, G, kWT, a, gb, pb, par); par ^= 1;
+      for (int it = 0; it < np; ++it) {
+        WIDE_LAUNCH((fv_wide_pcg_gemm<true, false>), gg, kWT, as, x, wide_sep_gemm_of(ds, 0), it, par); par ^= 1;
+        WIDE_LAUNCH((fv_wide_pcg_gemm<false, true>), gg, kWT, as, x, wide_sep_gemm_of(ds, 1), it, par);
+        WIDE_LAUNCH((fv_wide_pcg_gemm<false, false>), gg, kWT, as, x, wide_sep_gemm_of(ds, 2), it, par);
+        WIDE_LAUNCH((fv_wide_pcg_gemm<false, false>), gg, kWT, as, x, wide_sep_gemm_of(ds, 3), it, par);
+        WIDE_LAUNCH(fv_wide_sep_rz, G, kWT, a, par); par ^= 1;
+        WIDE_LAUNCH(fv_wide_sep_ap, G, kWT, a, gb, it, par); par ^= 1;
+        WIDE_LAUNCH(fv_wide_sep_xr, G, kWT, a, it, par); par ^= 1;
+      }
+    } else {
+      WIDE_LAUNCH(fv_wide_pcg_init, G, kWT, a, par); par ^= 1;
+      for (int it = 0; it < np; ++it) {
+        WIDE_LAUNCH((fv_wide_pcg_gemm<true, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 0), it, par); par ^= 1;
+        WIDE_LAUNCH((fv_wide_pcg_gemm<false, true>), gg, kWT, a1, x, wide_pcg_gemm_of(d, 1), it, par);
+        WIDE_LAUNCH((fv_wide_pcg_gemm<false, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 2), it, par);
+        WIDE_LAUNCH((fv_wide_pcg_gemm<false, false>), gg, kWT, a, x, wide_pcg_gemm_of(d, 3), it, par);
+        WIDE_LAUNCH(fv_wide_pcg_rz, G, kWT, a, par); par ^= 1;
+        WIDE_LAUNCH(fv_wide_sg_pcg_ap, G, kWT, a, gb, it, par); par ^= 1;
+        WIDE_LAUNCH(fv_wide_pcg_xr, G, kWT, a, it, par); par ^= 1;
+      }
     }
     WIDE_LAUNCH(fv_wide_pcg_finish, 1, kWT, a, x, np, par);
     WIDE_LAUNCH(fv_wide_sg_correct, G, kWT, a, gb);
@@ -984,6 +1011,8 @@ int ldc_fv_wide_create(const struct ldc_fv_problem* pr, double* scratch, int64_t
   s->m = FvWideMix{};
   s->grid = FvGridBlk{};
   s->grid_mode = LDC_FV_GRID_UNIFORM;
+  s->prec = FvPrecondBlk{};
+  s->prec_mode = LDC_FV_PRECOND_LAPLACIAN;
   *out = s;
   return 0;
 }
@@ -1059,6 +1088,27 @@ int ldc_fv_wide_set_grid(ldc_fv_wide* h, const struct ldc_fv_grid* grid) {
   wide_graphs_free(h->gs);
   h->grid = blk;
   h->grid_mode = (signed char)mode;
+  h->prec = FvPrecondBlk{};                                 // (the tables belong to the mesh they were fitted to)
+  h->prec_mode = LDC_FV_PRECOND_LAPLACIAN;
+  return 0;
+}
+
+int ldc_fv_wide_set_preconditioner(ldc_fv_wide* h, const struct ldc_fv_precond* cfg) {
+  if (!h) return LDC_E_ARG;
+  FvPrecondBlk blk = {};
+  int mode = LDC_FV_PRECOND_LAPLACIAN;
+  if (cfg && cfg->mode != LDC_FV_PRECOND_LAPLACIAN) {
+    if (cfg->mode != LDC_FV_PRECOND_SEPARABLE || h->grid_mode != LDC_FV_GRID_TABLES) return LDC_E_ARG;
+    if (!cfg->x_table || !cfg->y_table) return LDC_E_ARG;
+    if (cfg->x_len < LDC_FV_PRECOND_TABLE_LEN(h->a.d.nx) || cfg->y_len < LDC_FV_PRECOND_TABLE_LEN(h->a.d.ny)) return LDC_E_ARG;
+    blk.px = cfg->x_table;
+    blk.py = cfg->y_table;
+    mode = LDC_FV_PRECOND_SEPARABLE;
+  }
+  if (h->grid_mode != LDC_FV_GRID_TABLES) return 0;         // (laplacian already, and a plain handle stays as short as it is)
+  wide_graphs_free(h->gs);
+  h->prec = blk;
+  h->prec_mode = mode;
   return 0;
 }
 

@@ -168,11 +168,18 @@ class FVParameters(Parameters):
     pressure_preconditioner: str = "laplacian"
     # what the phase kernels of a mapping "chip" trial read the geometry from: "uniform" (dx, dy) or "tables" (the per-axis
     # tables of grid "tanh": ldc_fv_wide_set_grid; accepted only with grid "tanh" and mapping "chip", a lone trial of
-    # 8 ... 1024 cells per axis, pressure_equation "reference" or "consistent"; no acceleration, separable preconditioner,
-    # sequencing or start_from; vortex metrics on the host, or streamfunction "wall_stretched" at every size).  With the
+    # 8 ... 1024 cells per axis, pressure_equation "reference" or "consistent"; no acceleration, sequencing or start_from,
+    # and pressure_preconditioner stays "laplacian" (the separable preconditioner of such a trial is chip_preconditioner,
+    # below); vortex metrics on the host, or streamfunction "wall_stretched" at every size).  With the
     # default a grid "tanh" trial takes mapping "cu" as before.  Like mapping it names where the same iteration runs (the
     # two agree to rounding): it stays out of MLflow
     chip_grid: str = "uniform"
+    # what preconditions the CG of such a trial (mapping "chip", grid "tanh", chip_grid "tables") with pressure_equation
+    # "consistent": "laplacian" (the operator with D left out) or "separable" (the fit, the tables and the scaling of
+    # pressure_preconditioner "separable", on the chip chain: ldc_fv_wide_set_preconditioner; a fifth to a twentieth of the CG
+    # iterations per solve).  "separable" is accepted only with all of those and pressure_preconditioner "laplacian".  Both
+    # solve the same equation to pressure_tol, so the results differ at that level: it goes to MLflow
+    chip_preconditioner: str = "laplacian"
 
     def to_mlflow(self) -> dict:
         skip = {"device", "check_every", "vortex_metrics", "mapping", "linear_budget", "chip_grid"}

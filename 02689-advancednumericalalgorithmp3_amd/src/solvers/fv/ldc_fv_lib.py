@@ -138,6 +138,7 @@ EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue"
            "ldc_fv_wide_batch_launches", "ldc_fv_wide_post_enqueue", "ldc_fv_wide_post_launches",
            "ldc_fv_wide_prolong_enqueue", "ldc_fv_wide_set_anderson", "ldc_fv_wide_set_pressure",
            "ldc_fv_wide_set_pressure_budget", "ldc_fv_wide_batch_set_pressure_budget", "ldc_fv_wide_set_grid",
+           "ldc_fv_wide_set_preconditioner",
            "ldc_fv_sample_nodes",
            "ldc_fv_wall_post_enqueue", "ldc_fv_wall_post_launches", "ldc_fv_wall_stretched_post_enqueue",
            "ldc_fv_wall_stretched_post_launches", "ldc_fv_prolong_tables_enqueue", "ldc_fv_prolong_tables_launches")
@@ -235,6 +236,7 @@ def lib() -> C.CDLL:
         L.ldc_fv_wide_set_pressure.argtypes = [_dp, C.POINTER(Pressure), _dp, C.c_int64]
         L.ldc_fv_wide_set_pressure_budget.argtypes = [_dp, C.c_int]
         L.ldc_fv_wide_set_grid.argtypes = [_dp, C.POINTER(Grid)]
+        L.ldc_fv_wide_set_preconditioner.argtypes = [_dp, C.POINTER(Precond)]
         L.ldc_fv_wide_batch_set_pressure_budget.argtypes = [_dp, C.c_int]
         L.ldc_fv_sample_nodes.argtypes = [C.POINTER(SampleJob), C.c_int, _dp]
         L.ldc_fv_wall_post_enqueue.argtypes = [C.POINTER(WallJob), C.c_int, _dp]
@@ -372,6 +374,15 @@ def wide_set_grid(wide, x_tables_ptr: int, x_len: int, y_tables_ptr: int, y_len:
     cfg = Grid(mode=GRID_MODES["tanh"], pad=0, x_tables=x_tables_ptr, y_tables=y_tables_ptr, x_len=int(x_len),
                y_len=int(y_len))
     check(lib().ldc_fv_wide_set_grid(wide, C.byref(cfg)), "ldc_fv_wide_set_grid")
+
+
+def wide_set_preconditioner(wide, x_table_ptr: int, x_len: int, y_table_ptr: int, y_len: int) -> None:
+    """Attach the per-axis tables of ``set_preconditioner`` to an ``ldc_fv_wide`` handle with geometry tables (the separable
+    scaled preconditioner of a lone chip trial; include/ldc_fv.h).  The pointers travel in the kernel arguments: nothing is
+    copied; the handle's graphs are freed."""
+    cfg = Precond(mode=PRECOND_MODES["separable"], pad=0, x_table=x_table_ptr, y_table=y_table_ptr, x_len=int(x_len),
+                  y_len=int(y_len))
+    check(lib().ldc_fv_wide_set_preconditioner(wide, C.byref(cfg)), "ldc_fv_wide_set_preconditioner")
 
 
 def sample_nodes(jobs, stream) -> None:

@@ -20,7 +20,9 @@ reference's rule, or with ``streamfunction="wall_stretched"`` on the device by t
 (``ldc_fv_wall_stretched_post_enqueue``: the Dirichlet generalised eigenpairs of each axis, the quadratic fit with unequal
 spacing; such trials of a call share seven launches per 32 of them).  With ``mapping="chip"`` and ``chip_grid="tables"`` a
 lone such trial of 8 ... 1024 cells per axis runs on the whole chip (``ldc_fv_wide_set_grid``: the chip chain with stretched
-twins of the phases that read the geometry, ``pressure_equation`` ``"reference"`` or ``"consistent"``).
+twins of the phases that read the geometry, ``pressure_equation`` ``"reference"`` or ``"consistent"``; with
+``chip_preconditioner="separable"`` the CG of the consistent equation takes the separable scaled preconditioner of the one-CU
+kernel, ``ldc_fv_wide_set_preconditioner``).
 ``transfer="tables"`` on the FINE trial of a pair lets ``prolong`` / ``start_from`` read both grids from per-axis tables
 (``ldc_fv_prolong_tables_enqueue``: one work-group per pair, 23 pairs per launch), so stretched trials are sequenced, continued
 in Re and started from uniform ones; the default ``"uniform"`` is the equal-spacing transfer of before.
@@ -53,6 +55,9 @@ GRIDS = ("uniform", "tanh")
 # what the phase kernels of a mapping "chip" trial read the geometry from: "uniform" (dx, dy) or "tables" (the per-axis tables
 # of grid="tanh": ldc_fv_wide_set_grid, a lone chip trial of 8 ... 1024 cells per axis)
 CHIP_GRIDS = ("uniform", "tables")
+# what preconditions the CG of such a trial with pressure_equation "consistent": "laplacian" (the operator with D left out) or
+# "separable" (the tables of pressure_preconditioner "separable" on the chip chain: ldc_fv_wide_set_preconditioner)
+CHIP_PRECONDITIONERS = ("laplacian", "separable")
 PRESSURE_PRECONDITIONERS = ("laplacian", "separable")
 # what prolong / start_from / the levels of solver=fv/fsg read the geometry from: "uniform" (dx, dy: the equal-spacing kernels)
 # or "tables" (per-axis tables of centres, widths and face weights: ldc_fv_prolong_tables_enqueue, either grid, mapping "cu")
@@ -215,7 +220,8 @@ def separable_axis_host(h, d, g, a, rho=1.0):
     K[i, i + 1] -= w
     K[i + 1, i] -= w
     lam, Q = eigh(K, np.diag(h * a))
-    assert abs(lam[0]) < 1e-9 * lam[-1] and lam[1] > 1e-6 * lam[-1], "Neumann stiffness: one zero mode, first"
+    # (lam[1] / lam[-1] falls below 1e-6 from about 600 cells per axis on, and at 256 with beta = 2.5; lam[1] itself stays put)
+    assert abs(lam[0]) < 1e-9 * lam[-1] and lam[1] > 0.5 * rho * (np.pi / h.sum()) ** 2, "Neumann stiffness: one zero mode, first"
     return lam, Q
 
 
@@ -914,7 +920,15 @@ class FVSolver(LidDrivenCavitySolver):
             raise ValueError(f"pressure_preconditioner='separable' with grid={p.grid!r}, pressure_equation="
                              f"{p.pressure_equation!r}: it preconditions the CG of a stretched one-CU trial, give the trial "
                              f"grid='tanh' and pressure_equation='consistent_cu'")
-        self.shared = p.mapping == "shared"       # the phase kernels of csrc/ldc_fv_wide.hip: a launch of its own per
+        if p.chip_preconditioner not in CHIP_PRECONDITIONERS:
+            raise ValueError(f"chip_preconditioner={p.chip_preconditioner!r}: 'laplacian' or 'separable'")
+        self.chip_separable = p.chip_preconditioner == "separable"    # tables on the wide handle: the twins of the CG launches
+        if self.chip_separable and not (self.chip_tables and self.consistent):
+            raise ValueError(f"chip_preconditioner='separable' with mapping={p.mapping!r}, grid={p.grid!r}, chip_grid="
+                             f"{p.chip_grid!r}, pressure_equation={p.pressure_equation!r}: it preconditions the CG of a lone "
+                             f"stretched chip trial, give the trial mapping='chip', grid='tanh', chip_grid='tables' and "
+                             f"pressure_equation='consistent' (a one-CU trial takes pressure_preconditioner='separable')")
+        self.shared =p.mapping == "shared"       # the phase kernels of csrc/ldc_fv_wide.hip: a launch of its own per
         self.chip = p.mapping == "chip" or self.shared        # phase ("chip") or one for all trials of a batch ("shared")
         nx, ny = int(p.nx), int(p.ny)
         max_n = F.WIDE_MAX_N if self.chip else F.MAX_N
@@ -967,7 +981,7 @@ class FVSolver(LidDrivenCavitySolver):
             gridy, lamy, Qy = grid_axis(ny, p.Ly, float(p.grid_stretch), self.device, self.rho)
             ulid = lid_profile_at(xc, p.Lx, p.lid_velocity, p.corner_treatment, p.corner_smoothing)
             ops = dict(Qx=Qx, lamx=lamx, Qy=Qy, lamy=lamy, gridx=gridx, gridy=gridy)
-            if self.separable:                   # shared per (nx, ny, Lx, Ly, beta, rho, device): the fit couples the axes
+            if self.separable or self.chip_separable:     # shared per (nx, ny, Lx, Ly, beta, rho, device): the fit couples the axes
                 ops["precx"], ops["precy"] = separable_tables(nx, ny, p.Lx, p.Ly, float(p.grid_stretch), self.device,
                                                               self.rho)
         else:
@@ -1052,7 +1066,10 @@ class FVSolver(LidDrivenCavitySolver):
                 if self.chip_tables:              # (the tables of grid_axis; Qx, lamx, Qy, lamy are its eigenpairs already)
                     F.wide_set_grid(h, self.t["gridx"].data_ptr(), self.t["gridx"].numel(), self.t["gridy"].data_ptr(),
                                     self.t["gridy"].numel())
-                if self.mixed_chip:               # (before the batch of one below: a batch copies the block)
+                if self.chip_separable:           # (after the grid: the call refuses a handle without geometry tables)
+                    F.wide_set_preconditioner(h, self.t["precx"].data_ptr(), self.t["precx"].numel(),
+                                              self.t["precy"].data_ptr(), self.t["precy"].numel())
+                if self.mixed_chip:              # (before the batch of one below: a batch copies the block)
                     F.wide_set_anderson(h, self._anderson_block(), self.t["mix_scratch"].data_ptr(),
                                         self.t["mix_scratch"].numel())
                 if self.shared:

@@ -1,6 +1,6 @@
 /* ldc_fv.h -- C ABI of the finite-volume SIMPLE solver in libldc_hip.so (csrc/ldc_fv_kernel.inc, csrc/ldc_fv_post.hip,
  * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc and
- * csrc/ldc_fv_wide_pressure.inc and csrc/ldc_fv_wide_stretched.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip, csrc/ldc_fv_wall_post.hip,
+ * csrc/ldc_fv_wide_pressure.inc and csrc/ldc_fv_wide_stretched.inc and csrc/ldc_fv_wide_separable.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip, csrc/ldc_fv_wall_post.hip,
  * csrc/ldc_fv_stretched.hip, csrc/ldc_fv_stretched_sep.hip, csrc/ldc_fv_wall_post_stretched.hip,
  * csrc/ldc_fv_prolong_tables.hip).
  *
@@ -266,6 +266,25 @@
  *    order), a batch (ldc_fv_wide_batch_create: the 256-byte table entry is full, and a stretched trial must never run the
  *    uniform kernels unnoticed), ldc_fv_wide_post_enqueue and ldc_fv_wide_prolong_enqueue (equal spacing).  The wall rule of
  *    such a trial is ldc_fv_wall_stretched_post_enqueue, which takes raw pointers and every size.
+ *
+ * The separable scaled preconditioner of a chip trial (ldc_fv_wide_set_preconditioner; csrc/ldc_fv_wide_separable.inc, inside
+ * the wide unit).  A lone ldc_fv_wide handle with geometry tables takes the tables of "The separable scaled preconditioner"
+ * above -- the same struct, per axis [a | lam | Q] of LDC_FV_PRECOND_TABLE_LEN(n) doubles, LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N
+ * cells per axis -- and its consistent chain then preconditions the CG by z = s . L_s+ (s . r), s_c = sqrt(a[i] b[j] / D_c):
+ * the same operator, b, start x = 0, stop rule on |r|, cap, budget protocol, statistics words, p' and face correction, so
+ * the result differs from the laplacian run's at the level of the pressure tolerance.
+ *  - the chain is launch for launch the stretched consistent one, in the same grids, with the same `par`, slots and scratch:
+ *      faces | init* | np x (gemm x 4* | rz* | ap* | xr*) | pfinish.
+ *    init* also writes s and s . b, xr* also s . r (work vectors 18 and 19, dead after linfinish; vector 15 of the one-CU
+ *    kernel is the second copy of p here); the GEMMs are the chain's own kernels on a copy of the arguments whose descriptor
+ *    carries Qx, lamx, Qy, lamy of these tables and dx = dy = 1, the first one reading s . r; rz* sums (s . r) . z'; ap* is
+ *    the stretched ap with s . z' for z at the cell and at its four neighbours.  The scaling factor has one definition for
+ *    both mappings (csrc/ldc_fv_stretched_cells.inc).  ldc_fv_wide_launches is unchanged;
+ *  - the block (two pointers and the mode) stands at the end of the handle, behind the grid block, and travels by value in
+ *    the kernel arguments: nothing is copied.  The mode is kept in either pressure mode and read only in consistent mode; a
+ *    handle without the block enqueues exactly the launches of before;
+ *  - ldc_fv_wide_set_grid resets it to LDC_FV_PRECOND_LAPLACIAN whenever it attaches or detaches geometry tables: the tables
+ *    belong to the mesh they were fitted to.
  *
  * Post-processing and prolongation of such a trial (ldc_fv_wide_post_enqueue, ldc_fv_wide_prolong_enqueue; the same
  * unit): what ldc_fv_post_enqueue and ldc_fv_prolong_enqueue do for a trial of up to LDC_FV_MAX_N cells per axis, by the
@@ -731,6 +750,16 @@ int ldc_fv_wide_set_pressure(ldc_fv_wide *h, const struct ldc_fv_pressure *cfg, 
 /* either way.  A handle with tables is refused (LDC_E_ARG) by ldc_fv_wide_set_anderson with depth > 0,                        */
 /* ldc_fv_wide_batch_create, ldc_fv_wide_post_enqueue and ldc_fv_wide_prolong_enqueue.                                         */
 int ldc_fv_wide_set_grid(ldc_fv_wide *h, const struct ldc_fv_grid *grid);
+/* The preconditioner of the consistent pressure equation on a handle with geometry tables: cfg == NULL or mode               */
+/* LDC_FV_PRECOND_LAPLACIAN is that of a new handle; mode LDC_FV_PRECOND_SEPARABLE attaches the per-axis tables of              */
+/* ldc_fv_set_preconditioner (the same struct and layout), device buffers owned by the caller and left alone while the handle */
+/* lives in that mode.  The two pointers travel by value in the kernel arguments: nothing is copied, and the handle's          */
+/* captured iterations are freed.  Call it after ldc_fv_wide_set_grid, between solves, with nothing of the handle in flight;   */
+/* ldc_fv_wide_set_grid resets the mode to LDC_FV_PRECOND_LAPLACIAN whenever it attaches or detaches tables.  Validation comes */
+/* first and needs no device: LDC_E_ARG for a null handle, another mode, a handle without geometry tables, a null table or a   */
+/* length below LDC_FV_PRECOND_TABLE_LEN.  A refused call leaves the handle as it was.  Either pressure mode takes the call;   */
+/* the chain reads the tables in consistent mode only.                                                                         */
+int ldc_fv_wide_set_preconditioner(ldc_fv_wide *h, const struct ldc_fv_precond *cfg);
 /* The CG iterations the next enqueues carry per SIMPLE iteration (>= 1; min(budget, max_iters) x 7 launches).  LDC_E_ARG for */
 /* a handle in the reference mode.  Graphs are kept: they are keyed on both budgets.                                          */
 int ldc_fv_wide_set_pressure_budget(ldc_fv_wide *h, int budget);
