@@ -18,8 +18,9 @@
 //   1. cells    after the barrier: u, v, p at every fine cell; every thread forms the interpolated p at fine cell 0 for
 //               itself, so the fine p[0] is exactly 0.0 and nothing is broadcast
 //   2. faces    after the barrier: the two loops over the faces of mdot
-// No reduction, no scratch in global memory.  The arithmetic is stated once, here, behind a pragma that keeps its
-// multiply-adds apart, so that tests/fv_prolong_tables_numpy.py states it with the same roundings.
+// No reduction, no scratch in global memory.  The arithmetic is stated once, in ldc_fv_prolong_tables_cells.inc (shared with
+// the chip mapping's csrc/ldc_fv_wide_prolong_tables.hip), included behind a pragma that keeps its multiply-adds apart, so
+// that tests/fv_prolong_tables_numpy.py states it with the same roundings.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -39,50 +40,7 @@ static_assert(2 * LDC_FV_MAX_N <= kFvThreads, "locate: one thread per fine centr
 
 #pragma STDC FP_CONTRACT OFF      // (from here on no multiply-add is contracted: the transfer rounds as its NumPy statement)
 
-// one axis of the extended coarse grid: nodes e_0 = 0, e_k = xc[k - 1] (k = 1 .. n), e_{n+1} = L
-struct FvPtAxis {
-  int n;
-  const double* xc;
-  double L;
-  __device__ __forceinline__ double node(int k) const { return k == 0 ? 0.0 : (k == n + 1 ? L : xc[k - 1]); }
-  // the left node of x (the largest k <= n with e_k <= x; 0 when there is none) and the weight inside its interval
-  __device__ __forceinline__ void locate(double x, int& k, double& t) const {
-    int lo = 0, hi = n + 1;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (node(mid) <= x) lo = mid; else hi = mid;
-    }
-    k = lo;
-    const double e0 = node(lo), e1 = node(lo + 1);
-    t = (x - e0) / (e1 - e0);
-  }
-};
-
-enum FvPtRing { PT_RING_U, PT_RING_V, PT_RING_P };
-
-// the extended coarse field at node (kx, ky), kx = 0 .. nx + 1, ky = 0 .. ny + 1: walls and corners 0, the lid the coarse
-// lid profile, p repeats the nearest cell; no index leaves the coarse arrays
-template <FvPtRing R>
-__device__ __forceinline__ double pt_node(const double* f, const double* ulid, int nx, int ny, int kx, int ky) {
-  if (R == PT_RING_P) {
-    const int i = kx < 1 ? 0 : (kx > nx ? nx - 1 : kx - 1), j = ky < 1 ? 0 : (ky > ny ? ny - 1 : ky - 1);
-    return f[j * nx + i];
-  }
-  const bool inx = kx >= 1 && kx <= nx, iny = ky >= 1 && ky <= ny;
-  if (inx && iny) return f[(ky - 1) * nx + (kx - 1)];
-  if (R == PT_RING_U && inx && ky == ny + 1) return ulid[kx - 1];
-  return 0.0;
-}
-
-template <FvPtRing R>
-__device__ __forceinline__ double pt_at(const double* f, const double* ulid, int nx, int ny, int kx, double tx, int ky,
-                                        double ty) {
-  const double a = pt_node<R>(f, ulid, nx, ny, kx, ky), b = pt_node<R>(f, ulid, nx, ny, kx + 1, ky);
-  const double lo = a + tx * (b - a);
-  const double a1 = pt_node<R>(f, ulid, nx, ny, kx, ky + 1), b1 = pt_node<R>(f, ulid, nx, ny, kx + 1, ky + 1);
-  const double hi = a1 + tx * (b1 - a1);
-  return lo + ty * (hi - lo);
-}
+#include "ldc_fv_prolong_tables_cells.inc"      // the arithmetic and the checks of a call: one definition for both mappings
 
 __global__ __launch_bounds__(kFvThreads) void fv_prolong_tables_kernel(const FvPtLaunch L) {
   __shared__ int lk[2 * LDC_FV_MAX_N];          // [0, nx): the x axis; [nx, nx + ny): the y axis
@@ -124,21 +82,9 @@ __global__ __launch_bounds__(kFvThreads) void fv_prolong_tables_kernel(const FvP
   const double *gx = J.fine_x_grid + 2 * nx + 1, *gy = J.fine_y_grid + 2 * ny + 1;
   const double rho = J.rho;
   double *fx = J.fine_mdot, *fy = J.fine_mdot + nfx;
-  for (int q = tid; q < nfx; q += kFvThreads) {
-    const int i = q % (nx + 1), j = q / (nx + 1);
-    double m = 0.0;
-    if (i > 0 && i < nx) m = rho * ((gx[i] * fu[j * nx + i] + (1.0 - gx[i]) * fu[j * nx + i - 1]) * hy[j]);
-    fx[q] = m;
-  }
-  for (int q = tid; q < nfy; q += kFvThreads) {
-    const int i = q % nx, j = q / nx;
-    double m = 0.0;
-    if (j > 0 && j < ny) m = rho * ((gy[j] * fv[j * nx + i] + (1.0 - gy[j]) * fv[(j - 1) * nx + i]) * hx[i]);
-    fy[q] = m;
-  }
+  for (int q = tid; q < nfx; q += kFvThreads) fx[q] = pt_xface(fu, gx, hy, rho, nx, q);
+  for (int q = tid; q < nfy; q += kFvThreads) fy[q] = pt_yface(fv, gy, hx, rho, nx, ny, q);
 }
-
-inline bool pt_size_ok(int n) { return n >= LDC_FV_MIN_N && n <= LDC_FV_MAX_N; }
 
 }  // namespace
 
@@ -151,28 +97,7 @@ int ldc_fv_prolong_tables_launches(int n) {
 
 int ldc_fv_prolong_tables_enqueue(const struct ldc_fv_prolong_tables_job* jobs, int n, void* stream) {
   if (!jobs || n < 1) return LDC_E_ARG;
-  for (int q = 0; q < n; ++q) {
-    const ldc_fv_prolong_tables_job& j = jobs[q];
-    const void* req[] = {j.coarse_u, j.coarse_v, j.coarse_p, j.coarse_ulid, j.coarse_xc, j.coarse_yc, j.fine_u, j.fine_v,
-                         j.fine_p, j.fine_mdot, j.fine_x_grid, j.fine_y_grid, j.fine_xc, j.fine_yc};
-    for (const void* x : req) if (!x) return LDC_E_ARG;
-    if (!pt_size_ok(j.coarse_nx) || !pt_size_ok(j.coarse_ny) || !pt_size_ok(j.fine_nx) || !pt_size_ok(j.fine_ny)) return LDC_E_ARG;
-    if (!(j.Lx > 0) || !(j.Ly > 0) || !(j.rho > 0)) return LDC_E_ARG;
-  }
-  // what a launch writes nobody else in it may read or write: its work-groups run in any order
-  for (int q = 0; q < n; ++q) {
-    const void* written[] = {jobs[q].fine_u, jobs[q].fine_v, jobs[q].fine_p, jobs[q].fine_mdot};
-    for (int a = 0; a < 4; ++a) {
-      for (int b = a + 1; b < 4; ++b) if (written[a] == written[b]) return LDC_E_ARG;
-      for (int r = 0; r < n; ++r) {
-        const void* read[] = {jobs[r].coarse_u, jobs[r].coarse_v, jobs[r].coarse_p};
-        for (const void* x : read) if (written[a] == x) return LDC_E_ARG;
-        if (r == q) continue;
-        const void* theirs[] = {jobs[r].fine_u, jobs[r].fine_v, jobs[r].fine_p, jobs[r].fine_mdot};
-        for (const void* x : theirs) if (written[a] == x) return LDC_E_ARG;
-      }
-    }
-  }
+  if (!pt_jobs_ok(jobs, n, LDC_FV_MAX_N)) return LDC_E_ARG;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess) return LDC_E_NODEVICE;
   for (int lo = 0; lo < n; lo += LDC_FV_PROLONG_TABLES_LAUNCH_MAX) {

@@ -168,7 +168,8 @@ class FVParameters(Parameters):
     pressure_preconditioner: str = "laplacian"
     # what the phase kernels of a mapping "chip" trial read the geometry from: "uniform" (dx, dy) or "tables" (the per-axis
     # tables of grid "tanh": ldc_fv_wide_set_grid; accepted only with grid "tanh" and mapping "chip", a lone trial of
-    # 8 ... 1024 cells per axis, pressure_equation "reference" or "consistent"; no acceleration, sequencing or start_from,
+    # 8 ... 1024 cells per axis, pressure_equation "reference" or "consistent"; no acceleration; sequencing and start_from
+    # with chip_transfer "tables" only (below),
     # and pressure_preconditioner stays "laplacian" (the separable preconditioner of such a trial is chip_preconditioner,
     # below); vortex metrics on the host, or streamfunction "wall_stretched" at every size).  With the
     # default a grid "tanh" trial takes mapping "cu" as before.  Like mapping it names where the same iteration runs (the
@@ -180,6 +181,14 @@ class FVParameters(Parameters):
     # iterations per solve).  "separable" is accepted only with all of those and pressure_preconditioner "laplacian".  Both
     # solve the same equation to pressure_tol, so the results differ at that level: it goes to MLflow
     chip_preconditioner: str = "laplacian"
+    # what prolong, start_from and the levels of solver=fv/fsg read the geometry from when THIS trial, a lone mapping "chip"
+    # trial, is the fine one of a pair: "uniform" (the routes of `transfer` above: equal spacing, and a grid "tanh" chip trial
+    # starts from rest only) or "tables" (per-axis tables on both sides through ldc_fv_wide_prolong_tables_enqueue, two
+    # launches over the whole chip per pair, 8 ... 1024 cells per axis on either side; accepted only with mapping "chip", on
+    # grid "uniform" or on grid "tanh" with chip_grid "tables", and with transfer "uniform"; the coarse trial of a pair may be
+    # of any mapping and grid).  With it solver=fv/fsg sequences a stretched chip trial up to 1024 cells.  Like transfer it
+    # changes the start of a solve (on a uniform pair to rounding): it goes to MLflow
+    chip_transfer: str = "uniform"
 
     def to_mlflow(self) -> dict:
         skip = {"device", "check_every", "vortex_metrics", "mapping", "linear_budget", "chip_grid"}

@@ -24,7 +24,8 @@ than the chunk carried is enqueued again on its own with twice the budget (``sol
 
 ``BatchedFVFSGSolver`` is the same for coarse-to-fine sequences (solvers.fv.fsg): stage by stage, every stage a batch of
 ordinary trials, one ``prolong`` call between stages, which splits its pairs by route: ``grid="tanh"`` trials with
-``transfer="tables"`` ride beside uniform ones.
+``transfer="tables"`` ride beside uniform ones.  A trial with ``chip_transfer="tables"`` is a lone chip trial: both batch
+classes refuse it by name.
 """
 from __future__ import annotations
 
@@ -88,6 +89,9 @@ class BatchedFVSolver:
         if not trials:
             raise ValueError(f"{type(self).__name__} needs at least one trial")
         for t in trials:
+            if t.get("chip_transfer", "uniform") != "uniform":
+                raise ValueError(f"chip_transfer={t['chip_transfer']!r} inside a batch: the transfer over the whole chip "
+                                 f"starts a lone mapping='chip' trial, run it on its own")
             if t.get("mapping", "cu") == "chip":
                 raise ValueError("mapping='chip' inside a batch: a chip trial takes every CU, run it on its own")
         maps = {t.get("mapping", "cu") for t in trials}

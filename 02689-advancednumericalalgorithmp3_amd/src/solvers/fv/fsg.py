@@ -8,6 +8,10 @@ never leaves the device).  ``start_from`` is the same transfer from ANY other FV
 and parameters: continuation in Re is ``start_from`` at equal size.  With ``grid="tanh"`` the trial needs
 ``transfer="tables"``: every level is then a stretched ``FVSolver`` of the same stretch, pressure equation and preconditioner
 at its own size, and the transfer between them reads both grids from tables (``ldc_fv_prolong_tables_enqueue``).
+With ``mapping="chip"`` and ``chip_transfer="tables"`` every level is a chip trial with the fine trial's parameters (on
+``grid="tanh"`` with ``chip_grid="tables"``: its stretch, pressure equation and ``chip_preconditioner``) and the transfer is
+``ldc_fv_wide_prolong_tables_enqueue``, two launches over the whole chip per level: no level needs a one-CU handle, so a
+sequence may end at 1024 cells per axis, on either grid.
 
 Sequencing is a capability, not a promised saving: the reference's stop rule (relative change per iteration) is bound
 by the asymptotic rate, so the fine level may take as many iterations from the prolonged state as from rest (DESIGN.md
@@ -67,7 +71,7 @@ class FVFSGSolver(FVSolver):
     fine.  ``metrics.wall_time_seconds`` is the time of the whole sequence."""
 
     Parameters = FVFSGParameters
-    _needs_cu_handle = "an FSG level"         # every level is prolonged through its one-CU handle
+    _needs_cu_handle = "an FSG level"         # every level is prolonged through its one-CU handle (not with chip_transfer="tables")
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)

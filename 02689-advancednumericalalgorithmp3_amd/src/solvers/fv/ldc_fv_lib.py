@@ -46,6 +46,7 @@ WALL_NOT_ASKED, WALL_REFINED, WALL_NO_CANDIDATE, WALL_INDEFINITE, WALL_REJECTED 
 WALL_POST_LAUNCHES = 7         # omega | gemm x 4 | extrema | result, per group of WALL_LAUNCH_MAX jobs
 WALL_STRETCHED_LAUNCH_MAX = 32     # LDC_FV_WALL_STRETCHED_LAUNCH_MAX: jobs per launch of ldc_fv_wall_stretched_post_enqueue
 PROLONG_TABLES_LAUNCH_MAX = 23     # LDC_FV_PROLONG_TABLES_LAUNCH_MAX: jobs per launch of ldc_fv_prolong_tables_enqueue
+WIDE_PROLONG_TABLES_LAUNCHES = 2   # LDC_FV_WIDE_PROLONG_TABLES_LAUNCHES: cells | faces, per job of ldc_fv_wide_prolong_tables_enqueue
 DBG = ("grad_p", "diag", "b", "u_star", "v_star", "mdot_star", "rhs_p", "p_prime", "u_prime", "v_prime", "mdot")
 
 _dp = C.c_void_p
@@ -141,7 +142,8 @@ EXPORTS = ("ldc_fv_version", "ldc_fv_create", "ldc_fv_destroy", "ldc_fv_enqueue"
            "ldc_fv_wide_set_preconditioner",
            "ldc_fv_sample_nodes",
            "ldc_fv_wall_post_enqueue", "ldc_fv_wall_post_launches", "ldc_fv_wall_stretched_post_enqueue",
-           "ldc_fv_wall_stretched_post_launches", "ldc_fv_prolong_tables_enqueue", "ldc_fv_prolong_tables_launches")
+           "ldc_fv_wall_stretched_post_launches", "ldc_fv_prolong_tables_enqueue", "ldc_fv_prolong_tables_launches",
+           "ldc_fv_wide_prolong_tables_enqueue", "ldc_fv_wide_prolong_tables_launches")
 
 _bound = None
 
@@ -245,6 +247,8 @@ def lib() -> C.CDLL:
         L.ldc_fv_wall_stretched_post_launches.argtypes = [C.c_int]
         L.ldc_fv_prolong_tables_enqueue.argtypes = [C.POINTER(ProlongTablesJob), C.c_int, _dp]
         L.ldc_fv_prolong_tables_launches.argtypes = [C.c_int]
+        L.ldc_fv_wide_prolong_tables_enqueue.argtypes = [C.POINTER(ProlongTablesJob), C.c_int, _dp]
+        L.ldc_fv_wide_prolong_tables_launches.argtypes = [C.c_int]
         for name in EXPORTS:
             getattr(L, name).restype = C.c_int
         _bound = L
@@ -417,3 +421,11 @@ def prolong_tables_enqueue(jobs, stream) -> None:
     launches PROLONG_TABLES_LAUNCH_MAX at a time, one work-group each; nothing synchronises."""
     arr = (ProlongTablesJob * len(jobs))(*jobs)
     check(lib().ldc_fv_prolong_tables_enqueue(arr, len(jobs), _dp(stream)), "ldc_fv_prolong_tables_enqueue")
+
+
+def wide_prolong_tables_enqueue(jobs, stream) -> None:
+    """The same for jobs of 8 ... 1024 cells per axis on either side, by the chip mapping's rules (include/ldc_fv.h): ONE call
+    for all jobs, which the library checks first and launches one after another, two launches over the whole chip each;
+    nothing synchronises."""
+    arr = (ProlongTablesJob * len(jobs))(*jobs)
+    check(lib().ldc_fv_wide_prolong_tables_enqueue(arr, len(jobs), _dp(stream)), "ldc_fv_wide_prolong_tables_enqueue")

@@ -26,6 +26,9 @@ kernel, ``ldc_fv_wide_set_preconditioner``).
 ``transfer="tables"`` on the FINE trial of a pair lets ``prolong`` / ``start_from`` read both grids from per-axis tables
 (``ldc_fv_prolong_tables_enqueue``: one work-group per pair, 23 pairs per launch), so stretched trials are sequenced, continued
 in Re and started from uniform ones; the default ``"uniform"`` is the equal-spacing transfer of before.
+``chip_transfer="tables"`` is the same for a lone ``mapping="chip"`` trial on either grid
+(``ldc_fv_wide_prolong_tables_enqueue``: the same arithmetic, two launches over the whole chip per pair, 8 ... 1024 cells per
+axis on both sides, a source of any mapping and grid), so a stretched chip trial is sequenced up to 1024 cells.
 """
 from __future__ import annotations
 
@@ -62,6 +65,9 @@ PRESSURE_PRECONDITIONERS = ("laplacian", "separable")
 # what prolong / start_from / the levels of solver=fv/fsg read the geometry from: "uniform" (dx, dy: the equal-spacing kernels)
 # or "tables" (per-axis tables of centres, widths and face weights: ldc_fv_prolong_tables_enqueue, either grid, mapping "cu")
 TRANSFERS = ("uniform", "tables")
+# the same choice for a lone mapping "chip" trial as the fine one of a pair: "uniform" (the routes of `transfer`) or "tables"
+# (ldc_fv_wide_prolong_tables_enqueue: both grids from per-axis tables, two launches over the chip, 8 ... 1024 cells per axis)
+CHIP_TRANSFERS = ("uniform", "tables")
 LINEAR_MAX_ITERATIONS = 1000        # scipy_solver.py:15
 
 
@@ -475,7 +481,11 @@ def prolong(pairs):
     A pair whose FINE trial has ``transfer="tables"`` goes through ``ldc_fv_prolong_tables_enqueue``: the same transfer with
     the geometry of both trials read from per-axis tables, so either may be a ``grid="tanh"`` trial (the coarse one with any
     ``transfer``); all such pairs of a call are one call of the library, 23 per launch, one work-group each.  A pair with a
-    stretched trial whose fine trial lacks the option is refused."""
+    stretched trial whose fine trial lacks the option is refused.
+
+    A pair whose FINE trial has ``chip_transfer="tables"`` (a lone ``mapping="chip"`` trial on either grid) goes through
+    ``ldc_fv_wide_prolong_tables_enqueue``: the same arithmetic, two launches over the whole chip per pair, 8 ... 1024 cells per
+    axis on both sides; the coarse trial may be of any mapping and grid.  All routes may stand in one call."""
     import torch
     from solvers.spectral import ldc_lib
     pairs = list(pairs)
@@ -483,34 +493,38 @@ def prolong(pairs):
         return
     # (getattr: a trial built before the option, or a stand-in that has only `stretched`, is a transfer="uniform" trial)
     by_tables = [bool(getattr(f, "transfer_tables", False)) for _, f in pairs]
-    for (c, f), tables in zip(pairs, by_tables):
-        if (c.stretched or f.stretched) and not tables:
+    by_chip_tables = [bool(getattr(f, "chip_transfer_tables", False)) for _, f in pairs]
+    for (c, f), tables, chip_tables in zip(pairs, by_tables, by_chip_tables):
+        if (c.stretched or f.stretched) and not (tables or chip_tables):
             raise ValueError("prolong / start_from with grid='tanh': the prolongation kernel assumes equal spacing on both "
                              "trials; give the FINE trial transfer='tables' (the transfer that reads both grids from tables)")
     dev = pairs[0][1].device
     index = torch.cuda.current_device() if dev.index is None else dev.index
-    routes = [prolong_route(c._has_cu_handle, f._has_cu_handle, c.chip, f.chip, tables)
-              for (c, f), tables in zip(pairs, by_tables)]
+    # (a fine trial with chip_transfer="tables" takes raw pointers of both trials: no handle of a particular kind is needed)
+    routes = ["chip_tables" if chip_tables else prolong_route(c._has_cu_handle, f._has_cu_handle, c.chip, f.chip, tables)
+              for (c, f), tables, chip_tables in zip(pairs, by_tables, by_chip_tables)]
     for (c, f), route in zip(pairs, routes):
         for s in (c, f):
             if route in ("cu", "tables"):
                 s._require_cu_handle("prolong")
-            elif s._wide is None:
+            elif route == "chip" and s._wide is None:
                 raise ValueError(f"prolong: a trial of {s.nx} x {s.ny} cells has no whole-chip handle")
             if (torch.cuda.current_device() if s.device.index is None else s.device.index) != index:
                 raise ValueError("prolong: all trials must be on one device")
-        if route == "tables" and not (_same_extent(c.params.Lx, f.params.Lx) and _same_extent(c.params.Ly, f.params.Ly)):
+        if route in ("tables", "chip_tables") and not (_same_extent(c.params.Lx, f.params.Lx) and _same_extent(c.params.Ly, f.params.Ly)):
             raise ValueError(f"prolong: the trials of a pair cover one domain, got Lx, Ly = {c.params.Lx}, {c.params.Ly} and "
                              f"{f.params.Lx}, {f.params.Ly}")
     cu = [pair for pair, route in zip(pairs, routes) if route == "cu"]
     chip = [pair for pair, route in zip(pairs, routes) if route == "chip"]
     tables = [pair for pair, route in zip(pairs, routes) if route == "tables"]
-    if chip or tables:  # (the library checks the pairs of ONE of its calls together; with others beside them the rule is kept here)
+    chip_tables = [pair for pair, route in zip(pairs, routes) if route == "chip_tables"]
+    if chip or tables or chip_tables:  # (the library checks the pairs of ONE of its calls together; with others beside them the rule is kept here)
         for q, (_, f) in enumerate(pairs):
             if any(f is c2 or (r != q and f is f2) for r, (c2, f2) in enumerate(pairs)):
                 raise ValueError("prolong: a fine trial is the coarse or the fine trial of another pair of the call")
     with torch.cuda.device(dev):
         jobs = [f._prolong_tables_job(c) for c, f in tables]
+        chip_jobs = [f._prolong_tables_job(c) for c, f in chip_tables]
         with ldc_lib.resident_lock(index):
             stream = torch.cuda.current_stream(dev).cuda_stream
             if cu:
@@ -519,6 +533,8 @@ def prolong(pairs):
                 F.wide_prolong_enqueue(c._wide, f._wide, stream)
             if jobs:
                 F.prolong_tables_enqueue(jobs, stream)
+            if chip_jobs:
+                F.wide_prolong_tables_enqueue(chip_jobs, stream)
             torch.cuda.current_stream(dev).synchronize()      # (the lock goes back with the CUs free)
     for _, f in pairs:
         f._post = None
@@ -816,7 +832,8 @@ class FVSolver(LidDrivenCavitySolver):
     """Collocated finite-volume SIMPLE solver; ``nx`` x ``ny`` cells (8 ... 256 each with ``mapping="cu"``, one
     work-group per trial; 8 ... 1024 with ``mapping="chip"``, one launch per phase over the whole chip, and with
     ``mapping="shared"``, the same launches shared by all trials of a batch).  ``streamfunction()``, ``vorticity()``,
-    ``vortex_metrics="chip"``, ``prolong`` and ``start_from`` take a chip or shared trial of any of these sizes."""
+    ``vortex_metrics="chip"``, ``prolong`` and ``start_from`` take a chip or shared trial of any of these sizes; a chip trial
+    on a stretched mesh (``chip_grid="tables"``) starts from another trial with ``chip_transfer="tables"``."""
 
     Parameters = FVParameters
     rho = 1.0
@@ -871,6 +888,20 @@ class FVSolver(LidDrivenCavitySolver):
         if p.transfer not in TRANSFERS:
             raise ValueError(f"transfer={p.transfer!r}: 'uniform' or 'tables'")
         self.transfer_tables = p.transfer == "tables"       # prolong() routes the pairs this trial is the FINE one of on it
+        if p.chip_transfer not in CHIP_TRANSFERS:
+            raise ValueError(f"chip_transfer={p.chip_transfer!r}: 'uniform' or 'tables'")
+        self.chip_transfer_tables = p.chip_transfer == "tables"     # likewise, through ldc_fv_wide_prolong_tables_enqueue
+        if self.chip_transfer_tables:
+            if p.mapping != "chip":
+                raise ValueError(f"chip_transfer='tables' with mapping={p.mapping!r}: the transfer over the whole chip that "
+                                 f"reads the grids from tables starts a lone mapping='chip' trial (a one-CU trial takes "
+                                 f"transfer='tables')")
+            if self.transfer_tables:
+                raise ValueError("chip_transfer='tables' beside transfer='tables': one transfer per trial, and transfer="
+                                 "'tables' is the one-CU kernel's (mapping='cu')")
+            if p.grid == "tanh" and p.chip_grid != "tables":
+                raise ValueError(f"chip_transfer='tables' with grid='tanh' and chip_grid={p.chip_grid!r}: a stretched chip "
+                                 f"trial takes chip_grid='tables'")
         if self.transfer_tables and p.mapping != "cu":
             raise ValueError(f"transfer='tables' with mapping={p.mapping!r}: the transfer that reads the grids from tables "
                              f"takes mapping='cu' trials")
@@ -896,7 +927,7 @@ class FVSolver(LidDrivenCavitySolver):
             if p.acceleration != "none":
                 raise ValueError(f"grid='tanh' with acceleration={p.acceleration!r}: Anderson mixing has not been tested "
                                  f"on stretched grids, give the trial acceleration='none'")
-            if self._needs_cu_handle and not self.transfer_tables:
+            if self._needs_cu_handle and not (self.transfer_tables or self.chip_transfer_tables):
                 raise ValueError("grid='tanh' with solver=fv/fsg: the prolongation between the levels assumes equal "
                                  "spacing, run the trial with solver=fv (or give it transfer='tables', the transfer that "
                                  "reads the grids of both levels from tables)")
@@ -946,7 +977,8 @@ class FVSolver(LidDrivenCavitySolver):
             raise ValueError(f"vortex_metrics='chip' with mapping={p.mapping!r}: the post-processing chain over the whole "
                              f"chip takes mapping='chip' or 'shared' trials")
         self._has_cu_handle = not self.chip or max(nx, ny) <= F.MAX_N
-        if self._needs_cu_handle and not self._has_cu_handle:
+        # (with chip_transfer="tables" the levels are prolonged over the whole chip: no level needs the one-CU handle)
+        if self._needs_cu_handle and not self._has_cu_handle and not self.chip_transfer_tables:
             raise ValueError(f"{self._needs_cu_handle} of {nx} x {ny} cells: the prolongation takes at most {F.MAX_N} "
                              f"cells per axis")
         if p.vortex_metrics == "device" and not self._has_cu_handle:

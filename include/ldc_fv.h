@@ -2,7 +2,7 @@
  * csrc/ldc_fv_prolong.hip, csrc/ldc_fv_anderson.hip, csrc/ldc_fv_wide.hip with csrc/ldc_fv_wide_anderson.inc and
  * csrc/ldc_fv_wide_pressure.inc and csrc/ldc_fv_wide_stretched.inc and csrc/ldc_fv_wide_separable.inc, csrc/ldc_fv_sample.hip, csrc/ldc_fv_cu_pressure.hip, csrc/ldc_fv_wall_post.hip,
  * csrc/ldc_fv_stretched.hip, csrc/ldc_fv_stretched_sep.hip, csrc/ldc_fv_wall_post_stretched.hip,
- * csrc/ldc_fv_prolong_tables.hip).
+ * csrc/ldc_fv_prolong_tables.hip, csrc/ldc_fv_wide_prolong_tables.hip with csrc/ldc_fv_prolong_tables_cells.inc).
  *
  * The reference's other solver (src/solvers/fv/ and src/shared/meshing/): a collocated finite-volume SIMPLE
  * iteration on a uniform nx x ny Cartesian grid of the lid-driven cavity.  One work-group advances one trial for a
@@ -265,7 +265,8 @@
  *  - not for such a handle, each LDC_E_ARG before any device call: Anderson mixing (ldc_fv_wide_set_anderson, in either
  *    order), a batch (ldc_fv_wide_batch_create: the 256-byte table entry is full, and a stretched trial must never run the
  *    uniform kernels unnoticed), ldc_fv_wide_post_enqueue and ldc_fv_wide_prolong_enqueue (equal spacing).  The wall rule of
- *    such a trial is ldc_fv_wall_stretched_post_enqueue, which takes raw pointers and every size.
+ *    such a trial is ldc_fv_wall_stretched_post_enqueue, its coarse-to-fine transfer ldc_fv_wide_prolong_tables_enqueue (below);
+ *    both take raw pointers and every size.
  *
  * The separable scaled preconditioner of a chip trial (ldc_fv_wide_set_preconditioner; csrc/ldc_fv_wide_separable.inc, inside
  * the wide unit).  A lone ldc_fv_wide handle with geometry tables takes the tables of "The separable scaled preconditioner"
@@ -300,7 +301,9 @@
  *    the solve;
  *  - prolong: a launch for u, v, p at the fine cells (every thread recomputes the interpolated p at fine cell 0, so
  *    p[0] is exactly 0.0) and one for mdot, LDC_FV_WIDE_GROUPS of the fine trial each; the arithmetic of
- *    ldc_fv_prolong_enqueue with no multiply-add contracted, so the fine u, v, p, mdot are its bits.
+ *    ldc_fv_prolong_enqueue with no multiply-add contracted, so the fine u, v, p, mdot are its bits.  It is the transfer of
+ *    two EQUALLY SPACED chip trials; a chip trial on either grid is also served by ldc_fv_wide_prolong_tables_enqueue (below),
+ *    which reads both grids from tables.
  *
  * Sampling at the nodes of a tensor grid (csrc/ldc_fv_sample.hip, ldc_fv_sample_nodes): the initial guess of a spectral
  * trial from a finite-volume state of the same cavity.  A job holds raw device pointers only, no handle, so a trial of any
@@ -417,6 +420,22 @@
  *    centres go to LDS first, one bisection per thread; then the cells; then the faces, a barrier between the phases.  A job's
  *    result does not depend on what else is in the call, bit for bit;
  *  - written: the fine u, v, p (ny x nx each) and mdot (LDC_FV_FACES), nothing else: no ctrl, no rec, no work vector.
+ *
+ * The same transfer over the whole chip (csrc/ldc_fv_wide_prolong_tables.hip, ldc_fv_wide_prolong_tables_enqueue; a unit of its
+ * own, every other code object stays what it was): the job struct, the tables, the checks and the arithmetic above -- one
+ * definition for both units, csrc/ldc_fv_prolong_tables_cells.inc, no multiply-add contracted -- for LDC_FV_MIN_N ..
+ * LDC_FV_WIDE_MAX_N cells per axis on both sides, so a pair that both entries take gets the same bits from either.  The
+ * source may be a trial of any mapping and grid; the coarse state is only read.
+ *  - the mapping is the chip mapping's: LDC_FV_WIDE_PROLONG_TABLES_LAUNCHES = 2 launches per job, `cells` and `faces`, of
+ *    LDC_FV_WIDE_GROUPS(fine_nx, fine_ny) work-groups of 256 threads each (a grid that depends on the fine sizes alone), the
+ *    launch boundary the only barrier between work-groups, no work-group reading what another of the same launch writes, no
+ *    scratch in global memory, no atomics, no waits.  The jobs of a call are launched one after another, each job travelling
+ *    by value in the kernel arguments;
+ *  - `cells`: every work-group fills its own LDS with (k, t) of all fine_nx + fine_ny fine centres (at most 2048 entries,
+ *    24 KB, eight bisections per thread) and, after one work-group barrier, strides over the fine cells; every thread forms
+ *    the interpolated p at fine cell 0 for itself.  `faces` strides over the x faces, then the y faces.  (k, t) of a centre
+ *    does not depend on who computes it: a job's result does not depend on the grouping or on the other jobs, bit for bit;
+ *  - written: the fine u, v, p and mdot, nothing else: no ctrl, no rec, no work vector, no scratch of the solve, no table.
  */
 #ifndef LDC_FV_H
 #define LDC_FV_H
@@ -501,6 +520,8 @@ extern "C" {
 #define LDC_FV_WALL_STRETCHED_TABLE_LEN(n) ((int64_t)(n) * ((int64_t)(n) + 2))
 /* ldc_fv_prolong_tables_enqueue: jobs per launch (152 bytes per job in the arguments) */
 #define LDC_FV_PROLONG_TABLES_LAUNCH_MAX 23
+/* ldc_fv_wide_prolong_tables_enqueue: launches per job (cells | faces) */
+#define LDC_FV_WIDE_PROLONG_TABLES_LAUNCHES 2
 
 /* intermediates of ldc_fv_step_debug (bit k of `which` selects out[k]) and their lengths */
 #define LDC_FV_DBG_GRAD_P 0        /* 2n: d/dx p, then d/dy p                                    */
@@ -640,8 +661,8 @@ struct ldc_fv_prolong_tables_job {
   const double *fine_xc, *fine_yc; /* the fine cell centres (fine_nx), (fine_ny) */
   double Lx, Ly;                  /* > 0: the domain of both trials */
   double rho;                     /* > 0: the fine trial's */
-  int32_t coarse_nx, coarse_ny;   /* LDC_FV_MIN_N .. LDC_FV_MAX_N each */
-  int32_t fine_nx, fine_ny;       /* LDC_FV_MIN_N .. LDC_FV_MAX_N each */
+  int32_t coarse_nx, coarse_ny;   /* LDC_FV_MIN_N .. LDC_FV_MAX_N each (ldc_fv_wide_prolong_tables_enqueue: .. LDC_FV_WIDE_MAX_N) */
+  int32_t fine_nx, fine_ny;       /* likewise */
 };
 
 typedef struct ldc_fv ldc_fv;
@@ -835,6 +856,14 @@ int ldc_fv_wall_stretched_post_launches(int n);
 int ldc_fv_prolong_tables_enqueue(const struct ldc_fv_prolong_tables_job *jobs, int n, void *stream);
 /* Kernel launches of that call: 1 per group of LDC_FV_PROLONG_TABLES_LAUNCH_MAX jobs.  Needs no device; LDC_E_ARG for n < 1. */
 int ldc_fv_prolong_tables_launches(int n);
+/* The same jobs over the whole chip: sizes LDC_FV_MIN_N .. LDC_FV_WIDE_MAX_N on both sides, ldc_fv_wide_prolong_tables_launches(n) */
+/* launches on `stream`, two per job (LDC_FV_WIDE_GROUPS of the fine trial work-groups of 256 threads each), job after job,     */
+/* nothing synchronises.  Validation is that of ldc_fv_prolong_tables_enqueue with the larger size bound, before any launch and  */
+/* without a device: every refusal is LDC_E_ARG; then LDC_E_NODEVICE.  A refused call launches nothing.  The bits of a job are   */
+/* those of ldc_fv_prolong_tables_enqueue wherever both take it.                                                               */
+int ldc_fv_wide_prolong_tables_enqueue(const struct ldc_fv_prolong_tables_job *jobs, int n, void *stream);
+/* Kernel launches of that call: LDC_FV_WIDE_PROLONG_TABLES_LAUNCHES per job.  Needs no device; LDC_E_ARG for n < 1. */
+int ldc_fv_wide_prolong_tables_launches(int n);
 
 #ifdef __cplusplus
 }
