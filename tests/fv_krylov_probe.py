@@ -66,15 +66,19 @@ def bicg_shapes(shapes, mode):
 
 
 # ---------------------------------------------------------------------------------------------- the seeded state
+def seed_fields(X, Y):
+    """(u, v, p) of the seeded state at the cell centres X, Y in [0, 1] (2-D arrays); p of cell 0 is 0."""
+    u = 0.5 * np.sin(np.pi * X) * np.cos(2 * np.pi * Y) + 0.1 * np.sin(3 * np.pi * X * Y)
+    v = -0.4 * np.cos(np.pi * X) * np.sin(2 * np.pi * Y) + 0.1 * np.cos(2 * np.pi * (X - Y)) * np.sin(np.pi * X) * np.sin(np.pi * Y)
+    p = 0.3 * np.cos(np.pi * X) * np.cos(np.pi * Y)
+    return u, v, p - p.flat[0]
+
+
 def seeded(o):
     """A developed, non-solenoidal state on an ``FVState`` (or a subclass): all four face fluxes take both signs.  Returns
     (u, v, p, mdot) flattened as include/ldc_fv.h lays them out, for ``FVSolver.set_state``."""
     nx, ny = o.nx, o.ny
-    X, Y = np.meshgrid((np.arange(nx) + 0.5) / nx, (np.arange(ny) + 0.5) / ny)
-    u = 0.5 * np.sin(np.pi * X) * np.cos(2 * np.pi * Y) + 0.1 * np.sin(3 * np.pi * X * Y)
-    v = -0.4 * np.cos(np.pi * X) * np.sin(2 * np.pi * Y) + 0.1 * np.cos(2 * np.pi * (X - Y)) * np.sin(np.pi * X) * np.sin(np.pi * Y)
-    p = 0.3 * np.cos(np.pi * X) * np.cos(np.pi * Y)
-    p = p - p.flat[0]
+    u, v, p = seed_fields(*np.meshgrid((np.arange(nx) + 0.5) / nx, (np.arange(ny) + 0.5) / ny))
     ux, vy = o.faces(u, v)
     fx, fy = o.rho * ux * o.dy, o.rho * vy * o.dx
     fx[:, 0] = fx[:, -1] = 0.0
@@ -267,6 +271,11 @@ def threshold_case(nx, ny):
     is below the threshold, and that solve stops at K."""
     o = _state(nx, ny, "consistent", THRESHOLD_K, None, "none", 1e-12, 1e-300)
     seeded(o)
+    return threshold_of(o)
+
+
+def threshold_of(o):
+    """``threshold_case`` of a seeded restatement whose CG is capped at THRESHOLD_K with a pressure_tol it cannot meet."""
     o.step()
     b = o.last["b"].ravel()
     r = (o.last["b"] - o.apply(o.last["wx"], o.last["wy"], o.last["x"])).ravel()
