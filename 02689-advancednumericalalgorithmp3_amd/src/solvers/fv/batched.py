@@ -20,7 +20,7 @@ cells / 256) each, so a handful of trials already spreads over the chip where th
 A trial is the same launches' work alone and in a batch: its results are bit-identical to its lone ``mapping="chip"``
 or ``"shared"`` solve.  A chunk hands every live trial a quota of iterations and everyone else quota 0, so finished
 trials stay in the batch object and cost empty work-groups; a trial whose momentum solves need more BiCGSTAB launches
-than the chunk carried is enqueued again on its own with twice the budget (``solver.advance_batch_with_budget``).
+than the chunk carried is enqueued again on its own with twice the budget (``budget.advance_with_retries``).
 
 ``BatchedFVFSGSolver`` is the same for coarse-to-fine sequences (solvers.fv.fsg): stage by stage, every stage a batch of
 ordinary trials, one ``prolong`` call between stages, which splits its pairs by route: ``grid="tanh"`` trials with
@@ -37,7 +37,7 @@ import numpy as np
 from ..base import WARMUP_ITERATIONS
 from . import ldc_fv_lib as F
 from .fsg import FVFSGSolver, level_tolerance
-from .solver import WALL_RULES, FVSolver, SharedBatch, advance, postprocess, prolong
+from .solver import WALL_RULES, FVSolver, SharedBatch, advance, device_index, postprocess, prolong
 
 log = logging.getLogger(__name__)
 
@@ -110,9 +110,7 @@ class BatchedFVSolver:
         except BaseException:                 # the handles of the trials already built
             self.close()
             raise
-        import torch
-        devs = {(d.type, torch.cuda.current_device() if d.index is None else d.index)
-                for d in (s.device for s in self.solvers)}
+        devs = {(s.device.type, device_index(s.device)) for s in self.solvers}
         if len(devs) != 1:
             self.close()
             raise ValueError(f"all trials of a batch must be on one device, got {sorted(devs)}")

@@ -3,7 +3,7 @@
 The counterpart of ``solvers.spectral.fsg`` for ``solver=fv`` (conf/solver/fv/fsg.yaml).  Every level is an ordinary
 ``FVSolver`` -- the fine trial's parameters at the level's own nx and ny, so its lid profile is that of its own mesh --
 solved by the same ``_begin`` / ``_advance`` loop as a lone trial; the coarsest level starts from rest, every other from
-the prolongation of the level below (``solver.prolong``: ``ldc_fv_prolong_enqueue``, one work-group per pair, the state
+the prolongation of the level below (``transfer.prolong``: ``ldc_fv_prolong_enqueue``, one work-group per pair, the state
 never leaves the device).  ``start_from`` is the same transfer from ANY other FV trial of the device, whatever its grid
 and parameters: continuation in Re is ``start_from`` at equal size.  With ``grid="tanh"`` the trial needs
 ``transfer="tables"``: every level is then a stretched ``FVSolver`` of the same stretch, pressure equation and preconditioner
